@@ -1,16 +1,27 @@
 #!/usr/bin/env python
 """Headline benchmark: GP fit + predict on synthetic N x d fp64 tables (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c4|c5] [--map-evals E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c4|c5] [--map-evals E] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs when ``--dump-outputs DIR``
+is given (DIR/<name>.npy, float64: grid mean / variance, hyper-parameters, NLML; the inputs are seeded, so two builds can
+be compared output for output) and prints ONE JSON line: ``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` (= K timed steps / K) and the configuration.  Everything else below -- roofline, kbuild, phases,
+fit_quality, the CPU baselines, the side configurations, ``comm`` and the one-GPU check of a multi-GPU run -- takes runs of
+its own and comes with ``--full`` only.
 
 One GPU (default; BASELINE.json configs[2] = C3, the largest single-GPU configuration: N = 50k, d = 8,
 Matern-5/2 ARD, M = 10^4 grid).  A *step* is one pass of the hot path the reference reaches through
 ``gp.fit()`` + ``gp.predict_grid()``, inputs already resident in HBM:
 
-    find_MAP  -- L-BFGS-B on -(log-lik + log-priors) TO CONVERGENCE (scipy defaults, what pm.find_MAP runs);
-                 every objective / gradient evaluation = covariance build -> Cholesky -> v = L^-1 y, log-det
-                 -> L^-T, Sigma^-1, fused trace reductions
+    evaluate  -- ONE MAP objective + gradient evaluation at the declared model's starting hyper-parameters (the
+                 fit's first evaluation; fixed, so every run and every build computes the same numbers) =
+                 covariance build -> Cholesky -> v = L^-1 y, log-det -> L^-T, Sigma^-1, fused trace reductions
     predict   -- mean / variance on the M-point grid against the resident factor     (all in libgumbi_hip.so)
+
+``--map-evals k`` replaces the evaluation by L-BFGS-B on -(log-lik + log-priors) with at most k evaluations
+(``--map-evals 200``: TO CONVERGENCE, scipy defaults, what pm.find_MAP runs: ~30 evaluations = 53 s at C3); with
+``--full`` the default line also carries that whole fit as ``fit_to_convergence`` (GUMBI_BENCH_NO_FIT=1 leaves it out).
 
 The model is declared as a Gumbi user who knows the scale of the inputs would: ``ls_bounds`` (the reference's own
 knob, pymc/GP.py:630-650, built with ``make_deltas_parray``) says "length scales of at least LS_LOWER_Z standard
@@ -20,14 +31,13 @@ plateau having learnt nothing; that run is kept as the side figure
 ``fit_quality`` says what the timed fits found: RMSE / correlation of the grid mean against the generator's
 noise-free f, sigma-hat against the generator's, the final NLML, evaluations, scipy's convergence flag.
 
-``value`` = algorithmic GFLOP/s of the whole step; ``ms_per_step`` = fit + predict wall time.  Warm-up steps run
-the same code path with the evaluation budget capped at WARMUP_EVALS (they are untimed; a full fit is ~30
-evaluations = 55 s at C3).  The same JSON line carries ``roofline`` (the Cholesky's trailing-update SYRK/GEMM
+``value`` = algorithmic GFLOP/s of the whole step; ``ms_per_step`` = its wall time.  Warm-up steps run
+the same code path (a fit's with the evaluation budget capped at WARMUP_EVALS; they are untimed).  With ``--full`` the same JSON line carries ``roofline`` (the Cholesky's trailing-update SYRK/GEMM
 launches alone -- the kernel the north star's MFMA target is stated on -- from per-launch HIP events of a few
 profiled evaluations after the timed region, plus the same figure over every GEMM launch, plus the register-only
 MFMA ceiling sampled for >= 1 s BEFORE and AFTER the timed region), ``kbuild`` (HBM GB/s of the covariance build),
 ``phases``, ``cpu_baseline`` (the oracle on a bounded sample on the host cores) and, while the time budget
-(GUMBI_BENCH_BUDGET_S, default 1400 s of process time: a quarter of the driver's 1800 s stays free) allows, ``c2_single_gpu`` (the N = 10k fit whose factorisation is ONE
+(GUMBI_BENCH_BUDGET_S, default 500 s of process time: a --full run ends within 10 minutes) allows, ``c2_single_gpu`` (the N = 10k fit whose factorisation is ONE
 launch of the persistent tile kernel: step, phases, the launch's roofline), ``strong_scaling_base_gflops`` / ``c5_single_gpu``
 (the N = 100k problem of the multi-GPU runs on this one GPU), ``default_start`` and ``end_to_end`` (the user-level
 ``DataSet -> GP.fit() -> prepare_grid() -> predict_grid()`` wall time, host transfers included).
@@ -41,7 +51,7 @@ configs[4] = C5, N = 100k, d = 8, RBF-ARD -- factored block-cyclically over all 
 MAP objective + gradient evaluation (factorise + row-partitioned gradient) + re-factorisation (``fit`` at fixed
 theta) + prediction of the 10^4 grid sharded over the ranks.  ``--map-evals k``: a step = a distributed
 ``GP(distributed=True).find_MAP(maxeval=k)`` from the same declared model + the grid prediction.  ``scaling`` is
-"strong" (the same problem at every N); the line carries ``comm`` (transport, rank count as RCCL reports it,
+"strong" (the same problem at every N); with ``--full`` the line carries ``comm`` (transport, rank count as RCCL reports it,
 per-phase collective time and how much of it nothing hid -- gmb_timings.dist_*) and
 ``strong_scaling_base_gflops``: the same step on ONE GPU of the same node, run by rank 0 after the timed region.
 The barrier / max-over-ranks timing contract is the same.
@@ -177,14 +187,17 @@ def build_gp(cfg, device, ls_lower=LS_LOWER_Z, distributed=None):
 
 
 class Budget:
-    """Wall-clock budget of the whole process (the driver gives a run 1800 s): side sections are skipped, and
+    """Wall-clock budget of the whole process (a --full run must end within 10 minutes): side sections are skipped, and
     say so in the JSON, when starting them would overrun it; the timed steps never are."""
 
     def __init__(self):
-        self.total = float(os.environ.get("GUMBI_BENCH_BUDGET_S", "1400"))
+        self.total = float(os.environ.get("GUMBI_BENCH_BUDGET_S", "500"))
 
     def used(self):
         return time.perf_counter() - T_PROCESS_START
+
+    def left(self):
+        return self.total - self.used()
 
     def allows(self, estimate_s):
         return self.used() + estimate_s <= self.total
@@ -328,7 +341,7 @@ def cpu_config_size_sections(budget, gpu_c2=None):
 
     def host_fit(maxeval, est):
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--cpu-fit", "c2"], cwd=str(ROOT), capture_output=True, text=True,
-                           timeout=est * 1.5 + 60.0, env=dict(os.environ, GUMBI_BENCH_NO_CPU="1", GUMBI_BENCH_CPU_FIT_MAXEVAL=str(maxeval)))
+                           timeout=min(est * 1.5 + 60.0, max(budget.left(), est)), env=dict(os.environ, GUMBI_BENCH_NO_CPU="1", GUMBI_BENCH_CPU_FIT_MAXEVAL=str(maxeval)))
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if r.returncode == 0 and line:
             return json.loads(line[-1])
@@ -376,7 +389,7 @@ def cpu_config_size_sections(budget, gpu_c2=None):
     est_c3 = 75.0  # (measured: 43 - 45 s for the factorisation + ~15 s to fill 20 GB)
     if budget.allows(est_c3):
         try:
-            out.update(cpu_dpotrf_seconds(CONFIGS["c3"]["N"]))
+            out.update(cpu_dpotrf_seconds(CONFIGS["c3"]["N"], timeout_s=max(budget.left(), est_c3)))
         except Exception as err:  # noqa: BLE001
             out["c3_cholesky_seconds"] = None
             out["c3_cholesky"] = {"error": f"{type(err).__name__}: {err}"[:300]}
@@ -389,7 +402,23 @@ def cpu_config_size_sections(budget, gpu_c2=None):
     return out
 
 
-def cpu_dpotrf_seconds(N):
+def cpu_dpotrf_seconds(N, timeout_s=None):
+    """``cpu_dpotrf_in_process`` in a process of its own (``python bench.py --cpu-dpotrf N``): a crash of the host LAPACK (the
+    threaded dpotrf of some OpenBLAS builds dies on a 50k matrix) or a run past ``timeout_s`` is reported, not fatal to the bench."""
+    import subprocess
+
+    try:
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--cpu-dpotrf", str(int(N))], cwd=str(ROOT), capture_output=True,
+                           text=True, timeout=timeout_s)
+    except subprocess.TimeoutExpired:
+        return {"c3_cholesky_seconds": None, "c3_cholesky": {"skipped": f"time budget: the host dpotrf did not finish in {timeout_s:.0f} s"}}
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    if r.returncode == 0 and line:
+        return json.loads(line[-1])
+    return {"c3_cholesky_seconds": None, "c3_cholesky": {"error": f"host dpotrf process exited with {r.returncode}: {(r.stderr or r.stdout)[-200:]}"}}
+
+
+def cpu_dpotrf_in_process(N):
     """LAPACK dpotrf (scipy.linalg.cholesky, in place, all BLAS threads) on an N x N SPD matrix -- what PyTensor's Cholesky op
     dispatches to once per objective evaluation.  The values do not matter for the time; the matrix is N I + 0.5."""
     import scipy.linalg
@@ -669,7 +698,11 @@ class Clock:
 # -----------------------------------------------------------------------------------------------------
 # workload A: MAP fit + grid prediction of one table on ONE GPU (C1 / C2 / C3)
 # -----------------------------------------------------------------------------------------------------
-def map_fit_workload(cfg, config_name, local_rank, steps, warmup, map_evals, clock):
+def map_fit_workload(cfg, config_name, local_rank, steps, warmup, map_evals, clock, full=True):
+    """The timed steps: ``map_evals`` k > 0 -- a step = find_MAP(maxeval=k) + grid prediction (k = 200: the fit to
+    convergence); 0 -- a step = ONE MAP objective + gradient evaluation at the declared model's starting hyper-parameters
+    (the fit's first evaluation, gmb_evaluate) + grid prediction against the factor it leaves.  ``full`` adds what the
+    --full line carries beyond them (MFMA ceilings, the profiled pass behind `roofline`, phases, the tile trace, fit_quality)."""
     import torch
 
     from gumbi_amd import engine as E
@@ -686,33 +719,58 @@ def map_fit_workload(cfg, config_name, local_rank, steps, warmup, map_evals, clo
     var_dev = torch.empty(M, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     maxeval = map_evals if map_evals > 0 else 200
+    fit_mode = map_evals > 0
+    theta_start = gp._initial_theta()
+    last = {}
 
     def one_step(budget=maxeval):
-        gp.find_MAP(maxeval=budget)
+        if fit_mode:
+            gp.find_MAP(maxeval=budget)
+        else:
+            last["nlml"], last["grad"] = eng.evaluate(theta_start)  # the factor stays resident: no re-factorisation
         eng.predict_device(xs_dev.data_ptr(), M, cfg["d"], mean_dev.data_ptr(), var_dev.data_ptr(), True)
-        return gp.n_eval, gp.n_refactor
+        return (gp.n_eval, gp.n_refactor) if fit_mode else (1, 0)
 
     for _ in range(warmup):
         one_step(min(maxeval, WARMUP_EVALS))
     torch.cuda.synchronize()
-    ceiling_before = E.mfma_f64_sustained(local_rank, 1.0)  # register-only MFMA loop, >= 1 s, right before the timed region
+    if full:
+        ceiling_before = E.mfma_f64_sustained(local_rank, 1.0)  # register-only MFMA loop, >= 1 s, right before the timed region
     clock.sync()
     t0 = time.perf_counter()
     counts = [one_step() for _ in range(steps)]
     n_evals = [c[0] for c in counts]
     clock.sync()
     elapsed = time.perf_counter() - t0
-    ceiling_after = E.mfma_f64_sustained(local_rank, 1.0)   # ... and right after it
     mean_host = mean_dev.cpu().numpy()
     var_host = var_dev.cpu().numpy()
     finite = bool(np.all(np.isfinite(mean_host)) and np.all(var_host > 0))
-    quality = fit_quality(gp, mean_host, cfg)
-    theta_fit = gp._theta_fitted.copy()
+    theta_fit = gp._theta_fitted.copy() if fit_mode else np.array(theta_start, dtype=np.float64)
+    N = cfg["N"]
+    # what the last timed step hands its caller: the (MAP) hyper-parameters, the objective (and gradient), the grid mean / variance
+    outputs = {"mean": mean_host.copy(), "var": var_host.copy(), "theta": theta_fit.copy()}
+    if fit_mode:
+        outputs["nlml"] = np.array([gp.nlml_trace[-1] if gp.nlml_trace else np.nan])
+    else:
+        outputs["nlml"], outputs["grad"] = np.array([last["nlml"]]), np.array(last["grad"], dtype=np.float64)
+    timed = dict(elapsed=elapsed, n_evals=n_evals, n_refactor=[c[1] for c in counts], M=M, finite=finite,
+               flops=sum(step_flops(N, M, n, r) for n, r in counts), outputs=outputs)
+    if not full:
+        eng.close()
+        gp.engine = None
+        return timed
+    ceiling_after = E.mfma_f64_sustained(local_rank, 1.0)   # ... and right after it
+    quality = fit_quality(gp, mean_host, cfg) if fit_mode else None
     # Roofline pass: a few more evaluations + one prediction of the same workload with a HIP event pair around
     # every GEMM launch (on the stream it is launched on).  Kept out of the timed region: event pairs cost host
     # time per launch.
     eng.set_profiling(True)  # resets the totals
-    one_step(min(maxeval, PROFILE_EVALS))
+    if fit_mode:
+        one_step(min(maxeval, PROFILE_EVALS))
+    else:
+        for _ in range(PROFILE_EVALS - 1):
+            eng.evaluate(theta_start)
+        one_step()
     torch.cuda.synchronize()
     tm = eng.timings()
     eng.set_profiling(False)
@@ -750,14 +808,13 @@ def map_fit_workload(cfg, config_name, local_rank, steps, warmup, map_evals, clo
     phases["predict_after_fit_ms"] = wall_ms(predict)
     phases["predict_after_fit_form"] = "gemm against the resident inverse factor" if eng.timings().get("predict_gemm_form") else "triangular solve"
     phases["ls_limits_ms"] = wall_ms(lambda: gp._prepare_lengthscales(gp.model.X, ARD=True))
-    N = cfg["N"]
     phases["rates_tflops"] = {
         "factorize": round(N**3 / 3.0 / phases["factorize_ms"] / 1e9, 2),
         "map_evaluation": round(float(N) ** 3 / phases["factorize_plus_gradient_ms"] / 1e9, 2),
         "predict": round(float(N) ** 2 * M / phases["predict_ms"] / 1e9, 2),
         "predict_after_fit": round(float(N) ** 2 * M / phases["predict_after_fit_ms"] / 1e9, 2),
     }
-    phases["at_theta"] = "the MAP of the timed fits"
+    phases["at_theta"] = "the MAP of the timed fits" if fit_mode else "the declared model's starting hyper-parameters (the timed step's)"
     phases["profiled_last_evaluation_ms"] = {k: round(tm[k], 3) for k in
                                              ("kbuild_ms", "chol_ms", "chol_leaf_ms", "chol_trsm_ms", "chol_gemm_ms",
                                               "grad_ms", "grad_gemm_ms", "predict_ms", "predict_gemm_ms")}
@@ -766,25 +823,30 @@ def map_fit_workload(cfg, config_name, local_rank, steps, warmup, map_evals, clo
     # streams per process slow every kernel down on this stack
     eng.close()
     gp.engine = None
-    return dict(elapsed=elapsed, n_evals=n_evals, n_refactor=[c[1] for c in counts], M=M, tm=tm, phases=phases, finite=finite,
-                flops=sum(step_flops(N, M, n, r) for n, r in counts), quality=quality,
+    return dict(timed, tm=tm, phases=phases, quality=quality,
                 ceiling={"before_timed_region": ceiling_before, "after_timed_region": ceiling_after})
 
 
 def c2_side_section(local_rank, clock):
     """C2 (N = 10k, d = 4, RBF-ARD, M = 10^4) as a side figure of the default run: one timed MAP fit to convergence +
     prediction (after one capped warm-up step), the phases of one evaluation at the MAP and the roofline of its
-    factorisation launch.  ``python bench.py --config c2`` is the full-length form."""
-    cfg = CONFIGS["c2"]
-    res = map_fit_workload(cfg, "c2", local_rank, 1, 1, 0, clock)
+    factorisation launch.  ``python bench.py --config c2 --map-evals 200`` is the full-length form."""
+    return fit_side_section(CONFIGS["c2"], "c2", local_rank, clock, quality_keys=("corr", "sigma_rel_err", "converged", "n_eval"))
+
+
+def fit_side_section(cfg, config_name, local_rank, clock, quality_keys=None):
+    """One timed MAP fit to convergence + grid prediction (``--map-evals 200``) after one capped warm-up step: what the fit
+    costs end to end on the GPU, what it found, the phases of one evaluation at the MAP and the roofline of its launches."""
+    res = map_fit_workload(cfg, config_name, local_rank, 1, 1, 200, clock)
     elapsed = res["elapsed"]
-    r = roofline_block(res["tm"], "c2")
+    r = roofline_block(res["tm"], config_name)
     ph = res["phases"]
+    q = res["quality"]
     return {
-        "workload": cfg["label"],
+        "workload": cfg["label"], "step": "find_MAP to convergence (cap 200 evaluations) + grid prediction",
         "ms_per_step": round(1e3 * elapsed, 3), "fit_predict_seconds": round(elapsed, 4), "map_evals": res["n_evals"],
         "value": round(res["flops"] / elapsed / 1e9, 2),
-        "unit": "GFLOP/s", "fit_quality": {k: res["quality"][k] for k in ("corr", "sigma_rel_err", "converged", "n_eval") if k in res["quality"]},
+        "unit": "GFLOP/s", "fit_quality": {k: q[k] for k in (quality_keys or q) if k in q},
         "phases": {k: ph[k] for k in ("factorize_ms", "factorize_plus_gradient_ms", "predict_ms", "predict_after_fit_ms", "predict_after_fit_first_call_ms",
                                       "predict_after_fit_form", "rates_tflops", "tile_cholesky") if k in ph},
         "factorisation_roofline": {k: r[k] for k in ("kernel", "achieved", "peak", "frac", "achieved_on_unpadded_N3", "frac_on_unpadded_N3", "launches", "avg_launch_ms", "traffic", "traffic_source", "traffic_is_stale") if k in r},
@@ -889,7 +951,7 @@ def c4_step_flops(N, P, M_rows, n_eval, n_refactor):
     return P * (n_eval * n3 + n_refactor * n3 / 3.0 + float(N) ** 2 * M_rows + 4.0 * N * M_rows)
 
 
-def c4_workload(cfg, local_rank, steps, warmup, map_evals, clock, stacked_beside=True):
+def c4_workload(cfg, local_rank, steps, warmup, map_evals, clock, stacked_beside=True, full=True):
     import torch
 
     from gumbi_amd import engine as E
@@ -916,15 +978,24 @@ def c4_workload(cfg, local_rank, steps, warmup, map_evals, clock, stacked_beside
     for _ in range(warmup):
         one_step(min(maxeval, WARMUP_EVALS))
     torch.cuda.synchronize()
-    ceiling_before = E.mfma_f64_sustained(local_rank, 1.0)
+    if full:
+        ceiling_before = E.mfma_f64_sustained(local_rank, 1.0)
     clock.sync()
     t0 = time.perf_counter()
     counts = [one_step() for _ in range(steps)]
     clock.sync()
     elapsed = time.perf_counter() - t0
-    ceiling_after = E.mfma_f64_sustained(local_rank, 1.0)
     mu, var = last["mu"], last["var"]
     finite = bool(np.all(np.isfinite(mu)) and np.all(var > 0))
+    outputs = {"mean": np.array(mu, dtype=np.float64), "var": np.array(var, dtype=np.float64), "theta": gp._theta_fitted.copy(),
+               "nlml": np.array([gp.nlml_trace[-1] if gp.nlml_trace else np.nan])}
+    timed = dict(elapsed=elapsed, n_evals=[c[0] for c in counts], n_refactor=[c[1] for c in counts], M=M_rows, finite=finite,
+               flops=sum(c4_step_flops(N, P, M_rows, n, r) for n, r in counts), outputs=outputs)
+    if not full:
+        eng.close()
+        gp.engine = None
+        return timed
+    ceiling_after = E.mfma_f64_sustained(local_rank, 1.0)
     res = getattr(gp, "opt_result", None)
     Mg = len(Xg)
     quality = {
@@ -983,8 +1054,7 @@ def c4_workload(cfg, local_rank, steps, warmup, map_evals, clock, stacked_beside
                                                 "predict": round(phases["stacked_predict_ms"] / phases["kronecker_predict_ms"], 2)}
         finally:
             st.close()
-    return dict(elapsed=elapsed, n_evals=[c[0] for c in counts], n_refactor=[c[1] for c in counts], M=M_rows, tm=tm, phases=phases,
-                finite=finite, flops=sum(c4_step_flops(N, P, M_rows, n, r) for n, r in counts), quality=quality,
+    return dict(timed, tm=tm, phases=phases, quality=quality,
                 ceiling={"before_timed_region": ceiling_before, "after_timed_region": ceiling_after})
 
 
@@ -1067,16 +1137,22 @@ COMM_KEYS = ("dist_world", "dist_chol_collectives", "dist_chol_comm_bytes", "dis
              "dist_grad_comm_ms", "dist_grad_comm_exposed_ms", "dist_lockstep_repairs")
 
 
+def comm_ranks(eng):
+    """The rank count the engine's communicator reports (RCCL), None for other transports."""
+    comm = getattr(eng, "comm", None)
+    if comm is not None and hasattr(comm, "ranks"):
+        try:
+            return comm.ranks
+        except Exception:
+            return None
+    return None
+
+
 def comm_block(tm, eng, transport, clock):
     """Communication of the LAST factorisation and the LAST gradient evaluation of the run (gmb_timings.dist_*): what
     rank 0 saw, and the maximum over the ranks of the exposed part."""
     comm = getattr(eng, "comm", None)
-    ranks = None
-    if comm is not None and hasattr(comm, "ranks"):
-        try:
-            ranks = comm.ranks
-        except Exception:
-            ranks = None
+    ranks = comm_ranks(eng)
     chol_exp, grad_exp, chol_ms, grad_ms = clock.max_over_ranks([tm["dist_chol_comm_exposed_ms"], tm["dist_grad_comm_exposed_ms"],
                                                                   tm["dist_chol_comm_ms"], tm["dist_grad_comm_ms"]])
     return {
@@ -1101,7 +1177,7 @@ def comm_block(tm, eng, transport, clock):
     }
 
 
-def one_gp_workload(cfg, world, local_rank, dist, steps, warmup, clock, map_evals=0, capacity=False):
+def one_gp_workload(cfg, world, local_rank, dist, steps, warmup, clock, map_evals=0, capacity=False, full=True):
     import torch
 
     from gumbi_amd import engine as E
@@ -1174,18 +1250,27 @@ def one_gp_workload(cfg, world, local_rank, dist, steps, warmup, clock, map_eval
         one_step(record=True)
     clock.sync()
     elapsed = time.perf_counter() - t0
-    # (what the TIMED fit found -- before the profiled pass below runs a two-evaluation fit of its own on the same object)
-    quality_timed = fit_quality(gp, last["mu"], cfg) if map_evals > 0 else None
-    eng.set_profiling(True)
+    # what the last timed step hands its caller (the profiled pass below overwrites `last`)
+    outputs = {"mean": np.array(last["mu"], dtype=np.float64), "var": np.array(last["var"], dtype=np.float64),
+               "nlml": np.array([float(last["nl"])])}
     if map_evals > 0:
-        gp.find_MAP(maxeval=min(map_evals, 2))
-        eng.predict(Xs)
+        outputs["theta"] = gp._theta_fitted.copy()
     else:
-        one_step()
-    torch.cuda.synchronize()
-    tm = eng.timings()
-    eng.set_profiling(False)
-    comm = comm_block(tm, eng, transport, clock) if world > 1 else None
+        outputs["grad"] = np.array(last["grad"], dtype=np.float64)
+    tm, comm, quality_timed = None, None, None
+    if full:
+        # (what the TIMED fit found -- before the profiled pass below runs a two-evaluation fit of its own on the same object)
+        quality_timed = fit_quality(gp, last["mu"], cfg) if map_evals > 0 else None
+        eng.set_profiling(True)
+        if map_evals > 0:
+            gp.find_MAP(maxeval=min(map_evals, 2))
+            eng.predict(Xs)
+        else:
+            one_step()
+        torch.cuda.synchronize()
+        tm = eng.timings()
+        eng.set_profiling(False)
+        comm = comm_block(tm, eng, transport, clock) if world > 1 else None
     n3 = float(N) ** 3
     if map_evals > 0:
         per = clock.max_over_ranks([part["find_map"] / steps, part["predict"] / steps])
@@ -1202,14 +1287,30 @@ def one_gp_workload(cfg, world, local_rank, dist, steps, warmup, clock, map_eval
                                        "predict": round(float(N) ** 2 * M / per[2] / 1e12, 2)},
             "nlml": float(last["nl"]),
         }
-    phases["profiled_last_step_ms_rank0"] = {k: round(tm[k], 3) for k in ("kbuild_ms", "chol_ms", "chol_gemm_ms", "grad_ms",
-                                                                         "grad_gemm_ms", "predict_ms")}
+    if full:
+        phases["profiled_last_step_ms_rank0"] = {k: round(tm[k], 3) for k in ("kbuild_ms", "chol_ms", "chol_gemm_ms", "grad_ms",
+                                                                             "grad_gemm_ms", "predict_ms")}
+    else:
+        phases.pop("fit_quality_after_k_evals", None)
     finite = bool(np.all(np.isfinite(last["mu"])) and np.all(last["var"] > 0) and np.all(np.isfinite(last["grad"])))
+    ranks = comm_ranks(eng) if world > 1 else None
     eng.close()
     if gp is not None:
         gp.engine = None
-    return dict(elapsed=elapsed, M=M, tm=tm, phases=phases, finite=finite, transport=transport, flops=flops, comm=comm,
+    return dict(elapsed=elapsed, M=M, tm=tm, phases=phases, finite=finite, transport=transport, flops=flops, comm=comm, outputs=outputs,
+                rccl_ranks=ranks,
                 last=dict(nlml=float(last["nl"]), mean=np.asarray(last["mu"], dtype=float).copy(), var=np.asarray(last["var"], dtype=float).copy()))
+
+
+def dump_outputs(directory, outputs, max_bytes=64 << 20):
+    """``--dump-outputs DIR``: every array of ``outputs`` (what the last timed step computed) as DIR/<name>.npy in float64."""
+    arrays = {name: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for name, a in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs exceed the {max_bytes} byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def run_with_deadline(fn, seconds):
@@ -1284,7 +1385,7 @@ def self_launch(args):
 def c5_fit_predict_block(c5_side):
     """fit+predict at the north star's size (N = 100k) on ONE GPU for the default line: an estimate from THIS run's measured
     evaluation (n_eval of the recorded fit x map_eval_s + prediction), labelled, beside the builder-run record of a whole
-    find_MAP to convergence (profiles/*_bench_c5_map.json, `python bench.py --config c5 --map-evals 200 --steps 1 --warmup 0`)."""
+    find_MAP to convergence (profiles/*_bench_c5_map.json, `python bench.py --config c5 --map-evals 200 --steps 1 --warmup 0 --full`)."""
     import glob
 
     out = {}
@@ -1336,18 +1437,31 @@ def main():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="default: c3 on one GPU, c5 (ONE GP over all ranks) on several")
     ap.add_argument("--map-evals", type=int, default=0,
-                    help="one GPU: cap on L-BFGS objective evaluations per fit (0 = run to convergence, cap 200); c5 / several "
-                         "GPUs: 0 = fixed hyper-parameters, k > 0 = a (distributed) find_MAP(maxeval=k) per step")
+                    help="c1 / c2 / c3 and c5 / several GPUs: 0 = fixed hyper-parameters (c1 - c3: a step = ONE MAP objective + gradient "
+                         "evaluation + grid prediction), k > 0 = a (distributed) find_MAP(maxeval=k) per step (200 = the fit to "
+                         "convergence); c4: cap on evaluations per fit (0 = run to convergence, cap 400)")
     ap.add_argument("--capacity", action="store_true",
                     help="several GPUs, fixed hyper-parameters: the multi-GPU driver's CAPACITY mode (a rank keeps its own block rows + panel "
                          "buffers; L is streamed again for the gradient and the prediction) instead of the replicated factor")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the timed steps as well: MFMA ceilings, the profiled pass behind roofline / kbuild / comm, "
+                         "phases, fit_quality, the CPU baselines, the side configurations, the one-GPU check of a multi-GPU run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (grid mean / variance, hyper-parameters, NLML, ...) as DIR/<name>.npy")
     ap.add_argument("--cpu-fit", default=None, choices=["c1", "c2"],
                     help="internal (cpu_baseline): the config's whole step on the HOST -- HipGP's host code over the numpy/LAPACK oracle")
+    ap.add_argument("--cpu-dpotrf", type=int, default=None, metavar="N",
+                    help="internal (cpu_dpotrf_seconds): LAPACK dpotrf of an N x N SPD matrix on the HOST, one JSON line")
     args = ap.parse_args()
     if args.cpu_fit:
         cpu_fit_subprocess(args.cpu_fit)
         return
+    if args.cpu_dpotrf:
+        print(json.dumps(cpu_dpotrf_in_process(args.cpu_dpotrf)), flush=True)
+        return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))  # `python bench.py --gpus N` by itself: N ranks under torch.distributed.run
@@ -1396,13 +1510,16 @@ def main():
     if config_name == "c5":
         def section():
             torch.cuda.set_device(local_rank)  # the current device is per-thread state
-            return one_gp_workload(cfg, world, local_rank, dist, args.steps, args.warmup, clock, args.map_evals, args.capacity and world > 1)
+            return one_gp_workload(cfg, world, local_rank, dist, args.steps, args.warmup, clock, args.map_evals, args.capacity and world > 1,
+                                   full=args.full)
 
         res, healthy = run_with_deadline(section, float(os.environ.get("GUMBI_BENCH_DEADLINE", "1500")))
     elif config_name == "c4":
-        res = c4_workload(cfg, local_rank, args.steps, args.warmup, args.map_evals, clock)
+        res = c4_workload(cfg, local_rank, args.steps, args.warmup, args.map_evals, clock, full=args.full)
     else:
-        res = map_fit_workload(cfg, config_name, local_rank, args.steps, args.warmup, args.map_evals, clock)
+        res = map_fit_workload(cfg, config_name, local_rank, args.steps, args.warmup, args.map_evals, clock, full=args.full)
+    if rank == 0 and args.dump_outputs and "error" not in res:
+        dump_outputs(args.dump_outputs, res["outputs"])
 
     base_last = {}
 
@@ -1426,11 +1543,14 @@ def main():
     else:
         (elapsed,) = clock.max_over_ranks([res["elapsed"]]) if healthy else (res["elapsed"],)
         if rank == 0:
-            tm = res["tm"]
+            tm = res.get("tm")
             if config_name == "c4":
                 metric = "fit+predict achieved GFLOP/s (fp64 exact 2-output ICM GP, Kronecker form: MAP fit to convergence + grid prediction)"
-            elif config_name != "c5":
+            elif config_name != "c5" and args.map_evals > 0:
                 metric = "fit+predict achieved GFLOP/s (fp64 exact GP: MAP fit to convergence + grid prediction)"
+            elif config_name != "c5":
+                metric = ("fit+predict achieved GFLOP/s (fp64 exact GP: one MAP objective + gradient evaluation at the model's starting "
+                          "hyper-parameters + grid prediction)")
             elif args.map_evals > 0:
                 metric = f"fit+predict achieved GFLOP/s (fp64 exact GP: find_MAP(maxeval={args.map_evals}) + grid prediction)"
             else:
@@ -1455,10 +1575,7 @@ def main():
                                    f"ONE GP, 128-row blocks dealt block-cyclically over {world} GPUs; panel all-gathers: {res['transport']}",
                 },
                 "fit_predict_seconds": round(elapsed / args.steps, 4),
-                "roofline": roofline_block(tm, config_name),
-                "kbuild": kbuild_block(tm),
                 "results_finite": res["finite"],
-                "phases": res["phases"],
                 # what "parity green" means for these numbers: the HIP path agrees with the numpy restatement
                 # of PyMC's formulas to ~1e-13 (tests: <= 1e-8 mean, 1e-9 variance, 1e-10 NLML); the restatement itself meets PyMC
                 # only through the outputs the reference's notebooks print
@@ -1473,8 +1590,10 @@ def main():
                 out["config"]["map_evals_per_step"] = res["n_evals"]
                 out["config"]["refactorizations_at_the_map_per_step"] = res["n_refactor"]
                 out["config"]["ls_bounds"] = f"lower = {LS_LOWER_Z} standardized units on every input (make_deltas_parray), upper = default"
-                out["config"]["warmup_step"] = f"same code path, evaluation budget {WARMUP_EVALS} (untimed)"
-                out["fit_quality"] = res["quality"]
+                out["config"]["warmup_step"] = (f"same code path, evaluation budget {WARMUP_EVALS} (untimed)" if config_name == "c4" or args.map_evals > 0
+                                                else "the same step (untimed)")
+                if res.get("quality") is not None:
+                    out["fit_quality"] = res["quality"]
                 out["seconds_per_map_evaluation"] = round(elapsed / max(sum(res["n_evals"]), 1), 4)
             if config_name == "c5":
                 out["config"]["step"] = (f"a distributed find_MAP(maxeval={args.map_evals}) + grid prediction" if args.map_evals > 0 else
@@ -1484,17 +1603,27 @@ def main():
             if world > 1:
                 out["config"]["factor_storage"] = ("capacity mode: own block rows + panel buffers per rank (gmb_dist_set_mode 1)" if args.capacity and not args.map_evals
                                                    else "replicated: every rank ends with the complete factor")
+            if world > 1:
+                # (plain runs too: the rank count costs nothing and says whether the timed run spanned the launched ranks)
+                out["transport"], out["rccl_ranks"] = res["transport"], res.get("rccl_ranks")
+                out["launcher"] = "bench.py itself (--gpus N without WORLD_SIZE)" if os.environ.get("GUMBI_BENCH_SELF_LAUNCHED") == "1" else "external (WORLD_SIZE set)"
             if res.get("comm") is not None:
                 out["comm"] = res["comm"]
                 out["transport"], out["rccl_ranks"] = res["comm"]["transport"], res["comm"]["rccl_ranks"]
                 out["comm_ms_total"], out["comm_ms_exposed"] = res["comm"]["comm_ms_total"], res["comm"]["comm_ms_exposed"]
-                out["launcher"] = "bench.py itself (--gpus N without WORLD_SIZE)" if os.environ.get("GUMBI_BENCH_SELF_LAUNCHED") == "1" else "external (WORLD_SIZE set)"
+            if world > 1:
                 if out["transport"] == "rccl" and out["rccl_ranks"] != world:
                     # the library's communicator does not span the ranks that were launched: whatever was timed is not an N-GPU run
                     out["error"] = {"error": f"RCCL communicator reports {out['rccl_ranks']} ranks, {world} were launched"}
+            if "phases" in res:
+                out["phases"] = res["phases"]
+            if tm is not None:
+                out["roofline"] = roofline_block(tm, config_name)
+                out["kbuild"] = kbuild_block(tm)
             # the two roofline fractions side by side: the dominant kernel's (a subset of the launches) and the
             # whole timed step's on its algorithmic flops
-            out["roofline_frac_dominant_kernel"] = out["roofline"]["frac"]
+            if "roofline" in out:
+                out["roofline_frac_dominant_kernel"] = out["roofline"]["frac"]
             out["roofline_frac_whole_step"] = round(out["value"] / 1e3 / FP64_MFMA_PEAK_TFLOPS, 4)
             if "ceiling" in res:
                 cb, ca = res["ceiling"]["before_timed_region"], res["ceiling"]["after_timed_region"]
@@ -1517,7 +1646,20 @@ def main():
         finally:
             sections[name] = round(time.perf_counter() - t_, 1)
 
-    if world == 1 and out is not None and "error" not in out and config_name != "c5":
+    if args.full and world == 1 and out is not None and "error" not in out and config_name != "c5":
+        if config_name != "c4" and args.map_evals <= 0 and os.environ.get("GUMBI_BENCH_NO_FIT") != "1":
+            # the headline step is one evaluation: the whole fit it belongs to (evaluations to convergence, what it found)
+            est = 1.2 * 35 * out["seconds_per_map_evaluation"] + 30.0
+            if budget.allows(est):
+                try:
+                    out["fit_to_convergence"] = timed_section("fit_to_convergence", lambda: fit_side_section(cfg, config_name, local_rank, clock))
+                except Exception as err:
+                    out["fit_to_convergence"] = {"error": f"{type(err).__name__}: {err}"[:300]}
+            else:
+                out["fit_to_convergence"] = budget.skipped(est)
+        fit_s = (out.get("fit_to_convergence") or {}).get("fit_predict_seconds") or (
+            out["fit_predict_seconds"] if config_name == "c4" or args.map_evals > 0 else 35 * out["seconds_per_map_evaluation"])
+        fit_q = out.get("fit_quality") or (out.get("fit_to_convergence") or {}).get("fit_quality")
         if not args.no_cpu_baseline and os.environ.get("GUMBI_BENCH_NO_CPU") != "1":
             out["cpu_baseline"] = timed_section("cpu_baseline", lambda: cpu_baseline_c4(cfg, res) if config_name == "c4" else cpu_baseline(cfg))
         if config_name == "c3" and os.environ.get("GUMBI_BENCH_NO_C2") != "1":
@@ -1545,7 +1687,8 @@ def main():
             # (no warm-up step: the C3 run before it has just run the very same kernels for minutes -- VERDICT r05 item 3)
             est = 45.0
             if budget.allows(est):
-                out["c5_single_gpu"], _ = timed_section("c5_single_gpu", lambda: run_with_deadline(lambda: c5_on_one_gpu(1, 0), 600.0))
+                out["c5_single_gpu"], _ = timed_section("c5_single_gpu", lambda: run_with_deadline(lambda: c5_on_one_gpu(1, 0),
+                                                                                                    min(600.0, max(budget.left(), est))))
                 out["strong_scaling_base_gflops"] = out["c5_single_gpu"].get("value")
                 out["c5_fit_predict"] = c5_fit_predict_block(out["c5_single_gpu"])
             else:
@@ -1553,7 +1696,7 @@ def main():
                 out["strong_scaling_base_gflops"] = None
         if os.environ.get("GUMBI_BENCH_NO_E2E") != "1" and config_name != "c4":
             # the user-level call sequence, declaration and host transfers inside the clock (ahead of the host's sections)
-            est = 1.1 * out["fit_predict_seconds"] + 8.0
+            est = 1.1 * fit_s + 8.0
             if budget.allows(est):
                 try:
                     out["end_to_end"] = timed_section("end_to_end", lambda: end_to_end_fit(cfg, local_rank, args.map_evals))
@@ -1563,12 +1706,12 @@ def main():
                 out["end_to_end"] = budget.skipped(est)
         if "cpu_baseline" in out and os.environ.get("GUMBI_BENCH_NO_CPU_CONFIG_SIZE") != "1" and config_name != "c4":
             # the host at the configs' own sizes (minutes of host time), beside fit_predict_seconds
-            gpu_c2 = out.get("fit_quality") if config_name == "c2" else (out.get("c2_single_gpu") or {}).get("fit_quality")
+            gpu_c2 = fit_q if config_name == "c2" else (out.get("c2_single_gpu") or {}).get("fit_quality")
             try:
                 out["cpu_baseline"].update(timed_section("cpu_config_size", lambda: cpu_config_size_sections(budget, gpu_c2)))
             except Exception as err:  # noqa: BLE001
                 out["cpu_baseline"]["config_size_error"] = f"{type(err).__name__}: {err}"[:300]
-            gpu_c2_s = out.get("fit_predict_seconds") if config_name == "c2" else (out.get("c2_single_gpu") or {}).get("fit_predict_seconds")
+            gpu_c2_s = fit_s if config_name == "c2" else (out.get("c2_single_gpu") or {}).get("fit_predict_seconds")
             out["cpu_baseline"]["gpu_c2_fit_predict_seconds"] = gpu_c2_s
             if config_name == "c3":
                 out["cpu_baseline"]["gpu_c3_cholesky_seconds"] = round(out["phases"].get("factorize_ms", 0.0) / 1e3, 4) or None
@@ -1583,7 +1726,7 @@ def main():
                 out["default_start"] = budget.skipped(est)
     # several GPUs: the same step on ONE GPU of this node, by rank 0 (the other ranks wait at the final barrier) -- the curve's
     # one-GPU point AND the check of this line: the N-rank run must have computed what one GPU computes
-    if world > 1 and out is not None and "error" not in out and healthy and os.environ.get("GUMBI_BENCH_NO_BASE") != "1":
+    if args.full and world > 1 and out is not None and "error" not in out and healthy and os.environ.get("GUMBI_BENCH_NO_BASE") != "1":
         base, _ = run_with_deadline(lambda: c5_on_one_gpu(1, 1), 500.0)
         out["strong_scaling_base"] = base
         out["strong_scaling_base_gflops"] = base.get("value")
@@ -1595,7 +1738,7 @@ def main():
                 out["error"] = {"error": "the N-rank run and the one-GPU run of the same step disagree: " + out["results_match_note"]}
     elif world == 1 and out is not None and "error" not in out and config_name == "c5":
         out["strong_scaling_base_gflops"] = out["value"]  # this IS the one-GPU point
-    if out is not None and "error" not in out:
+    if out is not None and "error" not in out and (args.full or config_name == "c5"):
         # ONE key under which every line of `--gpus 1 / 2 / 4 / 8` carries its point of the SAME curve (C5, the one-GP workload):
         # the default one-GPU line's headline is C3 (a different problem), its C5 point is the side figure
         c5_step = ("find_MAP(maxeval=%d) + grid prediction" % args.map_evals if (config_name == "c5" and args.map_evals > 0) else

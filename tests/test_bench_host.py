@@ -7,6 +7,7 @@ import time
 from pathlib import Path
 
 import numpy as np
+import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -337,14 +338,17 @@ def test_host_c2_fit_is_capped_and_extrapolated_when_the_budget_is_short(monkeyp
             {"fit_predict_seconds": 6.0 * n + 4.0, "fit_seconds": 6.0 * n, "predict_seconds": 4.0, "n_eval": n, "nlml_final": 1.0}) + "\n")
 
     monkeypatch.setattr(subprocess, "run", fake_run)
-    monkeypatch.setattr(bench, "cpu_dpotrf_seconds", lambda N: {"c3_cholesky_seconds": 44.0, "c3_cholesky": {"N": N}})
+    monkeypatch.setattr(bench, "cpu_dpotrf_seconds", lambda N, timeout_s=None: {"c3_cholesky_seconds": 44.0, "c3_cholesky": {"N": N}})
 
     class B:
         def __init__(self, left):
-            self.left = left
+            self.seconds_left = left
 
         def allows(self, est):
-            return est <= self.left
+            return est <= self.seconds_left
+
+        def left(self):
+            return self.seconds_left
 
         def skipped(self, est):
             return {"skipped": f"needs ~{est:.0f} s"}
@@ -366,3 +370,22 @@ def test_host_c2_fit_is_capped_and_extrapolated_when_the_budget_is_short(monkeyp
     # nothing left
     out = bench.cpu_config_size_sections(B(5.0), None)
     assert out["c2_seconds"] is None and "skipped" in out["c2_fit"] and "c2_one_evaluation_seconds" not in out
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path):
+    """``--dump-outputs DIR``: every output of the last timed step as DIR/<name>.npy in float64; more than 64 MB is refused."""
+    bench = load_bench()
+    outs = {"mean": np.linspace(0.0, 1.0, 10, dtype=np.float32), "theta": np.array([0.5, 1.0, 0.2]), "nlml": np.array([12.5])}
+    bench.dump_outputs(str(tmp_path / "out"), outs)
+    for name, a in outs.items():
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(a, dtype=np.float64))
+    with pytest.raises(RuntimeError, match="64"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_steps_below_one_are_refused():
+    """``--steps`` is the number of timed steps: a run without one has no ms_per_step to report."""
+    out = _run_bench(["--gpus", "1", "--steps", "0", "--warmup", "0"])
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr

@@ -740,7 +740,7 @@ def test_bench_contract_with_two_ranks_on_one_gpu(gpu, launcher, map_evals):
     head = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
             "127.0.0.1", "--master-port", str(_free_port())] if launcher == "torchrun" else [sys.executable]
     capacity = launcher.endswith("capacity")  # (--capacity: the same step with no rank holding the factor)
-    cmd = (head + [str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"] + (["--map-evals", str(map_evals)] if map_evals else [])
+    cmd = (head + [str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"] + (["--map-evals", str(map_evals)] if map_evals else [])
            + (["--capacity"] if capacity else []))
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -788,6 +788,30 @@ def test_bench_contract_with_two_ranks_on_one_gpu(gpu, launcher, map_evals):
     assert abs(d["value"] - flops / (d["ms_per_step"] * 2e-3) / 1e9) / d["value"] < 1e-3
 
 
+def test_bench_plain_two_rank_line_keeps_its_rank_check(gpu):
+    """A plain ``python bench.py --gpus 2`` (no --full) leaves out ``comm`` and the one-GPU run, but still says which transport
+    it ran on and how many ranks its communicator spans -- the check that a plain N-GPU figure is an N-GPU run."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    env = dict(os.environ, GUMBI_BENCH_SINGLE_DEVICE="1", GUMBI_BENCH_BACKEND="gloo", GUMBI_BENCH_DIST_N="3000",
+               HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], cwd=root, env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert "error" not in d and d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] > 0 and d["results_finite"]
+    assert d["transport"] == "torch-gloo" and d["rccl_ranks"] is None and d["launcher"].startswith("bench.py itself")
+    for extra in ("comm", "roofline", "strong_scaling_base", "results_match_one_gpu"):
+        assert extra not in d, extra
+
+
 def test_bench_contract_single_process(gpu):
     """``python bench.py --config c2`` (N = 1): one JSON line with the contract's keys plus ``roofline`` (the
     trailing update alone), ``cpu_baseline`` (here on a shortened sample), the per-phase timings, the
@@ -807,7 +831,7 @@ def test_bench_contract_single_process(gpu):
     # (the host's config-size sections -- minutes of CPU time: a whole C2 fit over the oracle, a 50k dpotrf -- are switched off here)
     env = dict(os.environ, GUMBI_BENCH_DIST_N="2304", GUMBI_BENCH_C4_N="1536", GUMBI_BENCH_CPU_SECONDS="2", GUMBI_BENCH_NO_CPU_CONFIG_SIZE="1")
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "c2", "--steps", "1", "--warmup", "0",
-                          "--map-evals", "4"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                          "--map-evals", "4", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -866,7 +890,7 @@ def test_bench_config_c4_is_the_kronecker_fit(gpu):
         _POOL[0] = None
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, GUMBI_BENCH_C4_N="1536", GUMBI_BENCH_CPU_SECONDS="2")
-    out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "c4", "--steps", "1", "--warmup", "1", "--map-evals", "12"],
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "c4", "--steps", "1", "--warmup", "1", "--map-evals", "12", "--full"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -885,6 +909,47 @@ def test_bench_config_c4_is_the_kronecker_fit(gpu):
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and "stacked" in c["sample"] and c["value"] > 0
     assert "c5_single_gpu" not in d and "1e-3" in d["parity_pin"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain ``python bench.py`` (no --full) times its steps -- one MAP objective + gradient evaluation at the declared model's
+    starting hyper-parameters + the grid prediction each -- and prints the contract's line, nothing measured beside them;
+    ``--dump-outputs DIR`` writes what the last timed step computed as float64 .npy files, and since the inputs are seeded and
+    the hyper-parameters fixed, two runs of the same command write the same bits."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    if _POOL[0] is not None:
+        _POOL[0].close()
+        _POOL[0] = None
+    root = Path(__file__).resolve().parent.parent
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "c2", "--steps", "2", "--warmup", "1",
+                              "--dump-outputs", str(out_dir)], cwd=root, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and "fit+predict" in d["metric"]
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["results_finite"] and "one MAP objective + gradient evaluation" in d["metric"]
+        assert d["config"]["map_evals_per_step"] == [1, 1] and d["config"]["refactorizations_at_the_map_per_step"] == [0, 0]
+        for extra in ("roofline", "kbuild", "phases", "fit_quality", "cpu_baseline", "c4_single_gpu", "c5_single_gpu", "end_to_end",
+                      "default_start", "fit_to_convergence", "section_seconds"):
+            assert extra not in d, extra
+        flops = sum(n * 1e12 + r * 1e12 / 3 + 1e8 * 10_000 + 4e4 * 10_000
+                    for n, r in zip(d["config"]["map_evals_per_step"], d["config"]["refactorizations_at_the_map_per_step"]))
+        assert abs(d["value"] - flops / (d["ms_per_step"] * 2e-3) / 1e9) / d["value"] < 1e-3
+        got = {p.stem: np.load(p) for p in sorted(out_dir.glob("*.npy"))}
+        assert set(got) == {"mean", "var", "theta", "nlml", "grad"} and all(a.dtype == np.float64 for a in got.values())
+        assert got["grad"].shape == got["theta"].shape == (6,)
+        assert got["mean"].shape == got["var"].shape == (10_000,) and np.all(got["var"] > 0) and np.isfinite(got["nlml"]).all()
+        dumps.append(got)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_bench_default_config_is_the_largest_single_gpu_one():
