@@ -1684,9 +1684,9 @@ int launch_grad_nc(gmb_engine* e, const GradArgs& a_in, int nblocks) {
 //     from 64.  `h` receives the raw accumulators: plain sums over tiles, so shards of several GPUs add up.
 int grad_workspace(gmb_engine* e) {
   int rc;
-  if (e->cap_pts_alpha < e->Np) {
-    if ((rc = alloc(e, &e->dalpha, e->Np))) return rc;
-    e->cap_pts_alpha = e->Np;
+  if (e->cap_pts_alpha < 3 * e->Np) {  // alpha | the refinement's residual t | its correction (refine_alpha)
+    if ((rc = alloc(e, &e->dalpha, 3 * e->Np))) return rc;
+    e->cap_pts_alpha = 3 * e->Np;
   }
   return GMB_OK;  // (the accumulators live in the engine's scalar block)
 }
@@ -1890,6 +1890,27 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
   return GMB_OK;
 }
 
+// One refinement step of alpha = L^-T v (gradient.hpp: lt_residual_kernel): t = v - L^T alpha, then alpha += U t with U = L^-T
+// by rows in the factor buffer's upper triangle (the tile path: ut_tile_kernel, partial vectors in dApart) or, when W = L^-1
+// is given (the recursion: W in dW, lower), alpha += W^T t.
+int refine_alpha(gmb_engine* e, const TriOperand& L, const TriOperand* U, const double* W, int64_t ldw) {
+  const int nt = (int)(e->Np / TILE);
+  double* t = e->dalpha + e->Np;
+  hipLaunchKernelGGL(lt_residual_kernel, dim3((unsigned)((e->N + 3) / 4)), dim3(256), 0, e->stream, L, e->dv, e->dalpha, e->N, t);
+  if (U) {
+    hipLaunchKernelGGL(ut_tile_kernel, dim3(nt, nt), dim3(256), 0, e->stream, *U, t, e->N, e->dApart, e->Np);
+    hipLaunchKernelGGL(alpha_add_kernel, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, e->stream, e->dalpha, e->dApart,
+                       e->Np, nt, 1, e->N);
+  } else {
+    double* corr = e->dalpha + 2 * e->Np;
+    hipLaunchKernelGGL(wt_v_kernel, dim3((unsigned)((e->N + 3) / 4)), dim3(256), 0, e->stream, W, ldw, t, e->N, corr);
+    hipLaunchKernelGGL(alpha_add_kernel, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, e->stream, e->dalpha, corr,
+                       e->Np, 1, 0, e->N);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
 // matrices whose inverse / Sigma^-1 run as tile tasks (eval_tiles.hpp): the sizes the tile Cholesky factors
 bool grad_by_tiles(const gmb_engine* e) {
   const int nt = (int)(e->Np / TILE);
@@ -1923,6 +1944,11 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
       own_launch = true;
     }
     e->et_fused = false;
+    {  // alpha = U v of the launch, refined against L (intact, diagonal tiles in place) before the a a^T term reads it
+      const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
+      const TriOperand U{e->dA, e->ld, e->dUdiag, TILE, (int64_t)TILE * TILE};
+      if ((rc = refine_alpha(e, L, &U, nullptr, 0))) return rc;
+    }
     e->light = light;
     rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h);
     e->light = false;
@@ -1977,6 +2003,10 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   // 2. alpha = W^T v = Sigma^-1 y   (before Sigma^-1 overwrites W)
   hipLaunchKernelGGL(wt_v_kernel, dim3((unsigned)((e->N + 3) / 4)), dim3(256), 0, e->stream, e->dW, e->Np,
                      e->dv, e->N, e->dalpha);
+  {  // ... refined against L (its diagonal blocks wait in dDiagSave while U's sit in the factor buffer)
+    const TriOperand L{e->dA, e->ld, e->dDiagSave, TILE, (int64_t)TILE * TILE};
+    if ((rc = refine_alpha(e, L, nullptr, e->dW, e->Np))) return rc;
+  }
   if (e->Np > e->N)
     hipLaunchKernelGGL(reset_pad_cols_kernel, dim3((unsigned)((e->Np + 255) / 256)), dim3(256), 0, e->stream,
                        e->dA, e->ld, e->N, e->Np);
@@ -2749,7 +2779,7 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
   if ((rc = predict_workspace(e, Mt))) return rc;
   const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
   // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
-  const bool use_gemm_form = !e->solve_hook && e->predict_form != 0 && e->u_valid && e->factor_kind == gmb_engine::FK_SINGLE &&
+  const bool use_gemm_form = !e->solve_hook && e->predict_form != 0 && e->u_valid && e->have_alpha && e->factor_kind == gmb_engine::FK_SINGLE &&
                              e->dW && e->dUdiag && e->cap_W >= e->Np * e->Np;
   if (use_gemm_form && e->Mt2_cap < Mt) {
     e->Mt2_cap = 0;
@@ -2869,7 +2899,12 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
       }
     }
     if (gemm_form) {
-      hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->dV2, e->Np, e->dv, e->N, e->dkss, e->dmean, e->dvar);
+      // variance from Vt, mean = K(X*, X) alpha from the cross-covariance, which the GEMM left in dV (predict_form.hpp)
+      hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->dV2, e->Np, e->N, e->dkss, e->dvar);
+      hipLaunchKernelGGL(predict_mean_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
+                         dim3(256), 0, e->stream, e->dV, mpad, e->dalpha, e->N, e->dpart, mpad);
+      hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->dpart, nchunk,
+                         mpad, mc, e->dmean);
       HIP_TRY(e, hipGetLastError());
     } else {
       double* pmu = e->dpart;

@@ -9,8 +9,13 @@
 //
 //   Linv(c, i) = U(i, c)            linv_from_u_kernel: tile (c, r) of Linv = tile (r, c) of U, transposed
 //   Vt(c, m)   = sum_{i <= c} Linv(c, i) K(x*_m, x_i)      gemm_f64: n = c, m = test point, k = i, k_hi per n-tile (khi_n)
-//   mean_m = sum_c Vt(c, m) v_c,   var_m = k** - sum_c Vt(c, m)^2        predict_rows_kernel: one workgroup per test point,
-//                                                                         contiguous reads, fixed-order sums
+//   var_m = k** - sum_c Vt(c, m)^2        predict_rows_kernel: one workgroup per test point, contiguous reads, fixed-order sums
+//   mean_m = sum_i K(x*_m, x_i) alpha_i   predict_mean_partial_kernel + predict_mean_final_kernel over the cross-covariance itself
+//
+// The mean does NOT go through the inverse: (L^-1 K*)^T v from the explicit L^-1 is off by ~cond(L) eps |L^-1| |K*| |v|, 1e-8
+// relative on smooth low-noise tables (cond(Sigma) ~ 1e9), where the triangular solve stays at 1e-10; K* alpha with the
+// refined alpha of the gradient (gradient.hpp: refine_alpha) is as accurate as the solve.  The variance is a sum of squares
+// and is as accurate in both forms (tests/test_gpu_conditioning.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,34 +58,54 @@ __global__ __launch_bounds__(256) void linv_from_u_kernel(LinvArgs a) {
     }
 }
 
-// mean / variance of test point m = blockIdx.x from column m of Vt (n valid rows, contiguous): 256 threads take the rows
-// t, t + 256, ... in order, then a fixed tree -- the same bits run to run
-__global__ __launch_bounds__(256) void predict_rows_kernel(const double* __restrict__ Vt, int64_t ldv, const double* __restrict__ v, int64_t n,
-                                                           const double* __restrict__ kss, double* __restrict__ mean,
-                                                           double* __restrict__ var) {
-  __shared__ double red[2][4];
+// variance of test point m = blockIdx.x from column m of Vt (n valid rows, contiguous): 256 threads take the rows t, t + 256, ...
+// in order, then a fixed tree -- the same bits run to run
+__global__ __launch_bounds__(256) void predict_rows_kernel(const double* __restrict__ Vt, int64_t ldv, int64_t n,
+                                                           const double* __restrict__ kss, double* __restrict__ var) {
+  __shared__ double red[4];
   const int64_t m = blockIdx.x;
   const double* col = Vt + m * ldv;
-  double am = 0.0, as = 0.0;
+  double as = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) {
     const double x = col[i];
-    am = fma(x, v[i], am);
     as = fma(x, x, as);
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    am += __shfl_down(am, off);
-    as += __shfl_down(as, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = am;
-    red[1][threadIdx.x >> 6] = as;
-  }
+  for (int off = 32; off > 0; off >>= 1) as += __shfl_down(as, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = as;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    mean[m] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    var[m] = kss[m] - ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+  if (threadIdx.x == 0) var[m] = kss[m] - ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// part[c * mpad + m] = sum_{i in chunk c} K(x*_m, x_i) alpha_i: predict_partial_kernel's mean half alone (the cross-covariance is
+// read once, coalesced along the test points; grid (mpad / 256 rounded up, chunks))
+__global__ __launch_bounds__(256) void predict_mean_partial_kernel(const double* __restrict__ V, int64_t ldz,
+                                                                   const double* __restrict__ alpha, int64_t n,
+                                                                   double* __restrict__ part, int64_t mpad) {
+  __shared__ double as[RED_CHUNK];
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.y * RED_CHUNK;
+  const int64_t i1 = (i0 + RED_CHUNK < n) ? i0 + RED_CHUNK : n;
+  if (i0 + threadIdx.x < n) as[threadIdx.x] = alpha[i0 + threadIdx.x];
+  __syncthreads();
+  if (m >= mpad) return;
+  double am = 0.0;
+  const double* col = V + m + i0 * ldz;
+  for (int64_t i = i0; i < i1; ++i) {
+    am = fma(*col, as[i - i0], am);
+    col += ldz;
   }
+  part[(int64_t)blockIdx.y * mpad + m] = am;
+}
+
+// mean_m = sum of the chunk partials of K(x*_m, X) alpha, in chunk order
+__global__ __launch_bounds__(256) void predict_mean_final_kernel(const double* __restrict__ part_mu, int nchunk, int64_t mpad,
+                                                                 int64_t M, double* __restrict__ mean) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  double am = 0.0;
+  for (int c = 0; c < nchunk; ++c) am += part_mu[(int64_t)c * mpad + m];
+  mean[m] = am;
 }
 
 }  // namespace gmb

@@ -348,7 +348,10 @@ int gmb_set_eval_pairs(gmb_engine* e, int32_t mode);
  * evaluation on the tile path (N <= ~28k: gmb_evaluate, or gmb_nlml with a gradient) the engine still holds U = L^-T of the
  * resident factor; the prediction is then ONE product with a triangular operand (the GEMM that runs at 0.93 of the f64 matrix
  * peak) instead of a triangular solve (0.73 at N = 10k).  -1 = that whenever U is there (default), 0 = always solve, 1 = as -1.
- * Results agree with the solve to ~cond(L) eps (tests: <= 1e-10 relative on the golden cases).  Returns the previous mode + 1. */
+ * Only the variance uses the inverse factor; the mean is K(X*, X) alpha with the gradient's alpha (refined against L to the
+ * accuracy of a triangular solve).  Tested against an extended-precision reference up to cond(Sigma) ~ 3e9
+ * (tests/test_gpu_conditioning.py): the mean's error within 1.25 x that of the solve form on the same factor, the variance within
+ * the solve form's bar; and <= 1e-10 relative to the solve form on the golden cases.  Returns the previous mode + 1. */
 int gmb_set_predict_form(gmb_engine* e, int32_t form);
 /* (ABI 10) Allocate now what the following calls would allocate on first use: the factor buffer (8 Nr Np bytes: 80 GB at
  * N = 100k), with `gradient` != 0 the Sigma^-1 buffer of gmb_nlml / gmb_evaluate (8 Np^2 bytes), with M > 0 the workspaces of

@@ -506,7 +506,6 @@ def nlml_and_grad(spec, theta, X, y, dist_mode="direct", inverse="trsm"):
     the parity tests pin) or "potri" (LAPACK dpotri on the factor: a third of the flops; what bench.py's host baseline times).
     """
     theta = np.asarray(theta, float)
-    p = unpack_theta(spec, theta)
     X = np.asarray(X, float)
     y = np.asarray(y, float)
     N = X.shape[0]
@@ -528,7 +527,15 @@ def nlml_and_grad(spec, theta, X, y, dist_mode="direct", inverse="trsm"):
         Sinv = Linv.T @ Linv
         alpha = Linv.T @ v
     M = 0.5 * (Sinv - np.outer(alpha, alpha))  # dNLML/dSigma_ij
+    return val, grad_given_M(spec, theta, X, M, dist_mode)
 
+
+def grad_given_M(spec, theta, X, M, dist_mode="direct"):
+    """d NLML / d theta (natural scale) from ``M = dNLML/dSigma = 1/2 (Sigma^-1 - a a^T)``: the chain rule through every
+    kernel, noise and table parameter (the second half of ``nlml_and_grad``)."""
+    theta = np.asarray(theta, float)
+    p = unpack_theta(spec, theta)
+    X = np.asarray(X, float)
     g = np.zeros_like(theta)
     if spec.get("additive"):
         for sub, th, mp in additive_terms(spec, theta):
@@ -559,7 +566,7 @@ def nlml_and_grad(spec, theta, X, y, dist_mode="direct", inverse="trsm"):
         g[k + 2 * P : k + 3 * P] = Gd
     else:
         g[i_sigma] = np.sum(Md) * 2.0 * p["sigma"]
-    return val, g
+    return g
 
 
 # ----------------------------------------------------------------------------------------
