@@ -38,6 +38,7 @@
 #include "chol_tiles.hpp"
 #include "eval_tiles.hpp"
 #include "predict_form.hpp"
+#include "joint_predict.hpp"
 
 using namespace gmb;
 
@@ -131,6 +132,7 @@ struct gmb_engine {
   int predict_form = -1;   // -1 = GEMM form whenever U is there; 0 = always the triangular solve; 1 = as -1 (explicit)
   double* dV2 = nullptr;   // Np x Mt: the solved cross-covariance with the TRAINING index fastest
   int64_t Mt2_cap = 0;
+  JointState jt;           // the second matrix of gmb_predict_joint / gmb_draw_joint (joint_predict.hpp)
   double* dXs = nullptr;
   double* txs = nullptr;
   double* txl = nullptr;
@@ -2318,7 +2320,8 @@ void gmb_destroy(gmb_engine* e) {
   void* ptrs[] = {e->dct, e->dct_trace, e->dstat, e->dDiagSave, e->dsend, e->drecv, e->dplan_gemm, e->dplan_tr, e->dDinv16, e->dX, e->dy, e->dA, e->xs, e->xl, e->cat, e->dtabs,
                   e->dnoise, e->dscal, e->dv, e->dV, e->dXs, e->txs, e->txl,
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
-                  e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2};
+                  e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
+                  e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage};
   if (e->cap_A == 0) ptrs[11] = nullptr;  // (e->dA may be a virtual base of the capacity driver: nothing of ours to free)
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -2741,6 +2744,370 @@ int predict_workspace(gmb_engine* e, int64_t Mt) {
   return ensure(e, &e->dpart, &e->cap_part, (int64_t)2 * nchunk * e->Mt_cap);
 }
 
+// ---- the pieces of one M-tile of a prediction, shared by gmb_predict (tile by tile) and the joint posterior (all M rows at
+// once, engine.hip: joint_covariance) ----------------------------------------------------------------------------------------
+
+// Which form V = K(X*, X) L^-T takes (gmb_set_predict_form): the product with the resident inverse factor needs what the tile
+// path's gradient leaves behind; everything else is the triangular solve.
+bool predict_takes_gemm_form(const gmb_engine* e) {
+  return !e->solve_hook && e->predict_form != 0 && e->u_valid && e->have_alpha && e->factor_kind == gmb_engine::FK_SINGLE &&
+         e->dW && e->dUdiag && e->cap_W >= e->Np * e->Np;
+}
+
+// ... and the second Mt x Np buffer that form needs
+int predict_gemm_form_workspace(gmb_engine* e, int64_t Mt) {
+  int rc;
+  if (e->Mt2_cap < Mt) {
+    e->Mt2_cap = 0;
+    if ((rc = alloc(e, &e->dV2, Mt * e->Np))) return rc;
+    e->Mt2_cap = Mt;
+  }
+  return GMB_OK;
+}
+
+// mc test points (Xs: their first row) -> prepared points in txs / txl / tcat, the cross-covariance K(X*, X) in dV (mpad x Np,
+// test index fastest) and the prior variances (+ noise) in dkss
+int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, int32_t with_noise,
+                      hipMemcpyKind in_kind) {
+  int rc;
+  HIP_TRY(e, hipMemcpy2DAsync(e->dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double),
+                              e->D * sizeof(double), mc, in_kind, e->stream));
+  if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat))) return rc;
+  const PointSet test{e->txs, e->txl, e->tcat, mc, mpad};
+  {  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
+    CovTileArgs a{};
+    a.p = e->cp;
+    a.rows = test;
+    a.cols = train_set(e);
+    a.out = e->dV;
+    a.ldo = mpad;
+    a.ti = (int)(mpad / TILE);
+    a.tj = (int)(e->Np / TILE);
+    a.mode = COV_CROSS;
+    if ((rc = launch_cov(e, a))) return rc;
+  }
+  KssArgs k{};
+  k.p = e->cp;
+  k.pts = test;
+  k.with_noise = with_noise;
+  k.kss = e->dkss;
+  hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
+  for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: one accumulating pass per further term
+    const gmb_engine::Term& tr = e->terms[t];
+    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat, &tr.pa))) return rc;
+    CovTileArgs a{};
+    a.p = tr.cp;
+    a.rows = test;
+    a.cols = train_set(e);
+    a.out = e->dV;
+    a.ldo = mpad;
+    a.ti = (int)(mpad / TILE);
+    a.tj = (int)(e->Np / TILE);
+    a.mode = COV_CROSS;
+    a.accumulate = 1;
+    if ((rc = launch_cov(e, a))) return rc;
+    k.p = tr.cp;
+    k.with_noise = 0;
+    k.accumulate = 1;
+    hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
+  }
+  if (e->terms.size() > 1 &&
+      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa)))
+    return rc;
+  return GMB_OK;
+}
+
+// V <- V L^-T in dV (the solve), or V^T = L^-1 K(X, X*) into dV2 with the cross-covariance left in dV (`gemm_form`)
+int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
+  int rc;
+  // the triangular solve V <- V L^-T: one persistent launch for the matrices the tile Cholesky factors, else the recursion
+  const int nblocks = (int)(e->Np / TILE);
+  // (measured window, r03: faster than the recursion whenever the launch has enough tile tasks to fill the chip --
+  // row tiles x block columns >= 576: 1000 test points at N = 10k 4.05 -> 3.25 ms, 2500 at N = 5k 2.15 -> 1.86, 640 at
+  // N = 16k 6.55 -> 5.24, 384 at N = 28k 12.7 -> 8.9; 5 - 10 % for the standard 10^4-point grid -- and slower below
+  // that (a few row tiles walk the block columns as a chain either way, the recursion's launches are lighter), and for
+  // 4 x 10^4 points, where the recursion's large GEMMs run at 73 TF/s against the persistent loop's 69;
+  // scheme 3 forces it for any size; tools/gpu_chol_tiles.py CT_PREDICT=1)
+  const int ntm = (int)(mpad / TILE);
+  const bool by_size = nblocks >= e->tiles_trsm_min_blocks && nblocks <= e->tiles_max_blocks &&
+                       (ntm >= 32 || (long long)ntm * nblocks >= 576);
+  const bool tiles = !e->naive_leaf && ntm <= 96 && (e->chol_scheme == 3 || (e->chol_scheme < 0 && by_size));
+  e->cur = e->stream;
+  e->tt_used = false;
+  if (e->solve_hook) {
+    if ((rc = e->solve_hook(e->dV, mpad, (int)(mpad / TILE)))) return rc;
+  } else if (use_gemm_form) {
+    // U = L^-T of this factor is resident (the fit's last evaluation left it): V^T = L^-1 K(X, X*) as ONE product with a
+    // triangular operand (predict_form.hpp) instead of a solve
+    if (!e->linv_valid) {
+      LinvArgs la{};
+      la.U = e->dA;
+      la.ldu = e->ld;
+      la.udiag = e->dUdiag;
+      la.W = e->dW;
+      la.ldw = e->Np;
+      la.nct = nblocks;
+      hipLaunchKernelGGL(linv_from_u_kernel, dim3((unsigned)((long long)nblocks * (nblocks + 1) / 2)), dim3(256), 0, e->stream, la);
+      HIP_TRY(e, hipGetLastError());
+      e->linv_valid = true;
+    }
+    GemmArgs g{};
+    g.C = e->dV2;
+    g.ldc = e->Np;
+    g.A = e->dV;
+    g.lda = mpad;
+    g.B = e->dW;
+    g.ldb = e->Np;
+    g.mt = ntm;
+    g.nt = nblocks;
+    g.k = (int)e->Np;
+    g.alpha = 1.0;
+    g.beta = 0.0;
+    g.khi_n = 1;
+    if ((rc = launch_gemm(e, g, 3))) return rc;
+  } else if ((rc = tiles ? trsm_tiles(e, e->dV, mpad, (int)(mpad / TILE), 3)
+                         : trsm_cols(e, e->dV, mpad, (int)(mpad / TILE), 0, nblocks, 3, 6)))
+    return rc;
+  if (e->tt_used) {  // a launch that gave up waiting must not be mistaken for a prediction
+    uint32_t ab = 0;
+    HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (ab != 0) return fail(e, GMB_EHIP, "tile triangular solve: a workgroup waited longer than its time-out for a tile (launch abandoned)");
+  }
+  return GMB_OK;
+}
+
+// mean and variance of the tile's mc points into dmean / dvar
+int predict_reduce(gmb_engine* e, int64_t mc, int64_t mpad, bool gemm_form) {
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  if (gemm_form) {
+    // variance from Vt, mean = K(X*, X) alpha from the cross-covariance, which the GEMM left in dV (predict_form.hpp)
+    hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->dV2, e->Np, e->N, e->dkss, e->dvar);
+    hipLaunchKernelGGL(predict_mean_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
+                       dim3(256), 0, e->stream, e->dV, mpad, e->dalpha, e->N, e->dpart, mpad);
+    hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->dpart, nchunk,
+                       mpad, mc, e->dmean);
+    HIP_TRY(e, hipGetLastError());
+  } else {
+    double* pmu = e->dpart;
+    double* ps = e->dpart + (int64_t)nchunk * mpad;
+    hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
+                       dim3(256), 0, e->stream, e->dV, mpad, e->dv, e->N, pmu, ps, mpad);
+    hipLaunchKernelGGL(predict_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream,
+                       pmu, ps, nchunk, mpad, e->dkss, mc, e->dmean, e->dvar);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return GMB_OK;
+}
+
+// ---- the joint posterior (joint_predict.hpp): full covariance and correlated draws ----------------------------------------------
+
+// While C is factored its matrix, sub-block inverses, scalar block, info word and control block stand in for the training
+// factor's: the Cholesky's host routines (chol_tiles, chol_cols, chol_tiles_panel, chol_leaf) read them from the engine.
+// Everything is put back on every way out, so the training factorisation -- factor, log-determinant, flags -- survives.
+struct JointScope {
+  gmb_engine* e;
+  int64_t N, Np, Nr, ld, cap_A, cap_dinv16, cap_ct;
+  double *dA, *dDinv16, *dscal;
+  int32_t* dinfo;
+  uint32_t* dct;
+  bool ct_used, ct_panels, ct_traced, ct_trace, ct_injected, panel_tiles_on;
+  int ct_ntasks, ct_lose, chol_update_kind;
+  explicit JointScope(gmb_engine* e_)
+      : e(e_), N(e_->N), Np(e_->Np), Nr(e_->Nr), ld(e_->ld), cap_A(e_->cap_A), cap_dinv16(e_->cap_dinv16), cap_ct(e_->cap_ct),
+        dA(e_->dA), dDinv16(e_->dDinv16), dscal(e_->dscal), dinfo(e_->dinfo), dct(e_->dct), ct_used(e_->ct_used),
+        ct_panels(e_->ct_panels), ct_traced(e_->ct_traced), ct_trace(e_->ct_trace), ct_injected(e_->ct_injected),
+        panel_tiles_on(e_->panel_tiles_on), ct_ntasks(e_->ct_ntasks), ct_lose(e_->ct_lose), chol_update_kind(e_->chol_update_kind) {
+    const JointState& jt = e->jt;
+    e->N = jt.M, e->Np = jt.Mp, e->Nr = e->ld = jt.Mr;
+    e->dA = jt.dC, e->cap_A = jt.cap_C;
+    e->dDinv16 = jt.dDinv16, e->cap_dinv16 = jt.cap_dinv16;
+    e->dscal = jt.dscal, e->dinfo = reinterpret_cast<int32_t*>(jt.dscal + SCAL_INFO_AT);
+    e->dct = jt.dct, e->cap_ct = jt.cap_ct;
+    e->ct_used = e->ct_panels = e->ct_traced = e->ct_trace = e->ct_injected = e->panel_tiles_on = false;
+    e->ct_lose = 0;
+    e->chol_update_kind = 7;
+  }
+  ~JointScope() {
+    e->jt.dct = e->dct, e->jt.cap_ct = e->cap_ct;  // (the launches size the control block themselves)
+    e->N = N, e->Np = Np, e->Nr = Nr, e->ld = ld;
+    e->dA = dA, e->cap_A = cap_A;
+    e->dDinv16 = dDinv16, e->cap_dinv16 = cap_dinv16;
+    e->dscal = dscal, e->dinfo = dinfo;
+    e->dct = dct, e->cap_ct = cap_ct;
+    e->ct_used = ct_used, e->ct_panels = ct_panels, e->ct_traced = ct_traced, e->ct_trace = ct_trace, e->ct_injected = ct_injected;
+    e->panel_tiles_on = panel_tiles_on;
+    e->ct_ntasks = ct_ntasks, e->ct_lose = ct_lose, e->chol_update_kind = chol_update_kind;
+  }
+};
+
+// what both calls ask of the engine: a complete single-engine factor on this device
+int joint_ready(gmb_engine* e, const char* what) {
+  int rc = require_ready(e, true);
+  if (rc) return rc;
+  if (e->solve_hook || e->dist_mode != 0 || e->factor_kind != gmb_engine::FK_SINGLE)
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode): factorise with gmb_factorize on one device", what);
+  if ((rc = require_full_factor(e, what))) return rc;
+  if (e->factor_consumed) return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
+  return GMB_OK;
+}
+
+// Every buffer of a joint prediction at M points (+ `stage` doubles of device staging for host-side arguments), allocated
+// before anything is launched.  V is held whole -- the rank-N update needs every pair of its row tiles -- so a request is
+// first measured against the device: one that cannot fit is refused with the bytes it needs, and nothing has been touched.
+int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, double stage) {
+  JointState& jt = e->jt;
+  const double Mr = (double)round_up(M + 1, TILE), Mp = (double)round_up(M, TILE), Np = (double)e->Np;
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const double per_row = 8.0 * (Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;  // predict_workspace, per row of the M-tile
+  const double v_bytes = 8.0 * Mr * Np, c_bytes = 8.0 * Mr * Mp, stage_bytes = 8.0 * stage;
+  const double total = per_row * Mr + 16.0 * nchunk * Mr + (gemm_form ? v_bytes : 0.0) + c_bytes + stage_bytes;
+  // what is still to be allocated, less what those allocations release first
+  double fresh = 0.0;
+  if ((double)e->Mt_cap < Mr) fresh += per_row * (Mr - (double)e->Mt_cap);
+  if ((double)e->cap_part < 2.0 * nchunk * Mr) fresh += 8.0 * (2.0 * nchunk * Mr - (double)e->cap_part);
+  if (gemm_form && (double)e->Mt2_cap < Mr) fresh += 8.0 * Np * (Mr - (double)e->Mt2_cap);
+  if ((double)jt.cap_C < Mr * Mp) fresh += 8.0 * (Mr * Mp - (double)jt.cap_C);
+  if ((double)jt.cap_stage < stage) fresh += 8.0 * (stage - (double)jt.cap_stage);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+  if (fresh > (double)free_b || Mr > 1073741824.0)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld behind N = %lld needs %.0f bytes on the device (V: %.0f%s, C: %.0f), %.0f more than it holds "
+                               "for the engine now; %.0f bytes are free -- nothing was computed",
+                what, (long long)M, (long long)e->N, total, v_bytes, gemm_form ? " twice" : "", c_bytes, fresh, (double)free_b);
+  const int64_t mr = round_up(M + 1, TILE), mp = round_up(M, TILE);
+  int rc;
+  if ((rc = predict_workspace(e, mr))) return rc;
+  if (gemm_form && (rc = predict_gemm_form_workspace(e, mr))) return rc;
+  if ((rc = ensure(e, &jt.dC, &jt.cap_C, mr * mp))) return rc;
+  if ((rc = ensure(e, &jt.dDinv16, &jt.cap_dinv16, (mp / TILE) * (int64_t)8 * 256))) return rc;
+  if (!jt.dscal) {
+    int64_t cap = 0;
+    if ((rc = ensure(e, &jt.dscal, &cap, (int64_t)SCAL_GACC_AT))) return rc;
+  }
+  if (jt.cap_zero < mr) {
+    if ((rc = ensure(e, &jt.dzero, &jt.cap_zero, mr))) return rc;
+    HIP_TRY(e, hipMemsetAsync(jt.dzero, 0, (size_t)jt.cap_zero * sizeof(double), e->stream));
+  }
+  if (stage > 0.0 && (rc = ensure(e, &jt.dstage, &jt.cap_stage, (int64_t)stage))) return rc;
+  jt.M = M, jt.Mp = mp, jt.Mr = mr;
+  return GMB_OK;
+}
+
+// The posterior mean of all M points into dmean and the lower-triangle tiles of
+//   C = K(X*, X*) - V V^T (+ noise) + jitter I
+// into jt.dC (bordered layout of the training build: Mr x Mp, identity on the padding, a zero row where y would sit).
+int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter, bool gemm_form,
+                     hipMemcpyKind in_kind) {
+  JointState& jt = e->jt;
+  const int64_t Mr = jt.Mr, Mp = jt.Mp;
+  int rc;
+  // V for all M points at once, in the form gmb_predict would take, and the mean by gmb_predict's own reductions
+  if ((rc = predict_cross_cov(e, Xs, M, Mr, ldxs, with_noise, in_kind))) return rc;
+  if ((rc = predict_solve_v(e, Mr, gemm_form))) return rc;
+  if ((rc = predict_reduce(e, M, Mr, gemm_form))) return rc;
+  // the product form leaves V with the training index fastest: turned into the update's k-major layout (the cross-covariance
+  // in dV has served the mean)
+  if (gemm_form && (rc = launch_transpose(e, e->dV2, e->Np, e->dV, Mr, (int)e->Np, (int)Mr))) return rc;
+  // Columns N .. Np-1 of V belong to no training point.  gmb_predict never reads them (its reductions stop at N); the update
+  // below contracts over all Np, so they are cleared, whichever form produced them.
+  if (e->Np > e->N)
+    HIP_TRY(e, hipMemsetAsync(e->dV + e->N * Mr, 0, (size_t)((e->Np - e->N) * Mr) * sizeof(double), e->stream));
+
+  // K(X*, X*): the training build's launch (build_sigma) on the test points -- direct distances on the diagonal tiles, so the
+  // diagonal is gmb_predict's k** to the bit
+  const bool additive = e->terms.size() > 1;
+  if (additive && (rc = prep_points(e, e->dXs, M, e->D, Mr, e->txs, e->txl, e->tcat, &e->terms[0].pa))) return rc;
+  const PointSet test{e->txs, e->txl, e->tcat, M, Mr};
+  CovTileArgs a{};
+  a.p = e->cp;
+  a.p.sigma2 = with_noise ? e->cp.sigma2 : 0.0;
+  a.p.jitter = jitter;
+  a.rows = test;
+  a.cols = test;
+  a.out = jt.dC;
+  a.ldo = Mr;
+  a.ti = (int)(Mr / TILE);
+  a.tj = (int)(Mp / TILE);
+  a.mode = COV_TRAIN;
+  a.lower_only = 1;
+  a.tri_grid = 1;
+  a.y = jt.dzero;
+  if ((rc = launch_cov(e, a))) return rc;
+  for (size_t t = 1; t < e->terms.size(); ++t) {
+    if ((rc = prep_points(e, e->dXs, M, e->D, Mr, e->txs, e->txl, e->tcat, &e->terms[t].pa))) return rc;
+    a.p = e->terms[t].cp;
+    a.accumulate = 1;
+    if ((rc = launch_cov(e, a))) return rc;
+  }
+
+  // C -= V V^T: the trailing update's launch with contraction length Np (rows of the border stay as built: V is zero there)
+  GemmArgs g{};
+  g.C = jt.dC;
+  g.ldc = Mr;
+  g.A = e->dV;
+  g.lda = Mr;
+  g.B = e->dV;
+  g.ldb = Mr;
+  g.mt = (int)(Mp / TILE);
+  g.nt = (int)(Mr / TILE);
+  g.k = (int)e->Np;
+  g.alpha = -1.0;
+  g.beta = 1.0;
+  g.tri = 1;
+  e->cur = e->stream;
+  return launch_gemm(e, g, 3);
+}
+
+// C -> L* in place, by the schedule gmb_factorize would give a matrix of this size (the persistent tile kernel from six block
+// columns on, the recursion with tile-kernel panels otherwise).  Synchronises; an abandoned tile launch is an error.
+int joint_factor(gmb_engine* e) {
+  JointState& jt = e->jt;
+  HIP_TRY(e, hipMemsetAsync(jt.dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), e->stream));
+  int32_t info = 0;
+  uint32_t ab = 0;
+  {
+    JointScope scope(e);
+    int rc;
+    const int nblocks = (int)(e->Np / TILE);
+    const bool tiles = !e->naive_leaf && (e->chol_scheme == 3 || (e->chol_scheme < 0 && nblocks >= e->tiles_min_blocks &&
+                                                                   nblocks <= e->tiles_max_blocks));
+    e->cur = e->stream;
+    if (tiles) {
+      rc = chol_tiles(e);
+    } else {
+      e->panel_tiles_on = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
+      if (e->panel_tiles_on) {
+        if ((rc = ensure(e, &e->dct, &e->cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * (e->Nr / TILE)))) return rc;
+        HIP_TRY(e, hipMemsetAsync(e->dct, 0, 4 * sizeof(uint32_t), e->stream));
+      }
+      rc = chol_cols(e, 0, nblocks, (int)(e->Nr / TILE));
+    }
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(&info, e->dinfo, sizeof info, hipMemcpyDeviceToHost, e->stream));
+    if (e->ct_used) HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof ab, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+  }
+  if (ab != 0)
+    return fail(e, GMB_EHIP, "joint posterior: the tile Cholesky of the predictive covariance waited longer than its time-out for a tile (launch abandoned)");
+  if (info != 0) {
+    e->notpd = (int64_t)info - 1;
+    return fail(e, GMB_ENOTPD, "the posterior covariance of the test points is not positive definite at row %lld (raise the jitter)",
+                (long long)e->notpd);
+  }
+  return GMB_OK;
+}
+
+int launch_draw(gmb_engine* e, const DrawArgs& a) {
+  const unsigned nrb = (unsigned)((a.M + 15) / 16);
+  if (a.S <= 16) hipLaunchKernelGGL(joint_draw_kernel<1>, dim3(nrb, 1), dim3(256), 0, e->stream, a);
+  else if (a.S <= 32) hipLaunchKernelGGL(joint_draw_kernel<2>, dim3(nrb, 1), dim3(256), 0, e->stream, a);
+  else hipLaunchKernelGGL(joint_draw_kernel<4>, dim3(nrb, (unsigned)((a.S + 63) / 64)), dim3(256), 0, e->stream, a);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2777,16 +3144,9 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
 
   const int64_t Mt = predict_tile_rows(e, M);
   if ((rc = predict_workspace(e, Mt))) return rc;
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
   // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
-  const bool use_gemm_form = !e->solve_hook && e->predict_form != 0 && e->u_valid && e->have_alpha && e->factor_kind == gmb_engine::FK_SINGLE &&
-                             e->dW && e->dUdiag && e->cap_W >= e->Np * e->Np;
-  if (use_gemm_form && e->Mt2_cap < Mt) {
-    e->Mt2_cap = 0;
-    if ((rc = alloc(e, &e->dV2, Mt * e->Np))) return rc;
-    e->Mt2_cap = Mt;
-  }
-  bool gemm_form = false;
+  const bool use_gemm_form = predict_takes_gemm_form(e);
+  if (use_gemm_form && (rc = predict_gemm_form_workspace(e, Mt))) return rc;
   tm.predict_gemm_form = use_gemm_form ? 1 : 0;
 
   const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2795,129 +3155,98 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
   for (int64_t m0 = 0; m0 < M; m0 += Mt) {
     const int64_t mc = std::min<int64_t>(Mt, M - m0);
     const int64_t mpad = round_up(mc, TILE);
-    HIP_TRY(e, hipMemcpy2DAsync(e->dXs, e->D * sizeof(double), Xs + m0 * ldxs, ldxs * sizeof(double),
-                                e->D * sizeof(double), mc, in_kind, e->stream));
-    if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat))) return rc;
-    const PointSet test{e->txs, e->txl, e->tcat, mc, mpad};
-    {  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
-      CovTileArgs a{};
-      a.p = e->cp;
-      a.rows = test;
-      a.cols = train_set(e);
-      a.out = e->dV;
-      a.ldo = mpad;
-      a.ti = (int)(mpad / TILE);
-      a.tj = (int)(e->Np / TILE);
-      a.mode = COV_CROSS;
-      if ((rc = launch_cov(e, a))) return rc;
-    }
-    KssArgs k{};
-    k.p = e->cp;
-    k.pts = test;
-    k.with_noise = with_noise;
-    k.kss = e->dkss;
-    hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
-    for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: one accumulating pass per further term
-      const gmb_engine::Term& tr = e->terms[t];
-      if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
-      if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat, &tr.pa))) return rc;
-      CovTileArgs a{};
-      a.p = tr.cp;
-      a.rows = test;
-      a.cols = train_set(e);
-      a.out = e->dV;
-      a.ldo = mpad;
-      a.ti = (int)(mpad / TILE);
-      a.tj = (int)(e->Np / TILE);
-      a.mode = COV_CROSS;
-      a.accumulate = 1;
-      if ((rc = launch_cov(e, a))) return rc;
-      k.p = tr.cp;
-      k.with_noise = 0;
-      k.accumulate = 1;
-      hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
-    }
-    if (e->terms.size() > 1 &&
-        (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa)))
-      return rc;
-    {
-      // the triangular solve V <- V L^-T: one persistent launch for the matrices the tile Cholesky factors, else the recursion
-      const int nblocks = (int)(e->Np / TILE);
-      // (measured window, r03: faster than the recursion whenever the launch has enough tile tasks to fill the chip --
-      // row tiles x block columns >= 576: 1000 test points at N = 10k 4.05 -> 3.25 ms, 2500 at N = 5k 2.15 -> 1.86, 640 at
-      // N = 16k 6.55 -> 5.24, 384 at N = 28k 12.7 -> 8.9; 5 - 10 % for the standard 10^4-point grid -- and slower below
-      // that (a few row tiles walk the block columns as a chain either way, the recursion's launches are lighter), and for
-      // 4 x 10^4 points, where the recursion's large GEMMs run at 73 TF/s against the persistent loop's 69;
-      // scheme 3 forces it for any size; tools/gpu_chol_tiles.py CT_PREDICT=1)
-      const int ntm = (int)(mpad / TILE);
-      const bool by_size = nblocks >= e->tiles_trsm_min_blocks && nblocks <= e->tiles_max_blocks &&
-                           (ntm >= 32 || (long long)ntm * nblocks >= 576);
-      const bool tiles = !e->naive_leaf && ntm <= 96 && (e->chol_scheme == 3 || (e->chol_scheme < 0 && by_size));
-      e->cur = e->stream;
-      e->tt_used = false;
-      gemm_form = false;
-      if (e->solve_hook) {
-        if ((rc = e->solve_hook(e->dV, mpad, (int)(mpad / TILE)))) return rc;
-      } else if (use_gemm_form) {
-        // U = L^-T of this factor is resident (the fit's last evaluation left it): V^T = L^-1 K(X, X*) as ONE product with a
-        // triangular operand (predict_form.hpp) instead of a solve
-        if (!e->linv_valid) {
-          LinvArgs la{};
-          la.U = e->dA;
-          la.ldu = e->ld;
-          la.udiag = e->dUdiag;
-          la.W = e->dW;
-          la.ldw = e->Np;
-          la.nct = nblocks;
-          hipLaunchKernelGGL(linv_from_u_kernel, dim3((unsigned)((long long)nblocks * (nblocks + 1) / 2)), dim3(256), 0, e->stream, la);
-          HIP_TRY(e, hipGetLastError());
-          e->linv_valid = true;
-        }
-        GemmArgs g{};
-        g.C = e->dV2;
-        g.ldc = e->Np;
-        g.A = e->dV;
-        g.lda = mpad;
-        g.B = e->dW;
-        g.ldb = e->Np;
-        g.mt = ntm;
-        g.nt = nblocks;
-        g.k = (int)e->Np;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.khi_n = 1;
-        if ((rc = launch_gemm(e, g, 3))) return rc;
-        gemm_form = true;
-      } else if ((rc = tiles ? trsm_tiles(e, e->dV, mpad, (int)(mpad / TILE), 3)
-                             : trsm_cols(e, e->dV, mpad, (int)(mpad / TILE), 0, nblocks, 3, 6)))
-        return rc;
-      if (e->tt_used) {  // a launch that gave up waiting must not be mistaken for a prediction
-        uint32_t ab = 0;
-        HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-        if (ab != 0) return fail(e, GMB_EHIP, "tile triangular solve: a workgroup waited longer than its time-out for a tile (launch abandoned)");
-      }
-    }
-    if (gemm_form) {
-      // variance from Vt, mean = K(X*, X) alpha from the cross-covariance, which the GEMM left in dV (predict_form.hpp)
-      hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->dV2, e->Np, e->N, e->dkss, e->dvar);
-      hipLaunchKernelGGL(predict_mean_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
-                         dim3(256), 0, e->stream, e->dV, mpad, e->dalpha, e->N, e->dpart, mpad);
-      hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->dpart, nchunk,
-                         mpad, mc, e->dmean);
-      HIP_TRY(e, hipGetLastError());
-    } else {
-      double* pmu = e->dpart;
-      double* ps = e->dpart + (int64_t)nchunk * mpad;
-      hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
-                         dim3(256), 0, e->stream, e->dV, mpad, e->dv, e->N, pmu, ps, mpad);
-      hipLaunchKernelGGL(predict_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream,
-                         pmu, ps, nchunk, mpad, e->dkss, mc, e->dmean, e->dvar);
-      HIP_TRY(e, hipGetLastError());
-    }
+    if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, in_kind))) return rc;
+    if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
+    if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
     HIP_TRY(e, hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), out_kind, e->stream));
     HIP_TRY(e, hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), out_kind, e->stream));
   }
+  tp.stop();
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  tm.predict_ms = tp.ms();
+  ev_collect(e);
+  return GMB_OK;
+}
+
+int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                      double* mean, double* cov, int64_t ldc, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_predict_joint");
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !mean || !cov)) || ldxs < e->D || ldc < M || !(jitter >= 0.0))
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/cov/ldc/jitter");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = joint_workspace(e, "gmb_predict_joint", M, gemm_form, host ? (double)M * (double)M : 0.0))) return rc;
+  gmb_timings& tm = e->tm;
+  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
+  tm.predict_gemm_launches = 0;
+  tm.predict_gemm_form = gemm_form ? 1 : 0;
+  PhaseTimer tp(e);
+  if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice)))
+    return rc;
+  SymArgs sa{};
+  sa.C = e->jt.dC;
+  sa.ldc = e->jt.Mr;
+  sa.out = host ? e->jt.dstage : cov;
+  sa.ldo = host ? M : ldc;
+  sa.M = M;
+  const unsigned nb = (unsigned)((M + 31) / 32);
+  hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
+  if (host)
+    HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
+                                hipMemcpyDeviceToHost, e->stream));
+  tp.stop();
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  tm.predict_ms = tp.ms();
+  ev_collect(e);
+  return GMB_OK;
+}
+
+int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                   const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_draw_joint");
+  if (rc) return rc;
+  if (M < 0 || S < 0 || S > 0x7fffffff || (M > 0 && S > 0 && (!Xs || !Z || !Y)) || ldxs < e->D || ldz < M || ldy < M || !(jitter >= 0.0))
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/Z/S/ldz/Y/ldy/jitter");
+  if (M == 0 || S == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = joint_workspace(e, "gmb_draw_joint", M, gemm_form, host ? 2.0 * (double)S * (double)M : 0.0))) return rc;
+  gmb_timings& tm = e->tm;
+  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
+  tm.predict_gemm_launches = 0;
+  tm.predict_gemm_form = gemm_form ? 1 : 0;
+  PhaseTimer tp(e);
+  if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice)))
+    return rc;
+  if ((rc = joint_factor(e))) {
+    ev_collect(e);
+    return rc;
+  }
+  DrawArgs da{};
+  da.L = e->jt.dC;
+  da.ldl = e->jt.Mr;
+  da.mean = e->dmean;
+  da.M = M;
+  da.S = (int32_t)S;
+  if (host) {
+    double* dZ = e->jt.dstage;
+    double* dY = e->jt.dstage + S * M;
+    HIP_TRY(e, hipMemcpy2DAsync(dZ, M * sizeof(double), Z, ldz * sizeof(double), M * sizeof(double), S, hipMemcpyHostToDevice, e->stream));
+    da.Z = dZ, da.ldz = M, da.Y = dY, da.ldy = M;
+  } else {
+    da.Z = Z, da.ldz = ldz, da.Y = Y, da.ldy = ldy;
+  }
+  if ((rc = launch_draw(e, da))) return rc;
+  if (host)
+    HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
+  if (mean)
+    HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
   tp.stop();
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   tm.predict_ms = tp.ms();

@@ -236,6 +236,10 @@ _SIGNATURES = {
     "gmb_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                               C.c_void_p, C.c_int32]),
+    "gmb_predict_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_draw_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "gmb_ls_limits": (C.c_int, [C.c_int32, _DBL_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_peak": (C.c_int, [C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_sustained": (C.c_int, [C.c_int32, C.c_double, _DBL_P, _DBL_P, _DBL_P, C.POINTER(C.c_int64)]),
@@ -316,8 +320,9 @@ def _preload_hip_runtime():
 #: launch: ``gmb_set_grad_scheme``, ``gmb_debug_eval_tasks``, ``total_eval_tile_*`` in ``gmb_timings``; version 9 the timing
 #: tools' door ``gmb_debug_assume_factored``, the guards between single-engine and capacity-mode factorisations, ``gmb_set_eval_pairs``;
 #: version 10 ``gmb_set_predict_form`` (GEMM-form prediction behind a fit), ``total_chol_update_all_*`` / ``predict_gemm_form`` in
-#: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1)
-ABI_VERSION = 10
+#: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
+#: ``gmb_predict_joint`` / ``gmb_draw_joint``)
+ABI_VERSION = 11
 
 
 def load_library():
@@ -491,6 +496,47 @@ class Engine:
             "gmb_predict",
         )
         return mean, var
+
+    def _joint_points(self, Xs):
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        return Xs
+
+    def predict_joint(self, Xs, with_noise=True, jitter=0.0):
+        """Posterior mean (M) and the full M x M posterior covariance ``K** - V V^T (+ noise) + jitter I`` at the rows of
+        ``Xs`` (``gmb_predict_joint``; ``pm.gp.Marginal._build_conditional(..., diag=False)``).  ``MemoryError`` -- raised
+        before anything is computed -- when the device cannot hold the request."""
+        Xs = self._joint_points(Xs)
+        M = Xs.shape[0]
+        mean = np.empty(M, dtype=np.float64)
+        cov = np.empty((M, M), dtype=np.float64)
+        self._check(
+            self._lib.gmb_predict_joint(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), float(jitter), _ptr(mean),
+                                        _ptr(cov), M, GMB_HOST),
+            "gmb_predict_joint",
+        )
+        return mean, cov
+
+    def draw_joint(self, Xs, Z, with_noise=False, jitter=1e-6, return_mean=False):
+        """``Y[s] = mean + L* Z[s]`` for the S rows of ``Z`` (S x M standard normals of the caller's), ``L*`` the lower Cholesky
+        factor of ``predict_joint``'s covariance (``gmb_draw_joint``): S correlated draws of the posterior at the rows of
+        ``Xs``, a deterministic function of (model, theta, Xs, Z).  ``LinAlgError`` when that covariance is not positive
+        definite (``notpd_index``: its row).  ``return_mean=True`` returns ``(Y, mean)``."""
+        Xs = self._joint_points(Xs)
+        M = Xs.shape[0]
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != M:
+            raise ValueError(f"Z must be (S, {M}), got {Z.shape}")
+        S = Z.shape[0]
+        Y = np.empty((S, M), dtype=np.float64)
+        mean = np.empty(M, dtype=np.float64)
+        self._check(
+            self._lib.gmb_draw_joint(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), float(jitter), _ptr(Z), S, max(M, 1),
+                                     _ptr(Y), max(M, 1), _ptr(mean), GMB_HOST),
+            "gmb_draw_joint",
+        )
+        return (Y, mean) if return_mean else Y
 
     def predict_device(self, xs_ptr: int, M: int, ldxs: int, mean_ptr: int, var_ptr: int, with_noise=True):
         self._check(

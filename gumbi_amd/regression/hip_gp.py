@@ -165,6 +165,7 @@ class HipGP(Regressor):
         self._last_eval_theta = None
         self.n_refactor = 0
         self._theta_fitted = None
+        self._draw_rng = None  # generator of the posterior draws' normals (draw_point_samples), seeded on first use
 
     # ------------------------------------------------------------------------------------------
     def fit(self, outputs=None, linear_dims=None, continuous_dims=None, continuous_levels=None,
@@ -495,3 +496,85 @@ class HipGP(Regressor):
         if self.MAP is None or self.engine is None:
             raise ValueError("The model must be fit (find_MAP) before predicting")
         return self.engine.predict(np.asarray(points_array, dtype=np.float64), with_noise=with_noise)
+
+    # -- joint posterior: covariance and draws ---------------------------------------------------------------------------------
+    def _joint_engine(self, additive_level, what):
+        if additive_level != "total":
+            raise NotImplementedError("Prediction for additive sublevels is not yet supported.")
+        if self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before predicting")
+        if self.distributed:
+            raise NotImplementedError(f"{what}: the joint posterior is not built for distributed GPs (the factor is spread over ranks)")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError(f"{what}: the joint posterior is not built for the Kronecker path (pass kronecker=False)")
+        return self.engine
+
+    def predict_joint(self, points_array, with_noise=True, additive_level="total"):
+        """Posterior mean (M) and full M x M covariance at standardized points, in standardized units
+        (``pm.gp.Marginal._build_conditional(..., diag=False)``): one call into ``gmb_predict_joint`` against the factor
+        left resident by :meth:`find_MAP`.  No jitter is added; the diagonal is :meth:`predict`'s variance."""
+        engine = self._joint_engine(additive_level, "predict_joint")
+        return engine.predict_joint(np.asarray(points_array, dtype=np.float64), with_noise=with_noise, jitter=0.0)
+
+    def draw_point_samples(self, points, *args, source=None, output=None, var_name="posterior_samples", additive_level="total",
+                           increment_var=True, n_draws=1, with_noise=False, rng=None, z=None, **kwargs):
+        """Draw ``n_draws`` correlated samples of the fitted posterior at ``points`` (reference :861-922): a parray of shape
+        ``(n_draws, M)`` in standardized units, also left in :attr:`predictions` (with ``points`` in :attr:`predictions_X`).
+
+        The normals behind the draws are ``z`` (``(n_draws, M)``) if given, else drawn from ``rng``, else from a
+        ``np.random.default_rng(self.seed)`` generator kept on the GP: successive calls differ, a fresh GP with the same seed
+        repeats them.  A draw is ``mean + L* z`` with ``L*`` the Cholesky factor of the joint posterior covariance
+        (``gmb_draw_joint``), so it is reproducible from ``z`` alone.
+
+        Jitter convention implemented: the reference calls ``conditional(var_name, points_array)`` with PyMC's defaults,
+        i.e. noise-free draws whose covariance PyMC 5 stabilises with its default jitter -- the model's ``jitter`` (1e-6) is
+        added for ``with_noise=False``; with ``with_noise=True`` (``pred_noise=True``) PyMC adds none and neither do we.
+
+        ``source`` / ``var_name`` / ``increment_var`` exist for signature compatibility: draws come from the stored MAP, and
+        any other ``source`` raises."""
+        output = self._parse_prediction_output(output)
+        if len(output) > 1:
+            raise NotImplementedError("Drawing correlated samples of multiple outputs is not yet implemented.")
+        if args or kwargs:
+            raise TypeError(f"draw_point_samples: unsupported arguments {args} {sorted(kwargs)} (PyMC sampling options have no meaning here)")
+        points_array, tall_points, param_coords = self._prepare_points_for_prediction(points, output=output)
+        if self.MAP is None or self.engine is None:
+            raise ValueError('"Source" of predictions must be supplied if GP object has no trace or MAP stored.')
+        if not (source is None or source is self.MAP or
+                (isinstance(source, (list, tuple)) and len(source) == 1 and source[0] is self.MAP)):
+            raise NotImplementedError("draw_point_samples draws from the stored MAP only; `source` must be None or that MAP")
+        engine = self._joint_engine(additive_level, "draw_point_samples")
+
+        M = points_array.shape[0]
+        if z is None:
+            if rng is None:
+                if self._draw_rng is None:
+                    self._draw_rng = np.random.default_rng(self.seed)
+                rng = self._draw_rng
+            z = rng.standard_normal((int(n_draws), M))
+        else:
+            z = np.asarray(z, dtype=np.float64)
+            if z.shape != (int(n_draws), M):
+                raise ValueError(f"z must have shape (n_draws, M) = ({int(n_draws)}, {M}), got {z.shape}")
+        jitter = 0.0 if with_noise else float(self.model.spec.jitter)
+        samples = engine.draw_joint(points_array, z, with_noise=with_noise, jitter=jitter)
+
+        self.predictions = self.parray(**{output[0]: samples}, stdzd=True)
+        self.predictions_X = points
+        return self.predictions
+
+    def draw_grid_samples(self, *args, source=None, output=None, categorical_levels=None, var_name="posterior_samples",
+                          additive_level="total", increment_var=True, n_draws=1, with_noise=False, rng=None, z=None, **kwargs):
+        """Draw posterior samples at the points :meth:`prepare_grid` defined (reference :924-979): a parray of shape
+        ``(n_draws, *grid shape)``; see :meth:`draw_point_samples` for the arguments."""
+        if self.grid_points is None:
+            raise ValueError("Grid must first be specified with `prepare_grid`")
+        points = self.grid_points
+        if self.categorical_dims:
+            points = self.append_categorical_points(points, categorical_levels=categorical_levels)
+        samples = self.draw_point_samples(points, *args, source=source, output=output, var_name=var_name,
+                                          additive_level=additive_level, increment_var=increment_var, n_draws=n_draws,
+                                          with_noise=with_noise, rng=rng, z=z, **kwargs)
+        self.predictions = samples.reshape(-1, *self.grid_parray.shape)
+        self.predictions_X = self.predictions_X.reshape(self.grid_parray.shape)
+        return self.predictions

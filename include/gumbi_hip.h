@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 10
+#define GMB_ABI_VERSION 11
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -252,6 +252,30 @@ int gmb_nlml(gmb_engine* e, double* nlml, double* grad);
  * caller-allocated length-M arrays in the same memspace as Xs.  Reuses the resident factor. */
 int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
                 double* mean, double* var, int32_t memspace);
+
+/* (ABI 11) The JOINT posterior at M points (csrc/joint_predict.hpp).  Both calls need the resident factor exactly as gmb_predict
+ * does and leave it -- and gmb_nlml, the gradient's leftovers, gmb_factor_valid -- as they found it; V = K(X*, X) L^-T takes the
+ * form gmb_predict would take (gmb_set_predict_form) and is held for ALL M points at once (8 * (M padded) * (N padded) bytes, twice
+ * in the product form), beside the M x M matrix C.  A request the device cannot hold returns GMB_ENOMEM before anything is
+ * launched, with the bytes it needs in gmb_last_error; nothing is written.  Engines with a multi-GPU factorisation (gmb_dist_*,
+ * capacity mode) return GMB_EINVAL.  `jitter` (>= 0) is the caller's: PyMC adds its default 1e-6 to a noise-free conditional
+ * covariance and nothing when pred_noise=True -- the Python caller passes that convention in, as it does priors and Jacobians.
+ *
+ * Posterior mean (M) and the full M x M posterior covariance at M points, row-major with leading dimension ldc, both
+ * triangles written (exactly symmetric):
+ *   C = K(X*,X*) - V V^T  (+ the noise diagonal of the model at X* if with_noise)  + jitter * I
+ * pm.gp.Marginal._build_conditional(..., diag=False); diag(C) less noise and jitter is gmb_predict's variance to rounding. */
+int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                      double* mean, double* cov, int64_t ldc, int32_t memspace);
+
+/* S joint draws  Y[s, :] = mean + L* Z[s, :],  L* the lower Cholesky factor of the C above (the engine's own factorisation
+ * kernels on a second matrix).  Z is S x M standard normals supplied by the caller (row-major, leading dimension ldz), Y is
+ * S x M (ldy), mean (M, out) may be NULL.  The draw is a deterministic function of (model, theta, Xs, Z): the same bits call
+ * after call.  GMB_ENOTPD + gmb_notpd_index (a row of C) when C is not positive definite; GMB_EHIP when the tile Cholesky
+ * abandoned its launch (time-out).  Replaces pm.gp.Marginal.conditional + pm.sample_posterior_predictive at the MAP
+ * (gumbi/regression/pymc/GP.py:914-917: draw_point_samples / draw_grid_samples). */
+int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                   const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace);
 
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
