@@ -242,6 +242,13 @@ struct PrepArgs {
   // tile launch's control words and flags) -- two memsets less per evaluation; 8-byte words, null = nothing
   unsigned long long* zero[2];
   int64_t zero_words[2];
+  // Periodic models (gmb_set_periodic): continuous dimension d becomes the TWO prepared columns 2d, 2d + 1 =
+  // w_d sin(2 pi x_d / T_d), w_d cos(2 pi x_d / T_d), so that |u(x) - u(x')|^2 = 4 w_d^2 sin^2(pi (x_d - x'_d) / T_d) and every
+  // kernel downstream sees an ordinary stationary model on nc = 2 n_cont columns.  idx_cont / inv_ls are then filled PER
+  // PREPARED COLUMN (both columns of a dimension carry its X column and its weight w_d: 1 / ls_d for <kind>+Periodic,
+  // 1 / (2 ls_d) for pm.gp.cov.Periodic, whose exponent is -sin^2(..) / (2 ls^2)).  0 = off.
+  int32_t periodic;
+  double two_over_T[8];  // 2 / T_d: the angle goes through sincospi, whose argument reduction is exact
 };
 
 __device__ __forceinline__ void prep_one_point(const PrepArgs& a, const int64_t i);
@@ -261,11 +268,26 @@ __device__ __forceinline__ void prep_one_point(const PrepArgs& a, const int64_t 
   const bool real = i < a.n;
   const double* row = a.X + i * a.ldx;
   double nrm = 0.0;
-  for (int k = 0; k < a.nc_pad; ++k) {
-    double v = 0.0;
-    if (real && k < a.nc) v = row[a.idx_cont[k]] * a.inv_ls[k];
-    a.xs[(int64_t)k * a.npad + i] = v;
-    nrm = fma(v, v, nrm);
+  if (a.periodic) {  // (uniform; nc_pad is even: it is picked from 2 n_cont)
+    for (int k = 0; k < a.nc_pad; k += 2) {
+      double sn = 0.0, cs = 0.0;
+      if (real && k < a.nc) {
+        sincospi(row[a.idx_cont[k]] * a.two_over_T[k >> 1], &sn, &cs);
+        sn *= a.inv_ls[k];
+        cs *= a.inv_ls[k];
+      }
+      a.xs[(int64_t)k * a.npad + i] = sn;
+      a.xs[(int64_t)(k + 1) * a.npad + i] = cs;
+      nrm = fma(sn, sn, nrm);
+      nrm = fma(cs, cs, nrm);
+    }
+  } else {
+    for (int k = 0; k < a.nc_pad; ++k) {
+      double v = 0.0;
+      if (real && k < a.nc) v = row[a.idx_cont[k]] * a.inv_ls[k];
+      a.xs[(int64_t)k * a.npad + i] = v;
+      nrm = fma(v, v, nrm);
+    }
   }
   a.xs[(int64_t)a.nc_pad * a.npad + i] = nrm;  // row nc_pad: |x / ls|^2 (the interior tiles' augmented coordinate)
   for (int k = 0; k < a.n_lin; ++k)

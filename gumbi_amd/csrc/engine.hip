@@ -86,6 +86,8 @@ struct gmb_engine {
   bool have_spec = false, have_theta = false;
   std::vector<double> theta;
   int nc_pad = 1;
+  int periodic = 0;        // gmb_set_periodic: 0 off, 1 <kind>+Periodic, 2 pm.gp.cov.Periodic; the prepared columns are then 2 n_cont
+  double periods[8] = {};  // T_d per continuous dimension (standardized units)
   double* xs = nullptr;
   double* xl = nullptr;
   int32_t* cat = nullptr;
@@ -762,13 +764,30 @@ int apply_theta(gmb_engine* e) {
   const int n_ls = s.ard ? s.n_cont : 1;
   PrepArgs& pa = e->prep_proto;
   pa = PrepArgs{};
-  pa.nc = s.n_cont;
+  const int per = e->periodic;
+  pa.nc = per ? 2 * s.n_cont : s.n_cont;
   pa.nc_pad = e->nc_pad;
+  pa.periodic = per;
+  // Periodic models: dimension i feeds the prepared columns 2i, 2i + 1, both with the weight w_i = 1 / ls_i (<kind>+Periodic:
+  // r^2 = sum 4 sin^2(pi D / T) / ls^2) or 1 / (2 ls_i) (Periodic = ExpQuad on sum sin^2(pi D / T) / ls^2).  The halving is exact,
+  // so grad_reduce gets the gradient's true 1 / ls_i back as 2 w_i.
+  auto set_ls = [&](PrepArgs& p, int i, double ls) {
+    if (!per) {
+      p.inv_ls[i] = 1.0 / ls;
+      return;
+    }
+    p.inv_ls[2 * i] = p.inv_ls[2 * i + 1] = per == 2 ? 0.5 * (1.0 / ls) : 1.0 / ls;
+  };
   for (int i = 0; i < s.n_cont; ++i) {
     const double ls = th[s.ard ? i : 0];
     if (!(ls > 0.0)) return fail(e, GMB_EINVAL, "lengthscale %d = %g must be positive", i, ls);
-    pa.idx_cont[i] = s.idx_cont[i];
-    pa.inv_ls[i] = 1.0 / ls;
+    if (!per) {
+      pa.idx_cont[i] = s.idx_cont[i];
+    } else {
+      pa.idx_cont[2 * i] = pa.idx_cont[2 * i + 1] = s.idx_cont[i];
+      pa.two_over_T[i] = 2.0 / e->periods[i];
+    }
+    set_ls(pa, i, ls);
   }
   k += n_ls;
   const double eta = th[k], sigma = th[k + 1];
@@ -870,7 +889,7 @@ int apply_theta(gmb_engine* e) {
     for (int i = 0; i < s.n_cont; ++i) {
       const double ls = th[ka + (s.ard ? i : 0)];
       if (!(ls > 0.0)) return fail(e, GMB_EINVAL, "lengthscale %d of additive term %d = %g must be positive", i, j, ls);
-      t.pa.inv_ls[i] = 1.0 / ls;
+      set_ls(t.pa, i, ls);  // (periodic: the term's own lengthscales on the shared periods)
     }
     ka += n_ls;
     t.eta = th[ka++];
@@ -1747,8 +1766,12 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
     a.alpha = e->dalpha;
     a.tiles = nt;
     a.ard = s.ard;
-    a.nc_real = s.n_cont;
-    for (int k = 0; k < 16; ++k) a.inv_ls[k] = k < s.n_cont ? tr.pa.inv_ls[k] : 0.0;
+    // d r^2 / d ls = -2 r^2 / ls per prepared column whatever constant the preparation's weight carries: the gradient's factor
+    // is the TRUE 1 / ls_d -- the weight itself, or twice it for pm.gp.cov.Periodic (apply_theta)
+    const int ncols = e->periodic ? 2 * s.n_cont : s.n_cont;  // prepared columns
+    const double true_inv = e->periodic == 2 ? 2.0 : 1.0;
+    a.nc_real = ncols;
+    for (int k = 0; k < 16; ++k) a.inv_ls[k] = k < ncols ? true_inv * tr.pa.inv_ls[k] : 0.0;
     a.eta = tr.eta;
     a.row_first = shard;
     a.row_stride = nshards;
@@ -1808,8 +1831,9 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
         ++r.n;
       };
       double* tmp = e->dgpart + GACC_DOUBLES;  // scratch behind the accumulators
-      merged = e->light && e->terms.size() == 1 && s.ard && big == 0 && nvec <= 8192 && e->N <= 16384;
-      if (s.ard) add(0, s.n_cont, 0);
+      merged = e->light && e->terms.size() == 1 && s.ard && !e->periodic && big == 0 && nvec <= 8192 && e->N <= 16384;
+      if (e->periodic) add(0, ncols, (int)(tmp - acc));      // per-column sums, folded into the dimensions' parameters below
+      else if (s.ard) add(0, s.n_cont, 0);
       else add(0, s.n_cont, (int)(tmp - acc));               // per-dimension sums, folded into the one parameter below
       add(ncp, 2 + tr.cp.n_lin, n_ls);                        // eta | tau | c..
       for (int j = 0; j < tr.cp.n_tab; ++j)
@@ -1826,7 +1850,8 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
         hipLaunchKernelGGL(grad_sum_partials_kernel, dim3(a.part_stride), dim3(256), 0, e->stream, e->dgred, nvec,
                            (int64_t)a.part_stride, r, acc);
       }
-      if (!s.ard) hipLaunchKernelGGL(grad_fold_ls_kernel, dim3(1), dim3(64), 0, e->stream, acc, s.n_cont, tmp);
+      if (e->periodic) hipLaunchKernelGGL(grad_fold_periodic_kernel, dim3(1), dim3(64), 0, e->stream, acc, s.n_cont, (int)s.ard, tmp);
+      else if (!s.ard) hipLaunchKernelGGL(grad_fold_ls_kernel, dim3(1), dim3(64), 0, e->stream, acc, s.n_cont, tmp);
       if (big > 0) {
         GradRanges rb{};
         for (int j = 0; j < tr.cp.n_tab; ++j)
@@ -2427,7 +2452,35 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->factored = false;
   e->factor_kind = gmb_engine::FK_NONE;
   e->nc_pad = pick_nc(spec->n_cont);
+  e->periodic = 0;
   e->cap_pts = 0;
+  return GMB_OK;
+}
+
+int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t n) {
+  if (!e) return GMB_EINVAL;
+  if (!e->have_spec) return fail(e, GMB_EINVAL, "gmb_set_kernel must precede gmb_set_periodic");
+  const gmb_kernel_spec& s = e->spec;
+  if (mode < 0 || mode > 2) return fail(e, GMB_EINVAL, "gmb_set_periodic: mode %d must be 0 (off), 1 (<kind>+Periodic) or 2 (Periodic)", mode);
+  if (n != s.n_cont) return fail(e, GMB_EINVAL, "gmb_set_periodic: %d periods for %d continuous dimensions", n, s.n_cont);
+  if (mode != 0) {
+    if (s.n_cont > GMB_MAX_DIMS / 2)
+      return fail(e, GMB_EINVAL, "gmb_set_periodic: a periodic model has at most %d continuous dimensions (two prepared columns each), got %d",
+                  GMB_MAX_DIMS / 2, s.n_cont);
+    if (mode == 2 && s.kind != GMB_EXPQUAD) return fail(e, GMB_EINVAL, "gmb_set_periodic: mode 2 (Periodic) needs kind ExpQuad, got %d", s.kind);
+    if (!periods) return fail(e, GMB_EINVAL, "gmb_set_periodic: periods is null");
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(periods[i]) || !(periods[i] > 0.0))
+        return fail(e, GMB_EINVAL, "gmb_set_periodic: period %d = %g must be finite and positive", i, periods[i]);
+  }
+  e->periodic = mode;
+  for (int i = 0; i < 8; ++i) e->periods[i] = (mode != 0 && i < n) ? periods[i] : 0.0;
+  e->nc_pad = pick_nc(mode != 0 ? 2 * s.n_cont : s.n_cont);
+  // the prepared coordinates and everything factored from them belong to the previous feature map
+  e->have_theta = false;
+  e->factored = false;
+  e->factor_kind = gmb_engine::FK_NONE;
+  e->u_valid = e->linv_valid = false;
   return GMB_OK;
 }
 
@@ -3687,6 +3740,7 @@ int64_t gmb_resident_bytes(const gmb_engine* e, int32_t peak) {
 
 int gmb_dist_factorize(gmb_engine* e, const gmb_comm* comm, int32_t panel_blocks) {
   if (!e) return GMB_EINVAL;
+  if (e->periodic) return fail(e, GMB_EINVAL, "gmb_dist_factorize: periodic kernels are not supported by the multi-GPU driver");
   return e->dist_mode == 1 ? cap_factorize(e, comm, panel_blocks) : dist_factorize(e, comm, panel_blocks);
 }
 

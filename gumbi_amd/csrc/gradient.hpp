@@ -686,6 +686,19 @@ __global__ void grad_fold_ls_kernel(double* acc, int n, const double* tmp) {
   acc[0] = s;
 }
 
+// periodic models: the two prepared columns 2d, 2d + 1 of continuous dimension d belong to ITS lengthscale (tmp holds the 2 n
+// column sums) -- acc[d] = tmp[2d] + tmp[2d + 1], or all of them into acc[0] for a shared lengthscale; fixed order
+__global__ void grad_fold_periodic_kernel(double* acc, int n, int ard, const double* tmp) {
+  if (threadIdx.x || blockIdx.x) return;
+  double s = 0.0;
+  for (int d = 0; d < n; ++d) {
+    const double p = tmp[2 * d] + tmp[2 * d + 1];
+    if (ard) acc[d] = p;
+    else s += p;
+  }
+  if (!ard) acc[0] = s;
+}
+
 // Diagonal-only terms: d/d sigma and the noise-table partials.
 //   out[0] = sum_i M_ii * 2 sigma * nmult_i ;  out[1 + a] = sum_{i: out(i) = a} M_ii * sigma^2
 // One workgroup, fixed order: thread t takes rows t, t + 1024, ...; the noise-table partials go through per-wave

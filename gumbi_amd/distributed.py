@@ -309,6 +309,8 @@ class DistributedEngine:
         self.eng.set_data(X, y)
 
     def set_kernel(self, spec):
+        if getattr(spec, "periodic", 0):
+            raise NotImplementedError("periodic kernels on a distributed GP: the multi-GPU driver refuses them (gmb_set_periodic)")
         self.eng.set_kernel(spec)
         self.spec = spec
 

@@ -15,7 +15,8 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["Engine", "KernelSpec", "GumbiHipError", "library_path", "load_library", "KERNEL_KINDS",
+__all__ = ["Engine", "KernelSpec", "GumbiHipError", "library_path", "load_library", "KERNEL_KINDS", "resolve_kernel_name",
+           "PERIODIC_OFF", "PERIODIC_WARPED", "PERIODIC_PLAIN", "MAX_PERIODIC_DIMS",
            "ls_limits", "dist_plan", "GmbComm", "DistStep"]
 
 GMB_MAX_DIMS, GMB_MAX_LIN, GMB_MAX_COREG, GMB_MAX_LEVELS = 16, 8, 4, 32
@@ -24,6 +25,25 @@ GMB_HOST, GMB_DEVICE = 0, 1
 
 # pm.gp.cov names accepted by PymcGP._construct_kernels (gumbi/regression/pymc/GP.py:664-674)
 KERNEL_KINDS = {"ExpQuad": 0, "Matern52": 1, "Matern32": 2, "Matern12": 3, "Exponential": 4}
+
+
+#: ``gmb_set_periodic`` modes
+PERIODIC_OFF, PERIODIC_WARPED, PERIODIC_PLAIN = 0, 1, 2
+#: largest number of continuous dimensions of a periodic model (two prepared columns each)
+MAX_PERIODIC_DIMS = GMB_MAX_DIMS // 2
+
+
+def resolve_kernel_name(name: str):
+    """``continuous_kernel`` of the front end -> ``(stationary kind, periodic mode)``: ``"Matern52"`` -> ``("Matern52", 0)``,
+    ``"Matern52+Periodic"`` -> ``("Matern52", 1)``, ``"Periodic"`` -> ``("ExpQuad", 2)`` (pm.gp.cov.Periodic is the
+    exponentiated quadratic of the half-scaled warped inputs)."""
+    if name == "Periodic":
+        return "ExpQuad", PERIODIC_PLAIN
+    if isinstance(name, str) and name.endswith("+Periodic") and name[: -len("+Periodic")] in KERNEL_KINDS:
+        return name[: -len("+Periodic")], PERIODIC_WARPED
+    if name in KERNEL_KINDS:
+        return name, PERIODIC_OFF
+    raise ValueError(f"Continuous kernel must be one of {list(KERNEL_KINDS)}, optionally with '+Periodic', or 'Periodic'; got {name!r}")
 
 
 class GumbiHipError(RuntimeError):
@@ -131,6 +151,11 @@ class KernelSpec:
     hetero_noise: bool = True
     jitter: float = 1e-6
     additive: bool = False  # a global kernel + one kernel per coregion dim (specify_model(additive=True))
+    #: periodic mode (``gmb_set_periodic``; not part of ``gmb_kernel_spec``): 0 off, 1 ``<kind>+Periodic``, 2 ``Periodic``
+    periodic: int = 0
+    #: one period per entry of idx_cont, in the units of X.  ``to_c`` checks their number only; that each is finite and
+    #: positive is the engine's check (``gmb_set_periodic`` -> ``ValueError`` from ``Engine.set_kernel``)
+    periods: list = field(default_factory=list)
 
     @property
     def kind_id(self) -> int:
@@ -145,7 +170,7 @@ class KernelSpec:
                     idx_cont=[int(i) for i in self.idx_cont], idx_lin=[int(i) for i in self.idx_lin],
                     coreg=[(int(c), int(n)) for c, n in self.coreg], out_col=int(self.out_col),
                     n_out=int(self.n_out), hetero_noise=bool(self.hetero_noise), jitter=float(self.jitter),
-                    additive=bool(self.additive))
+                    additive=bool(self.additive), periodic=int(self.periodic), periods=[float(t) for t in self.periods])
 
     def theta_size(self) -> int:
         n = (len(self.idx_cont) if self.ard else 1) + 2
@@ -166,6 +191,13 @@ class KernelSpec:
             raise ValueError(f"at most {GMB_MAX_LIN} linear dimensions are supported")
         if len(self.coreg) > GMB_MAX_COREG:
             raise ValueError(f"at most {GMB_MAX_COREG} categorical dimensions are supported")
+        if self.periodic:  # (travels beside the struct: gmb_set_periodic)
+            if self.periodic not in (PERIODIC_WARPED, PERIODIC_PLAIN):
+                raise ValueError(f"periodic must be 0, 1 or 2, got {self.periodic!r}")
+            if len(self.idx_cont) > MAX_PERIODIC_DIMS:
+                raise ValueError(f"a periodic kernel supports at most {MAX_PERIODIC_DIMS} continuous dimensions")
+            if len(self.periods) != len(self.idx_cont):
+                raise ValueError(f"{len(self.periods)} periods for {len(self.idx_cont)} continuous dimensions")
         s = _Spec()
         s.kind, s.ard = self.kind_id, int(bool(self.ard))
         s.n_cont = len(self.idx_cont)
@@ -228,6 +260,7 @@ _SIGNATURES = {
     "gmb_set_y": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "gmb_set_kernel": (C.c_int, [C.c_void_p, C.POINTER(_Spec)]),
     "gmb_theta_size": (C.c_int, [C.POINTER(_Spec)]),
+    "gmb_set_periodic": (C.c_int, [C.c_void_p, C.c_int32, _DBL_P, C.c_int32]),
     "gmb_set_theta": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32]),
     "gmb_factorize": (C.c_int, [C.c_void_p]),
     "gmb_notpd_index": (C.c_int64, [C.c_void_p]),
@@ -321,8 +354,8 @@ def _preload_hip_runtime():
 #: tools' door ``gmb_debug_assume_factored``, the guards between single-engine and capacity-mode factorisations, ``gmb_set_eval_pairs``;
 #: version 10 ``gmb_set_predict_form`` (GEMM-form prediction behind a fit), ``total_chol_update_all_*`` / ``predict_gemm_form`` in
 #: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
-#: ``gmb_predict_joint`` / ``gmb_draw_joint``)
-ABI_VERSION = 11
+#: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``)
+ABI_VERSION = 12
 
 
 def load_library():
@@ -447,7 +480,17 @@ class Engine:
     def set_kernel(self, spec: KernelSpec):
         cs = spec.to_c()
         self._check(self._lib.gmb_set_kernel(self._h, C.byref(cs)), "gmb_set_kernel")
+        if int(getattr(spec, "periodic", 0)) != 0:
+            self.set_periodic(spec.periodic, spec.periods)
         self.spec = spec
+
+    def set_periodic(self, mode: int, periods):
+        """Periodic continuous kernel (``gmb_set_periodic``): ``mode`` 0 off, 1 ``<kind>+Periodic``, 2 ``Periodic`` (kind ExpQuad);
+        ``periods``: one per continuous dimension of the kernel, in the units of ``X``.  Call between ``set_kernel`` (which
+        resets the mode) and ``set_theta``; ``ValueError`` for what the engine refuses."""
+        periods = np.ascontiguousarray(periods, dtype=np.float64).ravel()
+        self._check(self._lib.gmb_set_periodic(self._h, int(mode), _dptr(periods) if periods.size else None, periods.size),
+                    "gmb_set_periodic")
 
     def set_theta(self, theta):
         theta = np.ascontiguousarray(theta, dtype=np.float64)

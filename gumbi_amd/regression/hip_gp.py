@@ -33,7 +33,7 @@ from math import lgamma
 import numpy as np
 
 from ..aggregation import DataSet
-from ..engine import KERNEL_KINDS, Engine, KernelSpec
+from ..engine import KERNEL_KINDS, MAX_PERIODIC_DIMS, Engine, KernelSpec, resolve_kernel_name
 from . import icm
 from ..utils.gp_utils import get_ls_prior
 from ..utils.misc import assert_in
@@ -212,17 +212,46 @@ class HipGP(Regressor):
     # -- model declaration ---------------------------------------------------------------------------------
     def build_model(self, seed=None, continuous_kernel="ExpQuad", period=None, heteroskedastic_inputs=False,
                     heteroskedastic_outputs=True, sparse=False, n_u=100, ARD=True, ls_bounds=None, mass=0.98):
-        """Declare the marginal GP (reference :468-583) and move the data into HBM."""
+        """Declare the marginal GP (reference :468-583) and move the data into HBM.
+
+        ``continuous_kernel``: one of the five stationary kinds, ``"Periodic"`` (``pm.gp.cov.Periodic``:
+        ``eta^2 exp(-1/2 sum_d sin^2(pi (x_d - x'_d) / T_d) / ls_d^2)``) or ``"<kind>+Periodic"`` (the stationary kind on the inputs
+        warped by ``u(x) = (sin(2 pi x / T), cos(2 pi x / T))``: ``r^2 = sum_d 4 sin^2(pi (x_d - x'_d) / T_d) / ls_d^2``).  All
+        six periodic forms need ``period``: a parray with one layer per continuous dimension, read as the reference reads it
+        (``period.z[dim + "_z"]``, reference :403, :431).  Build it with :func:`gumbi_amd.array_utils.make_deltas_parray`
+        (``make_deltas_parray(stdzr=..., scale="natural", X=[T])``), as ``ls_bounds`` is built, so that ``.z`` is the period as a
+        standardized STEP ``T / sigma`` rather than a standardized position.  Periods are data, not parameters: they are never
+        optimised.  At most 8 continuous dimensions.
+
+        ``"<kind>+Periodic"`` with several continuous dimensions is NOT what the reference evaluates: its inner kernel is
+        declared with ``input_dim=2, active_dims=None`` (:427-429), so it reads only the first two warped columns -- the sines
+        of the first two dimensions -- and is well-formed for one continuous dimension only.  Here every dimension contributes
+        its own (sin, cos) pair with its own lengthscale, the form the construction intends; the two agree for one dimension.
+        The lengthscale prior comes from the unwarped inputs, as in the reference."""
         if heteroskedastic_inputs:
             raise NotImplementedError("Heteroskedasticity over inputs is not yet implemented.")
         if sparse:
             raise NotImplementedError("The sparse (FITC) approximation is not part of the HIP backend.")
         periodic = [k + "+Periodic" for k in KERNEL_KINDS] + ["Periodic"]
         assert_in("Continuous kernel", continuous_kernel, list(KERNEL_KINDS) + periodic)
-        if continuous_kernel in periodic:
-            if period is None and continuous_kernel != "Periodic":
+        kind, periodic_mode = resolve_kernel_name(continuous_kernel)
+        periods = []
+        if periodic_mode:
+            if period is None:
                 raise ValueError("Period must be specified for periodic kernel")
-            raise NotImplementedError("Periodic kernels are not part of the HIP backend.")
+            if self.distributed:
+                raise NotImplementedError("Periodic kernels with distributed=True: the multi-GPU driver does not carry the periods")
+            if len(self.continuous_dims) > MAX_PERIODIC_DIMS:
+                raise ValueError(f"a periodic kernel supports at most {MAX_PERIODIC_DIMS} continuous dimensions, "
+                                 f"got {len(self.continuous_dims)}")
+            missing = [dim for dim in self.continuous_dims if dim not in period.names]
+            if missing:
+                raise ValueError(f"period has no entry for the continuous dimension(s) {missing}")
+            for dim in self.continuous_dims:
+                zp = np.asarray(period.z[dim + "_z"].values(), dtype=float).ravel()
+                if zp.size != 1 or not np.isfinite(zp[0]) or zp[0] <= 0:
+                    raise ValueError(f"period of {dim!r} must be one finite positive number on the standardized scale, got {zp}")
+                periods.append(float(zp[0]))
 
         X, y = self.get_shaped_data("mean")
         D_in = len(self.dims)
@@ -239,17 +268,21 @@ class HipGP(Regressor):
         self.model_specs = {"seed": seed, "continuous_kernel": continuous_kernel,
                             "heteroskedastic_inputs": heteroskedastic_inputs,
                             "heteroskedastic_outputs": heteroskedastic_outputs, "sparse": sparse, "n_u": n_u}
+        if periodic_mode:
+            # a periodic model cannot be rebuilt from its kernel's name alone: cross_validate rebuilds the training model
+            # with build_model(**model_specs)
+            self.model_specs["period"] = period
         self._ARD = ARD
 
         idx = self._get_dim_indexes()
         multi = self.out_col in self.categorical_dims
         coreg = [(i, len(self.categorical_levels[d])) for d, i in zip(self.categorical_dims, idx["c"])
                  if d != self.out_col]
-        spec = KernelSpec(D=D_in, idx_cont=idx["s"], kind=continuous_kernel, ard=ARD, idx_lin=idx["l"],
+        spec = KernelSpec(D=D_in, idx_cont=idx["s"], kind=kind, ard=ARD, idx_lin=idx["l"],
                           coreg=coreg, out_col=idx["p"] if multi else -1,
                           n_out=len(self.categorical_levels[self.out_col]) if multi else 0,
                           hetero_noise=bool(heteroskedastic_outputs), jitter=1e-6,
-                          additive=bool(self.additive and coreg))
+                          additive=bool(self.additive and coreg), periodic=periodic_mode, periods=periods)
         ls_params = self._prepare_lengthscales(X, ARD=ARD, ls_bounds=ls_bounds, mass=mass)
 
         # parameter blocks in the packing order of include/gumbi_hip.h

@@ -90,7 +90,8 @@ class IcmEngine:
         self.Y = self.y.reshape(self.P, self.N)
         self.spec_k = KernelSpec(D=spec.D - 1, idx_cont=list(spec.idx_cont), kind=spec.kind, ard=spec.ard,
                                  idx_lin=list(spec.idx_lin), coreg=list(spec.coreg), out_col=-1, n_out=0,
-                                 hetero_noise=False, jitter=0.0)
+                                 hetero_noise=False, jitter=0.0, periodic=int(getattr(spec, "periodic", 0)),
+                                 periods=list(getattr(spec, "periods", [])))  # (the P systems share the warped inputs)
         self.nk = self.spec_k.theta_size()
         n_ls = len(spec.idx_cont) if spec.ard else 1
         self.i_eta, self.i_sigma = n_ls, n_ls + 1

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 11
+#define GMB_ABI_VERSION 12
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -214,6 +214,19 @@ int gmb_set_y(gmb_engine* e, const double* y, int32_t memspace);
  * 652-729): fixes which columns feed which covariance term. */
 int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec);
 int gmb_theta_size(const gmb_kernel_spec* spec);
+/* (ABI 12) Periodic continuous kernels (pymc/GP.py:416-447, 676-682).  `periods` holds one period T_d per continuous dimension
+ * of the spec (n == n_cont), in the units of X; they are data, not parameters: theta and gmb_theta_size do not change.
+ *   mode 0  off (what gmb_set_kernel leaves; `periods` is not read);
+ *   mode 1  <kind>+Periodic: the spec's stationary kind applied to the inputs warped by u(x) = (sin(2 pi x / T), cos(2 pi x / T))
+ *           per dimension, r^2 = sum_d |u(x_d) - u(x'_d)|^2 / ls_d^2 = sum_d 4 sin^2(pi (x_d - x'_d) / T_d) / ls_d^2
+ *           (pm.gp.cov.WarpedInput; the kind keeps its own sqrt(r^2 + 1e-12));
+ *   mode 2  pm.gp.cov.Periodic: k = eta^2 exp(-1/2 sum_d sin^2(pi (x_d - x'_d) / T_d) / ls_d^2); the spec's kind must be ExpQuad.
+ * Every dimension takes two of the GMB_MAX_DIMS prepared columns, so n_cont <= 8.  GMB_EINVAL for another mode, n != n_cont,
+ * n_cont > 8, a period that is not finite and > 0, mode 2 on another kind.  Call it between gmb_set_kernel (which resets the
+ * mode to off) and gmb_set_theta: it invalidates theta's prepared coordinates, the resident factor and the inverse factor.
+ * Additive models warp every term's own lengthscales with the same periods.  The multi-GPU driver (gmb_dist_*) refuses
+ * periodic engines. */
+int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t n);
 
 /* Hyper-parameters on the natural scale -- the role of `point=self.MAP` (pymc/GP.py:846). */
 int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n);
