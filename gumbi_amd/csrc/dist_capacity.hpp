@@ -14,7 +14,7 @@
 //
 // How the kernels of the replicated layout are reused unchanged: a panel buffer is a WINDOW OF COLUMNS of a virtual full
 // buffer with the same leading dimension -- element (row i, global column j) of panel [c0, c1) sits at
-// P + i + (j - 128 c0) ld = (P - 128 c0 ld) + i + j ld -- so with e->dA pointed at that virtual base every routine that
+// P + i + (j - 128 c0) ld = (P - 128 c0 ld) + i + j ld -- so given that virtual base as its matrix (cap_window) every routine that
 // touches only the panel's columns of "the factor buffer" (chol_cols on the diagonal square, trsm_cols against it, the
 // trailing updates' A and B operands, the unpack side of the all-gathers) runs as it is.  What changes is where a rank's OWN
 // rows live (dAown, contiguous: the updates write C through GemmArgs::cblk_stride = 1, the covariance build through
@@ -36,13 +36,12 @@ inline int cap_chunk(int nct) { return std::max(1, std::min(nct, std::min(DIST_I
 // packed block index of owned block row b
 inline int cap_packed(int b, int rank, int G) { return (b - rank) / G; }
 
-// RAII: e->dA points at the virtual base of a panel buffer while the kernels of the replicated layout run on it
-struct CapVirtual {
-  gmb_engine* e;
-  double* saved;
-  CapVirtual(gmb_engine* e_, double* panel, int c0) : e(e_), saved(e_->dA) { e->dA = panel - (int64_t)c0 * TILE * e->ld; }
-  ~CapVirtual() { e->dA = saved; }
-};
+// the training factor seen through a panel buffer that holds its block columns from c0 on: the matrix is the virtual base
+FactorRef cap_window(gmb_engine* e, double* panel, int c0) {
+  FactorRef f = train_factor(e);
+  f.A = panel - (int64_t)c0 * TILE * e->ld;
+  return f;
+}
 
 // this rank's packed rows + panel space of `panel_cols` block columns with all rows (the factorisation: two panels of the plan's
 // width; the gradient: three chunk-wide buffers; the prediction: two)
@@ -138,7 +137,6 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   e->sync_next = 0;
   e->time_next = 0;
   e->cur = mainS;
-  e->chol_update_kind = 0;
   DistDeferred bad;
   DistProbe probe;
   bool tail_in_flight = false;  // a TAIL has been issued on the communication stream since the last FORK
@@ -205,9 +203,8 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
       case DIST_SQUARE: {  // the diagonal square's block rows from their owners, then every rank factors it
         gathered = true;
         if ((rc = cap_gather_panel(e, comm, mainS, panel, s.c0, s.c1, s.lo, s.hi, true, &probe, e->dsend2, e->drecv2))) break;
-        CapVirtual v(e, panel, s.c0);
         e->cur = mainS;
-        rc = chol_cols(e, s.c0, s.c1, s.c1);
+        rc = chol_cols(e, cap_window(e, panel, s.c0), s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);
         // the owners' copies of the square's rows become L too (they are read again when L is streamed)
         int f, c;
         dist_owned(rank, G, s.lo, s.hi, &f, &c);
@@ -221,9 +218,10 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
       case DIST_SOLVE: {  // my rows below the square: solved in place in dAown, and copied into the panel buffer (U1 reads them there
                           // before the TAIL has delivered everybody's)
         if (s.count <= 0) break;
-        CapVirtual v(e, panel, s.c0);
         e->cur = mainS;
-        if ((rc = trsm_cols(e, e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE, e->ld_own, s.count, s.c0, s.c1, 2, 5))) break;
+        if ((rc = trsm_cols(e, cap_window(e, panel, s.c0), e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE, e->ld_own, s.count, s.c0, s.c1,
+                            EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP)))
+          break;
         rc = dist_pack(e, mainS, panel, e->ld, e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE + (int64_t)s.c0 * TILE * e->ld_own, e->ld_own, 0,
                        (int)W, false, 0, s.first, s.count, G, 0, 0, s.maxcount);
         break;
@@ -259,7 +257,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         g.tri_off = (s.first - s.lo) * TILE;
         g.nblk_stride = G;
         e->cur = s.stream ? bulkS : mainS;
-        rc = launch_gemm(e, g, 7);
+        rc = launch_gemm(e, g, EV_CHOL_UPDATE);
         e->cur = mainS;
         break;
       }
@@ -442,12 +440,12 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       bad.note(e, order_after(e, mainS, commS));
       bad.note(e, cap_gather_panel(e, comm, commS, Lbuf[(ci + 1) & 1], k1, std::min(k1 + cw, nt), k1, nrt, !bad.rc, &probe));
     }
-    CapVirtual v(e, panel, k0);
+    const FactorRef v = cap_window(e, panel, k0);
     int f2, mine;
     dist_owned(rank, G, 0, k1, &f2, &mine);
     const int mc = dist_max_owned(G, 0, k1);
     // 2. this rank's rows of U in these columns
-    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, V, ldv, mine, k0, k1, 4, 6, first, G));
+    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, v, V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
     if (!bad.rc && k1 == nt && e->Np > e->N && owned > 0) {  // (the last chunk holds the padding columns)
       hipLaunchKernelGGL(cap_reset_pad_cols_kernel, dim3((unsigned)(((int64_t)owned * TILE + 255) / 256)), dim3(256), 0, mainS, V, ldv, e->N, e->Np,
                          first, G, owned);
@@ -465,7 +463,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       GemmArgs g{};
       g.C = V + (int64_t)k1 * TILE * ldv;
       g.ldc = ldv;
-      g.A = e->dA + (int64_t)k1 * TILE + (int64_t)k0 * TILE * e->ld;
+      g.A = v.A + (int64_t)k1 * TILE + (int64_t)k0 * TILE * e->ld;
       g.lda = e->ld;
       g.B = V + (int64_t)k0 * TILE * ldv;
       g.ldb = ldv;
@@ -477,7 +475,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.klo_n = 1;
       g.krow_stride = G;
       g.krow_off = (first - k0) * TILE;
-      bad.note(e, launch_gemm(e, g, 4));
+      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
     }
     // alpha = U v, this chunk's columns (the chunk's columns of V are overwritten below)
     if (!bad.rc && owned > 0) {
@@ -512,7 +510,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.nblk_stride = G;
       g.alpha = 1.0;
       g.beta = 1.0;
-      bad.note(e, launch_gemm(e, g, 4));
+      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
     }
   }
   // alpha = U v: this rank's rows (the chunks' parts in chunk order), then everybody's
@@ -586,13 +584,13 @@ int cap_solve(gmb_engine* e, const gmb_comm* comm, double* V, int64_t ldv, int n
       bad.note(e, cap_gather_panel(e, comm, commS, Lbuf[(ci + 1) & 1], c1, std::min(c1 + cw, nct), c1, nrt, !bad.rc, nullptr));
     }
     if (bad.rc || ntm <= 0) continue;
-    CapVirtual v(e, Lbuf[ci & 1], c0);
-    bad.note(e, trsm_cols(e, V, ldv, ntm, c0, c1, 3, 6));
+    const FactorRef v = cap_window(e, Lbuf[ci & 1], c0);
+    bad.note(e, trsm_cols(e, v, V, ldv, ntm, c0, c1, EV_PREDICT_GEMM, EV_SOLVE_STRIP));
     if (!bad.rc && c1 < nct) {
       GemmArgs g{};
       g.C = V + (int64_t)c1 * TILE * ldv;
       g.ldc = ldv;
-      g.A = e->dA + (int64_t)c1 * TILE + (int64_t)c0 * TILE * e->ld;
+      g.A = v.A + (int64_t)c1 * TILE + (int64_t)c0 * TILE * e->ld;
       g.lda = e->ld;
       g.B = V + (int64_t)c0 * TILE * ldv;
       g.ldb = ldv;
@@ -601,7 +599,7 @@ int cap_solve(gmb_engine* e, const gmb_comm* comm, double* V, int64_t ldv, int n
       g.k = (c1 - c0) * TILE;
       g.alpha = -1.0;
       g.beta = 1.0;
-      bad.note(e, launch_gemm(e, g, 3));
+      bad.note(e, launch_gemm(e, g, EV_PREDICT_GEMM));
     }
   }
   bad.note(e, order_after(e, commS, st));  // (nothing of this pass is left on the other stream when the caller goes on)

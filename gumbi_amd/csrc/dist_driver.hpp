@@ -369,7 +369,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   e->sync_next = 0;
   e->time_next = 0;
   e->cur = mainS;
-  e->chol_update_kind = 0;  // chol_cols factors the panels' squares: in-panel products
+  const FactorRef F = train_factor(e);
   DistDeferred bad;
   DistProbe probe;
   bool tail_in_flight = false;  // a TAIL has been issued on the communication stream since the last FORK
@@ -424,7 +424,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         if ((rc = dist_all_gather(e, comm, mainS, e->dsend, e->drecv, s.elems, &probe))) break;
         if ((rc = dist_pack(e, mainS, cols, e->ld, e->drecv, ldp, s.elems, (int)W, false, G, 0, 0, G, s.lo, s.hi, s.maxcount))) break;
         e->cur = mainS;
-        rc = chol_cols(e, s.c0, s.c1, s.c1);  // the square only: rows below are PANEL's
+        rc = chol_cols(e, F, s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);  // the square only (rows below are PANEL's): in-panel products
         break;
       }
       case DIST_SOLVE: {  // my rows below the square, solved in the packed staging buffer and put back: no communication
@@ -433,7 +433,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         if (s.count <= 0) break;
         if ((rc = dist_pack(e, mainS, cols, e->ld, e->dsend, ldp, 0, (int)W, true, 0, s.first, s.count, G, 0, 0, s.maxcount))) break;
         e->cur = mainS;
-        if ((rc = trsm_cols(e, e->dsend - (int64_t)s.c0 * TILE * ldp, ldp, s.count, s.c0, s.c1, 2, 5))) break;
+        if ((rc = trsm_cols(e, F, e->dsend - (int64_t)s.c0 * TILE * ldp, ldp, s.count, s.c0, s.c1, EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP))) break;
         rc = dist_pack(e, mainS, cols, e->ld, e->dsend, ldp, 0, (int)W, false, 0, s.first, s.count, G, 0, 0, s.maxcount);
         break;
       }
@@ -472,7 +472,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         g.tri_off = (s.first - s.lo) * TILE;
         g.nblk_stride = G;
         e->cur = s.stream ? bulkS : mainS;
-        rc = launch_gemm(e, g, 7);
+        rc = launch_gemm(e, g, EV_CHOL_UPDATE);
         e->cur = mainS;
         break;
       }
@@ -627,7 +627,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
     int f2, mine;
     dist_owned(rank, G, 0, k1, &f2, &mine);
     const int mc = dist_max_owned(G, 0, k1);
-    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, V, ldv, mine, k0, k1, 4, 6, first, G));
+    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, train_factor(e), V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
     bad.note(e, order_after(e, mainS, commS));  // the chunk is final
     if (!bad.rc && mine > 0 && k1 < nt) {  // right-looking: V[:, k1:] -= V[:, k0:k1] L[k1:, k0:k1]^T, structural zeros skipped
       GemmArgs g{};
@@ -645,7 +645,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.klo_n = 1;
       g.krow_stride = G;
       g.krow_off = (first - k0) * TILE;
-      bad.note(e, launch_gemm(e, g, 4));
+      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
     }
     // ship the finished chunk while the update above runs (it only READS the chunk, and the unpack writes
     // rows < k1 of the factor buffer's chunk columns, the update reads rows >= k1 of them): rows b < k1 of

@@ -50,9 +50,24 @@ constexpr int DIST_HEADER = 3;       // words in front of them: status | collect
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// what a timed launch is, for ev_collect's sums; the values are written into GMB_TRACE_FILE lines and never change
+enum EvKind : int {
+  EV_CHOL_PANEL_GEMM = 0,   // Cholesky: in-panel product of the latency-bound chain
+  EV_LEAF = 1,              // potrf leaf
+  EV_CHOL_SOLVE_GEMM = 2,   // Cholesky: product of a panel's triangular solve (multi-GPU drivers)
+  EV_PREDICT_GEMM = 3,      // prediction (the tile triangular solve included)
+  EV_GRAD_GEMM = 4,         // gradient
+  EV_CHOL_STRIP = 5,        // Cholesky: strip solve below a leaf
+  EV_SOLVE_STRIP = 6,       // strip solve of the prediction's / the gradient's triangular solve
+  EV_CHOL_UPDATE = 7,       // Cholesky: bulk trailing update
+  EV_CHOL_TILES = 8,        // the persistent tile Cholesky, whole matrix
+  EV_EVAL_TILES = 9,        // the persistent evaluation launch
+  EV_CHOL_TILES_PANEL = 10  // the tile kernel on a panel at the recursion's bottom
+};
+
 struct EventPair {
   hipEvent_t a, b;
-  int kind;  // 0 chol in-panel gemm, 7 chol bulk trailing update, 1 leaf, 2 trsm gemm, 5 / 6 strips, 3 predict gemm, 4 grad gemm
+  EvKind kind;
   double flops;
   int mt, nt, k, flags;
   bool masked = false;  // launched on the CU-masked bulk stream
@@ -65,6 +80,29 @@ constexpr int GACC_DOUBLES = (1 + GMB_MAX_COREG) * GACC_REGION;  // additive mod
 // the engine's scalar block, ONE allocation (one memset per evaluation): [0, 64) scalars ([0] log-det, [1] |v|^2, [2 ..] the partials
 // and arrival counter of the |v|^2 sum) | [64, 72) the failure index (int32) | [72, ...) the gradient accumulators + 64 of scratch
 constexpr int SCAL_INFO_AT = 64, SCAL_GACC_AT = 72, SCAL_DOUBLES = SCAL_GACC_AT + GACC_DOUBLES + 64;
+
+// The matrix a Cholesky / triangular-solve host routine works on, said by its caller: the training factor (train_factor), the
+// joint posterior's C (joint_factor_ref), a panel window of the capacity driver (cap_window).  A VIEW: the buffers and their
+// capacities stay with their owner; only the tile kernel's control block is reached through its owner's pointer and capacity,
+// because the launches grow it (ensure).
+struct FactorRef {
+  double* A;          // column-major, leading dimension ld: Sigma's lower triangle in, L out
+  int64_t ld;
+  int64_t N, Np, Nr;  // order; padded to 128; rows of the bordered layout ((N + 1) up)
+  double* dinv16;     // 8 x (16 x 16) sub-block inverses per diagonal block
+  double* scal;       // head of a scalar block: [0] log-det, the info word (int32) at SCAL_INFO_AT
+  uint32_t** ct;      // control block of the persistent tile kernel
+  int64_t* cap_ct;
+  int32_t* info() const { return reinterpret_cast<int32_t*>(scal + SCAL_INFO_AT); }
+};
+
+// what the tile kernel did in a factorisation, for the caller that has to look at it afterwards
+struct CholResult {
+  bool tiles = false;     // it ran (whole matrix, panels, or the fused evaluation launch): the abort word has to be read back
+  bool traced = false;    // ... and left task stamps in dct_trace
+  bool injected = false;  // ... with injected faults (its failure is reported, not retried)
+  int ntasks = 0;         // tasks of the whole-matrix launch
+};
 
 struct gmb_engine {
   int device = 0;
@@ -196,9 +234,6 @@ struct gmb_engine {
   // level-parallel triangular inverse (independent merges dealt over stream + aux[0..2])
   hipStream_t cur = nullptr;
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-  // event kind of the updates chol_cols issues: 7 (bulk trailing update) for the plain recursion over the whole
-  // matrix, 0 (in-panel product of the latency-bound chain) inside the look-ahead schedules' panels
-  int chol_update_kind = 7;
   // -1 = by size; 0 = plain recursion; 2 = masked look-ahead; 3 = persistent tile kernel (chol_tiles.hpp)
   int chol_scheme = -1;
   // persistent tile Cholesky: control words + per-tile flags (zeroed before every launch), optional task trace
@@ -207,14 +242,10 @@ struct gmb_engine {
   unsigned long long* dct_trace = nullptr;
   int64_t cap_ct_trace = 0;
   bool ct_trace = false;
-  bool ct_used = false;      // the last factorisation ran on the tile kernel (its abort word has to be read back)
-  bool ct_panels = false;    // ... as panel launches at the bottom of the recursion (chol_tiles_panel)
-  bool ct_traced = false;    // ... and left task stamps in dct_trace
+  CholResult chol;           // what the tile kernel did in the last TRAINING factorisation
   bool tt_used = false;      // the current prediction ran its triangular solve on the tile kernel (same abort word)
-  int ct_ntasks = 0;
   int ct_lose = 0;           // fault injection (gmb_debug_chol_lose_tickets): one shot
   bool fact_in_flight = false;  // factorize_enqueue has run, factorize_finish has not
-  bool ct_injected = false;  // the last tile launch ran with injected faults (its failure is reported, not retried)
   // a factorisation that has been enqueued but not checked yet (factorize_enqueue / factorize_finish): where its scalars
   // land on the host, and the events around its two phases
   // (PINNED host memory: an asynchronous copy into pageable memory makes the host wait for the stream, and the gradient of
@@ -261,13 +292,13 @@ struct gmb_engine {
   int et_min_blocks = 1;       // smallest matrix (in 128-blocks) whose MAP evaluation runs as the fused launch by default
   // the bottom of the plain recursion (matrices beyond tiles_max_blocks): panels of <= panel_tiles_w block columns, with every
   // row below them, are factored by ONE launch of the tile kernel instead of leaf / strip / small-product launches
-  // (chol_tiles_panel).  `panel_tiles_on` is raised by factorize_enqueue around the single-engine recursion
+  // (chol_tiles_panel).  chol_factor asks chol_cols for them, i.e. the single-engine recursion
   // only: the multi-GPU driver's chains run beside a bulk stream whose workgroups a persistent launch would not fit beside.
   // Width by A/B on one box at N = 50k (profiles/r06_panel_tiles_ab.txt): launches only 598 ms; 4: 600, 8: 594.5, 16: 591, 32: 594 --
   // the panel launch does the in-panel work at the bulk updates' rate (73 TF/s-equivalent, chain included); what it takes away
   // is the ~500 launch boundaries of the leaves, strips and small products.
   int panel_tiles_w = 16;
-  bool panel_tiles_on = false, panel_tiles_veto = false;
+  bool panel_tiles_veto = false;
   int tiles_min_blocks = 6, tiles_max_blocks = 224;  // matrices (in 128-blocks) the tile kernel factors by default (measured faster from N = 768 on)
   int tiles_trsm_min_blocks = 16;                    // ... and the tile triangular solve of the predict path (measured from N = 2560 on)
   int masked_max_blocks = 128;  // GMB_MASKED_MAX_BLOCKS: largest matrix (in 128-blocks) factored with the masked bulk stream
@@ -399,7 +430,7 @@ struct PhaseTimer {
   }
 };
 
-void ev_begin(gmb_engine* e, int kind, double flops, int mt = 0, int nt = 0, int k = 0, int flags = 0) {
+void ev_begin(gmb_engine* e, EvKind kind, double flops, int mt = 0, int nt = 0, int k = 0, int flags = 0) {
   if (!e->profiling) return;
   EventPair p;
   p.mt = mt;
@@ -451,14 +482,17 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       if (cur_hi >= cur_lo) uni += cur_hi - cur_lo;
       return uni;
     };
-    e->tm.total_gemm_wall_ms += interval_union([](int k) { return k == 0 || k == 7 || k == 10 || k == 2 || k == 3 || k == 4; });
-    e->tm.total_chol_gemm_wall_ms += interval_union([](int k) { return k == 7; });
+    e->tm.total_gemm_wall_ms += interval_union([](EvKind k) {
+      return k == EV_CHOL_PANEL_GEMM || k == EV_CHOL_UPDATE || k == EV_CHOL_TILES_PANEL || k == EV_CHOL_SOLVE_GEMM || k == EV_PREDICT_GEMM ||
+             k == EV_GRAD_GEMM;
+    });
+    e->tm.total_chol_gemm_wall_ms += interval_union([](EvKind k) { return k == EV_CHOL_UPDATE; });
   }
   for (auto& p : e->evs) {
     float t = 0.f;
     (void)hipEventElapsedTime(&t, p.a, p.b);
-    if (trace) fprintf(trace, "%d %d %d %d %d %.5f %.1f\n", p.kind, p.mt, p.nt, p.k, p.flags, t, p.flops / 1e9);
-    if (p.kind == 0 || p.kind == 7 || p.kind == 8 || p.kind == 9 || p.kind == 10 || p.kind == 2 || p.kind == 3 || p.kind == 4) {
+    if (trace) fprintf(trace, "%d %d %d %d %d %.5f %.1f\n", (int)p.kind, p.mt, p.nt, p.k, p.flags, t, p.flops / 1e9);
+    if (p.kind != EV_LEAF && p.kind != EV_CHOL_STRIP && p.kind != EV_SOLVE_STRIP) {  // every product and persistent launch
       e->tm.total_gemm_ms += t;
       e->tm.total_gemm_flops += p.flops;
       e->tm.total_gemm_launches += 1;
@@ -468,7 +502,7 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       }
     }
     switch (p.kind) {
-      case 8:  // the persistent tile kernel: contraction, leaves and strip solves of the whole factorisation in one launch
+      case EV_CHOL_TILES:  // the persistent tile kernel: contraction, leaves and strip solves of the whole factorisation in one launch
         e->tm.total_chol_tile_ms += t;
         e->tm.total_chol_tile_flops += p.flops;
         e->tm.total_chol_tile_launches += 1;
@@ -476,14 +510,14 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
         e->tm.chol_gemm_flops += p.flops;
         e->tm.chol_gemm_launches += 1;
         break;
-      case 9:  // the persistent evaluation launch: (factorisation +) inverse + Sigma^-1 (flags & 1: with the factorisation)
+      case EV_EVAL_TILES:  // the persistent evaluation launch: (factorisation +) inverse + Sigma^-1 (flags & 1: with the factorisation)
         e->tm.total_eval_tile_ms += t;
         e->tm.total_eval_tile_flops += p.flops;
         e->tm.total_eval_tile_launches += 1;
         e->tm.grad_gemm_ms += t;
         e->tm.grad_gemm_flops += p.flops;
         break;
-      case 10:  // a panel of the recursion's bottom on the tile kernel: in-panel work of the chain, like kind 0
+      case EV_CHOL_TILES_PANEL:  // a panel of the recursion's bottom on the tile kernel: in-panel work of the chain, like kind 0
         e->tm.chol_gemm_ms += t;
         e->tm.chol_gemm_flops += p.flops;
         e->tm.chol_gemm_launches += 1;
@@ -493,8 +527,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
         e->tm.total_chol_panel_tile_flops += p.flops;
         e->tm.total_chol_panel_tile_launches += 1;
         break;
-      case 0:
-      case 7:
+      case EV_CHOL_PANEL_GEMM:
+      case EV_CHOL_UPDATE:
         e->tm.chol_gemm_ms += t;
         e->tm.chol_gemm_flops += p.flops;
         e->tm.chol_gemm_launches += 1;
@@ -503,7 +537,7 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
           e->tm.total_chol_update_all_flops += p.flops;
           e->tm.total_chol_update_all_launches += 1;
         }
-        if (p.kind == 7) {
+        if (p.kind == EV_CHOL_UPDATE) {
           e->tm.total_chol_gemm_ms += t;
           e->tm.total_chol_gemm_flops += p.flops;
           e->tm.total_chol_gemm_launches += 1;
@@ -512,18 +546,19 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
           e->tm.total_chol_panel_gemm_flops += p.flops;
         }
         break;
-      case 1: e->tm.chol_leaf_ms += t; break;
-      case 2:
-      case 5: e->tm.chol_trsm_ms += t; break;
-      case 3:
+      case EV_LEAF: e->tm.chol_leaf_ms += t; break;
+      case EV_CHOL_SOLVE_GEMM:
+      case EV_CHOL_STRIP: e->tm.chol_trsm_ms += t; break;
+      case EV_PREDICT_GEMM:
         e->tm.predict_gemm_ms += t;
         e->tm.predict_gemm_flops += p.flops;
         e->tm.predict_gemm_launches += 1;
         break;
-      case 4:
+      case EV_GRAD_GEMM:
         e->tm.grad_gemm_ms += t;
         e->tm.grad_gemm_flops += p.flops;
         break;
+      case EV_SOLVE_STRIP: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -546,7 +581,7 @@ long long gemm_nact128(const GemmArgs& g) {
   return nact;
 }
 
-int launch_gemm(gmb_engine* e, const GemmArgs& g_in, int ev_kind) {
+int launch_gemm(gmb_engine* e, const GemmArgs& g_in, EvKind ev_kind) {
   if (g_in.mt <= 0 || g_in.nt <= 0 || g_in.k <= 0) return GMB_OK;
   GemmArgs g = g_in;
   // tiles the 128 x 128 tiling would compute
@@ -614,9 +649,9 @@ int launch_gemm(gmb_engine* e, const GemmArgs& g_in, int ev_kind) {
   // entry point of their own (gemm_f64_dma_chol_update_kernel, the same body), so that a rocprofv3 kernel trace lists exactly
   // the launches the live events of `roofline` time.  Kind-7 launches small enough for another tile shape count as in-panel
   // products (kind 0), like the panels' own.
-  const bool bulk_update = ev_kind == 7 && variant == 0 && !in_place;
-  const int was_update = ev_kind == 7 ? (1 << 16) : 0;  // issued AS a trailing update, whatever tile shape it runs (total_chol_update_all_*)
-  if (ev_kind == 7 && !bulk_update) ev_kind = 0;
+  const bool bulk_update = ev_kind == EV_CHOL_UPDATE && variant == 0 && !in_place;
+  const int was_update = ev_kind == EV_CHOL_UPDATE ? (1 << 16) : 0;  // issued AS a trailing update, whatever tile shape it runs (total_chol_update_all_*)
+  if (ev_kind == EV_CHOL_UPDATE && !bulk_update) ev_kind = EV_CHOL_PANEL_GEMM;
   ev_begin(e, ev_kind, flops, g_in.mt, g_in.nt, g.k,
            g.tri | (g.klo_n << 3) | (g.khi_n << 4) | (g.klo_m << 5) | (variant << 8) | was_update);
   const dim3 grid(nblocks);
@@ -651,7 +686,7 @@ int launch_gemm(gmb_engine* e, const GemmArgs& g_in, int ev_kind) {
 
 // B <- B inv(L_kk)^T on `nrows` rows (multiple of 16): one wavefront per 16 rows
 int launch_trsm_strip(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, const double* L, int64_t ldl,
-                      const double* dinv16, int nvalid, int ev_kind) {
+                      const double* dinv16, int nvalid, EvKind ev_kind) {
   if (nrows <= 0) return GMB_OK;
   TrsmArgs t;
   t.B = B;
@@ -669,7 +704,7 @@ int launch_trsm_strip(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, cons
 }
 
 int launch_leaf(gmb_engine* e, const LeafArgs& a) {
-  ev_begin(e, 1, 0.0);
+  ev_begin(e, EV_LEAF, 0.0);
   if (e->naive_leaf)
     hipLaunchKernelGGL(potrf_leaf_naive_kernel, dim3(1), dim3(256), 0, e->cur, a);
   else
@@ -945,10 +980,10 @@ int flush_deferred_prep(gmb_engine* e) {
 PointSet train_set(const gmb_engine* e) { return PointSet{e->xs, e->xl, e->cat, e->N, e->Nr}; }
 
 // the full factor buffer (Nr x Np, leading dimension Nr), allocated on first use
-int ensure_factor_buffer(gmb_engine* e) {
-  if (e->dist_mode == 1 && e->dA && e->cap_A == 0) e->dA = nullptr;  // (a virtual base left behind by the capacity driver)
-  return ensure(e, &e->dA, &e->cap_A, e->ld * e->Np);
-}
+int ensure_factor_buffer(gmb_engine* e) { return ensure(e, &e->dA, &e->cap_A, e->ld * e->Np); }
+
+// the training factor as the Cholesky / triangular-solve routines take it
+FactorRef train_factor(gmb_engine* e) { return FactorRef{e->dA, e->ld, e->N, e->Np, e->Nr, e->dDinv16, e->dscal, &e->dct, &e->cap_ct}; }
 
 // Covariance build: lower-triangular tiles of Sigma = K + noise + jitter, the y row, identity padding, written
 // column-major into `out` (Nr x Np, leading dimension ldo) -- the factor buffer in gmb_factorize.
@@ -989,62 +1024,66 @@ int build_sigma(gmb_engine* e, double* out, int64_t ldo) {
 // ---- Cholesky recursion -------------------------------------------------------------------
 // `rend`: block row where the panel solve / updates stop (the whole matrix, or the end of a
 // diagonal square when the rows below are solved later in bulk)
-int chol_leaf(gmb_engine* e, int c, int rend) {
+int chol_leaf(gmb_engine* e, const FactorRef& f, int c, int rend) {
   LeafArgs a{};
-  a.A = e->dA + (int64_t)c * TILE + (int64_t)c * TILE * e->ld;
-  a.lda = e->ld;
-  a.nvalid = (int)std::min<int64_t>(TILE, e->N - (int64_t)c * TILE);
-  a.dinv16 = e->dDinv16 + (int64_t)c * 8 * 256;
-  a.logdet = e->dscal;
-  a.info = e->dinfo;
+  a.A = f.A + (int64_t)c * TILE + (int64_t)c * TILE * f.ld;
+  a.lda = f.ld;
+  a.nvalid = (int)std::min<int64_t>(TILE, f.N - (int64_t)c * TILE);
+  a.dinv16 = f.dinv16 + (int64_t)c * 8 * 256;
+  a.logdet = f.scal;
+  a.info = f.info();
   a.row0 = (int64_t)c * TILE;
   a.dbg = nullptr;
   int rc = launch_leaf(e, a);
   if (rc) return rc;
   // panel rows below the diagonal block:  P <- P inv(L_cc)^T   (in place, 16 rows per wavefront)
-  return launch_trsm_strip(e, e->dA + (int64_t)(c + 1) * TILE + (int64_t)c * TILE * e->ld, e->ld,
-                           (int64_t)(rend - c - 1) * TILE, a.A, e->ld, a.dinv16, a.nvalid, 5);
+  return launch_trsm_strip(e, f.A + (int64_t)(c + 1) * TILE + (int64_t)c * TILE * f.ld, f.ld,
+                           (int64_t)(rend - c - 1) * TILE, a.A, f.ld, a.dinv16, a.nvalid, EV_CHOL_STRIP);
 }
 
-int chol_tiles_panel(gmb_engine* e, int c0, int c1, int rend);
+int chol_tiles_panel(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, CholResult* res);
 
-int chol_cols(gmb_engine* e, int c0, int c1, int rend) {
-  if (c1 - c0 == 1) return chol_leaf(e, c0, rend);
-  if (e->panel_tiles_on && c1 - c0 <= e->panel_tiles_w) return chol_tiles_panel(e, c0, c1, rend);
+// `update_kind`: what the trailing updates are timed as -- EV_CHOL_UPDATE (bulk) for the plain recursion over the whole matrix,
+// EV_CHOL_PANEL_GEMM (in-panel product of the latency-bound chain) inside the look-ahead schedules' panels.  `tile_panels`, if
+// given: panels of <= panel_tiles_w block columns go to the tile kernel (chol_tiles_panel), which reports there.
+int chol_cols(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, EvKind update_kind, CholResult* tile_panels = nullptr) {
+  if (c1 - c0 == 1) return chol_leaf(e, f, c0, rend);
+  if (tile_panels && c1 - c0 <= e->panel_tiles_w) return chol_tiles_panel(e, f, c0, c1, rend, tile_panels);
   const int mid = c0 + (c1 - c0 + 1) / 2;
-  int rc = chol_cols(e, c0, mid, rend);
+  int rc = chol_cols(e, f, c0, mid, rend, update_kind, tile_panels);
   if (rc) return rc;
   GemmArgs g{};
-  g.C = e->dA + (int64_t)mid * TILE + (int64_t)mid * TILE * e->ld;
-  g.ldc = e->ld;
-  g.A = e->dA + (int64_t)mid * TILE + (int64_t)c0 * TILE * e->ld;
-  g.lda = e->ld;
+  g.C = f.A + (int64_t)mid * TILE + (int64_t)mid * TILE * f.ld;
+  g.ldc = f.ld;
+  g.A = f.A + (int64_t)mid * TILE + (int64_t)c0 * TILE * f.ld;
+  g.lda = f.ld;
   g.B = g.A;
-  g.ldb = e->ld;
+  g.ldb = f.ld;
   g.mt = c1 - mid;
   g.nt = rend - mid;
   g.k = (mid - c0) * TILE;
   g.alpha = -1.0;
   g.beta = 1.0;
   g.tri = 1;
-  rc = launch_gemm(e, g, e->chol_update_kind);
+  rc = launch_gemm(e, g, update_kind);
   if (rc) return rc;
-  return chol_cols(e, mid, c1, rend);
+  return chol_cols(e, f, mid, c1, rend, update_kind, tile_panels);
 }
 
 // The ragged last block of the persistent launches (chol_tiles.hpp: ct_ksum<.., RAG>): the fraction of a tile's contraction that
 // the last block ROW's tasks (rows: the y row included) and the last block COLUMN's solve / inverse tasks still perform
-double ragged_row_frac(const gmb_engine* e) {
-  const int64_t rv = e->N + 1 - (e->Nr - TILE);
+double ragged_row_frac(const FactorRef& f) {
+  const int64_t rv = f.N + 1 - (f.Nr - TILE);
   return rv >= TILE ? 1.0 : (double)((rv + 15) / 16) / 8.0;
 }
-double ragged_col_frac(const gmb_engine* e) {
-  const int64_t cv = e->N - (e->Np - TILE);
+double ragged_col_frac(const FactorRef& f) {
+  const int64_t cv = f.N - (f.Np - TILE);
   return cv >= TILE ? 1.0 : (double)((cv + 15) / 16) / 8.0;
 }
-// flops of the tile Cholesky's contractions (2 * 128^3 per k-block of a tile)
-double chol_tiles_flops(const gmb_engine* e, int nct, int nrt) {
-  const double fr = ragged_row_frac(e);
+// flops of the tile Cholesky's contractions (2 * 128^3 per k-block of a tile) on nct block columns with the nrt block rows from
+// their diagonal down; the last block row of the bordered matrix contracts its real rows only
+double chol_tiles_flops(const FactorRef& f, int nct, int nrt, bool to_last_row = true) {
+  const double fr = to_last_row ? ragged_row_frac(f) : 1.0;
   double flops = 0.0;
   for (int j = 1; j < nct; ++j) {
     const double tiles = nrt - 1 > j ? (double)(nrt - j - 1) + fr : (double)(nrt - j);  // (the diagonal tile is never cut)
@@ -1054,44 +1093,64 @@ double chol_tiles_flops(const gmb_engine* e, int nct, int nrt) {
 }
 
 // ---- persistent tile Cholesky (chol_tiles.hpp): the whole factorisation in one launch --------------------
-int chol_tiles(gmb_engine* e) {
-  const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
+// What every persistent launch passes alike: block columns [c0, c0 + nct) of f from their diagonal down, the control words at
+// the head of f's control block (sized by the caller) with the tile flags behind them.  `chol`: the launch factors -- log-det,
+// info word and the chain words behind nrt x nct tile flags.
+CholTilesArgs tiles_args(const FactorRef& f, int c0, int nct, int nrt, int ntasks, bool chol = true) {
+  uint32_t* ct = *f.ct;
+  CholTilesArgs a{};
+  a.A = f.A + (int64_t)c0 * TILE * (f.ld + 1);
+  a.ld = f.ld;
+  a.nct = nct;
+  a.nrt = nrt;
+  a.N = f.N - (int64_t)c0 * TILE;
+  a.row_base = (int64_t)c0 * TILE;
+  a.dinv16 = f.dinv16 + (int64_t)c0 * 8 * 256;
+  a.ctl = ct;
+  a.flags = ct + 4;
+  if (chol) {
+    a.logdet = f.scal;
+    a.info = f.info();
+    a.half = ct + 4 + (int64_t)nrt * nct;
+    a.prog = a.half + 2 * (int64_t)nct;
+  }
+  a.ntasks = ntasks;
+  a.timeout_us = 4000000u;  // a wait of 4 s means a lost flag: give the launch up, never the GPU
+  return a;
+}
+
+// fault injection (gmb_debug_chol_lose_tickets): tickets 0 .. lose-1 of the launch behind the cleared control block are never
+// handed out
+int tiles_lose_tickets(gmb_engine* e, uint32_t* ctl, int lose) {
+  const uint32_t first = (uint32_t)lose;
+  HIP_TRY(e, hipMemcpyAsync(ctl, &first, sizeof first, hipMemcpyHostToDevice, e->cur));
+  HIP_TRY(e, hipStreamSynchronize(e->cur));  // (`first` lives on this stack frame)
+  return GMB_OK;
+}
+
+// a traced launch stamps its tasks into the engine's trace buffer (gmb_chol_task_trace), cleared here
+int tiles_trace_buffer(gmb_engine* e, CholTilesArgs& a) {
+  int rc;
+  if ((rc = ensure(e, &e->dct_trace, &e->cap_ct_trace, 4 * (int64_t)a.ntasks))) return rc;
+  HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)a.ntasks * 4 * sizeof(unsigned long long), e->cur));
+  a.dbg = e->dct_trace;
+  return GMB_OK;
+}
+
+// `trace`, `lose`: task stamps and injected faults, as the caller of the factorisation asks for them
+int chol_tiles(gmb_engine* e, const FactorRef& f, bool trace, int lose, CholResult* res) {
+  const int nct = (int)(f.Np / TILE), nrt = (int)(f.Nr / TILE);
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
-  if ((rc = ensure(e, &e->dct, &e->cap_ct, words))) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), e->cur));
-  e->ct_injected = e->ct_lose > 0;
-  if (e->ct_lose > 0) {  // fault injection: tickets 0 .. ct_lose-1 are never handed out
-    const uint32_t first = (uint32_t)e->ct_lose;
-    e->ct_lose = 0;
-    HIP_TRY(e, hipMemcpyAsync(e->dct, &first, sizeof first, hipMemcpyHostToDevice, e->cur));
-    HIP_TRY(e, hipStreamSynchronize(e->cur));  // (`first` lives on this stack frame)
-  }
-  CholTilesArgs a{};
-  a.A = e->dA;
-  a.ld = e->ld;
-  a.nct = nct;
-  a.nrt = nrt;
-  a.N = e->N;
-  a.dinv16 = e->dDinv16;
-  a.logdet = e->dscal;
-  a.info = e->dinfo;
-  a.ctl = e->dct;
-  a.flags = e->dct + 4;
-  a.half = e->dct + 4 + (int64_t)nrt * nct;
-  a.prog = a.half + 2 * (int64_t)nct;
-  a.ntasks = ntasks;
-  a.timeout_us = 4000000u;  // a wait of 4 s means a lost flag: give the factorisation up, never the GPU
-  a.dbg = nullptr;
-  e->ct_traced = false;
-  if (e->ct_trace) {
-    e->ct_traced = true;
-    if ((rc = ensure(e, &e->dct_trace, &e->cap_ct_trace, 4 * (int64_t)ntasks))) return rc;
-    HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)ntasks * 4 * sizeof(unsigned long long), e->cur));
-    a.dbg = e->dct_trace;
-  }
-  const double flops = chol_tiles_flops(e, nct, nrt);
+  if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), e->cur));
+  res->injected = lose > 0;
+  if (lose > 0 && (rc = tiles_lose_tickets(e, *f.ct, lose))) return rc;
+  CholTilesArgs a = tiles_args(f, 0, nct, nrt, ntasks);
+  res->traced = trace;
+  if (trace && (rc = tiles_trace_buffer(e, a))) return rc;
+  const double flops = chol_tiles_flops(f, nct, nrt);
   // eight-wave workgroups, one per compute unit: every phase of the latency chain has the whole compute unit (N = 10k:
   // 6.8 ms against 8.7 ms with four-wave workgroups, two per compute unit -- which stay available to the tuning build)
   int nw = 8;
@@ -1102,13 +1161,13 @@ int chol_tiles(gmb_engine* e) {
 #ifdef GMB_TUNING
   if (const char* cg = getenv("GMB_CT_GRID")) grid = std::max(1, std::min(grid, atoi(cg)));
 #endif
-  ev_begin(e, 8, flops, nct, nrt, (int)e->Np, 0);
+  ev_begin(e, EV_CHOL_TILES, flops, nct, nrt, (int)f.Np, 0);
   if (nw == 8) hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
   else hipLaunchKernelGGL(chol_tiles_kernel<4>, dim3(grid), dim3(256), 0, e->cur, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
-  e->ct_used = true;
-  e->ct_ntasks = ntasks;
+  res->tiles = true;
+  res->ntasks = ntasks;
   return GMB_OK;
 }
 
@@ -1116,75 +1175,45 @@ int chol_tiles(gmb_engine* e) {
 // c0 already: ONE launch of the tile kernel on that panel (left-looking tile tasks inside it; the rows below the square ride
 // along as in the whole-matrix form).  Replaces, per panel of 16 block columns at C3, 16 leaf + 16 strip + 15 product launches
 // (the 64 x 64-tile products that run at 45 TF/s: profiles/r05_bench_c3_kernel_stats.csv).  The control block is the tile
-// Cholesky's; its ABORT word is not cleared between the panels of one factorisation (factorize_enqueue clears it once), so a
+// Cholesky's; its ABORT word is not cleared between the panels of one factorisation (chol_factor clears it once), so a
 // panel that gave up waiting makes every later one drain and the host sees it at the end.
-int chol_tiles_panel(gmb_engine* e, int c0, int c1, int rend) {
+int chol_tiles_panel(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, CholResult* res) {
   const int nct = c1 - c0, nrt = rend - c0;
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
-  if ((rc = ensure(e, &e->dct, &e->cap_ct, std::max<int64_t>(words, 4 + (int64_t)(e->panel_tiles_w + 3) * (e->Nr / TILE))))) return rc;  // (one size for every panel of the matrix)
-  HIP_TRY(e, hipMemsetAsync(e->dct, 0, sizeof(uint32_t), e->cur));                                       // the ticket counter
-  HIP_TRY(e, hipMemsetAsync(e->dct + 2, 0, (size_t)(words - 2) * sizeof(uint32_t), e->cur));            // flags and chain words
-  CholTilesArgs a{};
-  a.A = e->dA + (int64_t)c0 * TILE * (e->ld + 1);
-  a.ld = e->ld;
-  a.nct = nct;
-  a.nrt = nrt;
-  a.N = e->N - (int64_t)c0 * TILE;
-  a.row_base = (int64_t)c0 * TILE;
-  a.dinv16 = e->dDinv16 + (int64_t)c0 * 8 * 256;
-  a.logdet = e->dscal;
-  a.info = e->dinfo;
-  a.ctl = e->dct;
-  a.flags = e->dct + 4;
-  a.half = e->dct + 4 + (int64_t)nrt * nct;
-  a.prog = a.half + 2 * (int64_t)nct;
-  a.ntasks = ntasks;
-  a.timeout_us = 4000000u;
-  a.dbg = nullptr;
-  // flops of the panel's contractions (the last block row of the bordered matrix contracts its real rows only)
-  const double fr = rend == (int)(e->Nr / TILE) ? ragged_row_frac(e) : 1.0;
-  double flops = 0.0;
-  for (int j = 1; j < nct; ++j) flops += 2.0 * TILE * TILE * TILE * (double)j * (nrt - 1 > j ? (double)(nrt - j - 1) + fr : (double)(nrt - j));
+  if ((rc = ensure(e, f.ct, f.cap_ct, std::max<int64_t>(words, 4 + (int64_t)(e->panel_tiles_w + 3) * (f.Nr / TILE))))) return rc;  // (one size for every panel of the matrix)
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, sizeof(uint32_t), e->cur));                                       // the ticket counter
+  HIP_TRY(e, hipMemsetAsync(*f.ct + 2, 0, (size_t)(words - 2) * sizeof(uint32_t), e->cur));            // flags and chain words
+  const CholTilesArgs a = tiles_args(f, c0, nct, nrt, ntasks);
+  const double flops = chol_tiles_flops(f, nct, nrt, rend == (int)(f.Nr / TILE));
   const int grid = (int)std::min<long long>(ntasks, e->wg_slots / 2);
-  ev_begin(e, 10, flops, nct, nrt, nct * TILE, 0);
+  ev_begin(e, EV_CHOL_TILES_PANEL, flops, nct, nrt, nct * TILE, 0);
   hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
-  e->ct_used = true;  // (the abort word is read back with the factorisation's scalars)
-  e->ct_panels = true;
+  res->tiles = true;  // (the abort word is read back with the factorisation's scalars)
   return GMB_OK;
 }
 
 // V <- V L^-T (V: ntm x Np/128 tiles, leading dimension ldv) as one persistent launch (chol_tiles.hpp: trsm_tiles_kernel)
-int trsm_tiles(gmb_engine* e, double* V, int64_t ldv, int ntm, int ev_kind) {
-  const int nct = (int)(e->Np / TILE);
+int trsm_tiles(gmb_engine* e, const FactorRef& f, double* V, int64_t ldv, int ntm, EvKind ev_kind) {
+  const int nct = (int)(f.Np / TILE);
   const long long ntasks = (long long)ntm * nct;
   if (ntasks <= 0) return GMB_OK;
   const int64_t words = 4 + (int64_t)ntm * nct;
   int rc;
-  if ((rc = ensure(e, &e->dct, &e->cap_ct, words))) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), e->cur));
-  CholTilesArgs a{};
-  a.A = e->dA;
-  a.ld = e->ld;
-  a.nct = nct;
-  a.nrt = nct;
-  a.N = e->N;
-  a.dinv16 = e->dDinv16;
-  a.ctl = e->dct;
-  a.flags = e->dct + 4;
-  a.ntasks = (int)ntasks;
-  a.timeout_us = 4000000u;
+  if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), e->cur));
+  CholTilesArgs a = tiles_args(f, 0, nct, nct, (int)ntasks, false);
   a.V = V;
   a.ldv = ldv;
   a.ntm = ntm;
   double flops = 0.0;
   for (int c = 0; c < nct; ++c)
-    flops += (double)ntm * (2.0 * TILE * TILE * TILE * c * (c == nct - 1 ? ragged_col_frac(e) : 1.0) + (double)TILE * TILE * TILE);
+    flops += (double)ntm * (2.0 * TILE * TILE * TILE * c * (c == nct - 1 ? ragged_col_frac(f) : 1.0) + (double)TILE * TILE * TILE);
   const int grid = (int)std::min<long long>(ntasks, e->wg_slots / 2);
-  ev_begin(e, ev_kind, flops, nct, ntm, (int)e->Np, 0);
+  ev_begin(e, ev_kind, flops, nct, ntm, (int)f.Np, 0);
   hipLaunchKernelGGL(trsm_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
@@ -1207,6 +1236,7 @@ bool eval_will_fuse(const gmb_engine* e) {
 }
 
 int eval_tiles(gmb_engine* e, bool with_chol) {
+  const FactorRef f = train_factor(e);
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   int rc;
   // The ticket counter runs ahead of the factorisation's latency chain by about as many tasks as there are workgroups: an
@@ -1244,36 +1274,15 @@ int eval_tiles(gmb_engine* e, bool with_chol) {
   if (!(with_chol && e->prezeroed)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), e->cur));
   // a factor that is final already: every tile flag reads "final" (any non-zero word)
   if (!with_chol) HIP_TRY(e, hipMemsetAsync(e->dct + 4, 1, (size_t)nrt * nct * sizeof(uint32_t), e->cur));
-  e->ct_injected = with_chol && e->ct_lose > 0;
-  if (with_chol && e->ct_lose > 0) {  // fault injection: tickets 0 .. ct_lose-1 are never handed out
-    const uint32_t first = (uint32_t)e->ct_lose;
+  const int lose = with_chol ? e->ct_lose : 0;
+  e->chol.injected = lose > 0;
+  if (lose > 0) {
     e->ct_lose = 0;
-    HIP_TRY(e, hipMemcpyAsync(e->dct, &first, sizeof first, hipMemcpyHostToDevice, e->cur));
-    HIP_TRY(e, hipStreamSynchronize(e->cur));
+    if ((rc = tiles_lose_tickets(e, e->dct, lose))) return rc;
   }
-  CholTilesArgs a{};
-  a.A = e->dA;
-  a.ld = e->ld;
-  a.nct = nct;
-  a.nrt = nrt;
-  a.N = e->N;
-  a.dinv16 = e->dDinv16;
-  a.logdet = e->dscal;
-  a.info = e->dinfo;
-  a.ctl = e->dct;
-  a.flags = e->dct + 4;
-  a.half = e->dct + 4 + (int64_t)nrt * nct;
-  a.prog = a.half + 2 * (int64_t)nct;
-  a.ntasks = ntasks;
-  a.timeout_us = 4000000u;
-  a.dbg = nullptr;
-  e->ct_traced = false;
-  if (e->ct_trace) {
-    e->ct_traced = true;
-    if ((rc = ensure(e, &e->dct_trace, &e->cap_ct_trace, 4 * (int64_t)ntasks))) return rc;
-    HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)ntasks * 4 * sizeof(unsigned long long), e->cur));
-    a.dbg = e->dct_trace;
-  }
+  CholTilesArgs a = tiles_args(f, 0, nct, nrt, ntasks);
+  e->chol.traced = e->ct_trace;
+  if (e->ct_trace && (rc = tiles_trace_buffer(e, a))) return rc;
   EvalTilesArgs x{};
   x.tasks = e->det_tasks;
   x.ntasks = ntasks;
@@ -1289,20 +1298,20 @@ int eval_tiles(gmb_engine* e, bool with_chol) {
   x.vpart = e->dApart + (int64_t)nct * nct * TILE;
   x.scal = e->dscal + 1;
   x.with_v = with_chol ? 1 : 0;  // v = L^-1 y with |v|^2, which gmb_factorize takes with extract_v_kernel
-  double flops = with_chol ? chol_tiles_flops(e, nct, nrt) : 0.0;
+  double flops = with_chol ? chol_tiles_flops(f, nct, nrt) : 0.0;
   for (int c = 0; c < nct; ++c)                                                                                       // INV column c
-    flops += 2.0 * TILE * TILE * TILE * 0.5 * (double)c * (double)(c + 1) * (c == nct - 1 ? ragged_col_frac(e) : 1.0);
+    flops += 2.0 * TILE * TILE * TILE * 0.5 * (double)c * (double)(c + 1) * (c == nct - 1 ? ragged_col_frac(f) : 1.0);
   for (int I = 0; I < nct; ++I) flops += 2.0 * TILE * TILE * TILE * (double)(nct - I) * (double)(I + 1);             // ZZ block row I
   const int grid = (int)std::min<long long>(ntasks, nw == 8 ? e->wg_slots / 2 : e->wg_slots);
-  ev_begin(e, 9, flops, nct, nrt, (int)e->Np, with_chol ? 1 : 0);
+  ev_begin(e, EV_EVAL_TILES, flops, nct, nrt, (int)e->Np, with_chol ? 1 : 0);
   if (nw == 8) hipLaunchKernelGGL(eval_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a, x);
 #ifdef GMB_TUNING
   else hipLaunchKernelGGL(eval_tiles_kernel<4>, dim3(grid), dim3(256), 0, e->cur, a, x);
 #endif
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
-  e->ct_used = true;
-  e->ct_ntasks = ntasks;
+  e->chol.tiles = true;
+  e->chol.ntasks = ntasks;
   return GMB_OK;
 }
 
@@ -1332,9 +1341,6 @@ int order_after(gmb_engine* e, hipStream_t from, hipStream_t to) {
   return GMB_OK;
 }
 
-int trsm_cols(gmb_engine* e, double* V, int64_t ldz, int ntm, int c0, int c1, int kind_gemm, int kind_strip,
-              int lfirst = -1, int lstride = 0);
-
 // Look-ahead Cholesky for SMALL matrices (<= masked_max_blocks block columns, N <= 16k): right-looking over
 // panels; the latency-bound chain of panel p+1 (leaves, strips, in-panel products) runs on the main stream
 // beside U2(p), the bulk of the trailing update, which runs on the process-wide CU-masked stream (it leaves 4
@@ -1342,34 +1348,33 @@ int trsm_cols(gmb_engine* e, double* V, int64_t ldz, int ntm, int c0, int c1, in
 // matrix, one stream): there the chain is a few per cent of the work, and bulk updates that share the chip with
 // chain kernels lose more than the overlap wins -- r02: N = 50k 627 ms with look-ahead (bulk updates at 63
 // TF/s) vs 607 ms plain (70.8 TF/s); N = 100k 5.02 vs 4.75 s; N = 24k / 32k 1 % apart; N = 16k equal.
-int chol_lookahead_masked(gmb_engine* e) {
-  const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
+int chol_lookahead_masked(gmb_engine* e, const FactorRef& f) {
+  const int nct = (int)(f.Np / TILE), nrt = (int)(f.Nr / TILE);
   const int w = e->panel_blocks;
   hipStream_t mainS = e->stream, bulkS = e->aux[2];
   e->sync_next = 0;
   int rc;
-  e->chol_update_kind = 0;  // chol_cols below factors panels: its products belong to the chain
   e->cur = mainS;
-  if ((rc = chol_cols(e, 0, std::min(w, nct), nrt))) return rc;
+  if ((rc = chol_cols(e, f, 0, std::min(w, nct), nrt, EV_CHOL_PANEL_GEMM))) return rc;  // (panels: their products belong to the chain)
   for (int c0 = 0; c0 < nct; c0 += w) {
     const int c1 = std::min(c0 + w, nct);
     const int n0 = c1, n1 = std::min(c1 + w, nct);
     if (n0 >= nct) break;
     auto update = [&](int col_lo, int col_hi) {
       GemmArgs g{};
-      g.C = e->dA + (int64_t)col_lo * TILE + (int64_t)col_lo * TILE * e->ld;
-      g.ldc = e->ld;
-      g.A = e->dA + (int64_t)col_lo * TILE + (int64_t)c0 * TILE * e->ld;
-      g.lda = e->ld;
+      g.C = f.A + (int64_t)col_lo * TILE + (int64_t)col_lo * TILE * f.ld;
+      g.ldc = f.ld;
+      g.A = f.A + (int64_t)col_lo * TILE + (int64_t)c0 * TILE * f.ld;
+      g.lda = f.ld;
       g.B = g.A;
-      g.ldb = e->ld;
+      g.ldb = f.ld;
       g.mt = col_hi - col_lo;
       g.nt = nrt - col_lo;
       g.k = (c1 - c0) * TILE;
       g.alpha = -1.0;
       g.beta = 1.0;
       g.tri = 1;
-      return launch_gemm(e, g, 7);
+      return launch_gemm(e, g, EV_CHOL_UPDATE);
     };
     e->cur = mainS;
     if ((rc = order_after(e, bulkS, mainS))) return rc;   // U2(p-1) reached these columns
@@ -1379,30 +1384,58 @@ int chol_lookahead_masked(gmb_engine* e) {
     rc = (n1 < nct) ? update(n1, nct) : 0;          // U2, on the compute units its mask allows
     e->cur = mainS;
     if (rc) return rc;
-    if ((rc = chol_cols(e, n0, n1, nrt))) return rc;      // panel p+1, beside U2
+    if ((rc = chol_cols(e, f, n0, n1, nrt, EV_CHOL_PANEL_GEMM))) return rc;  // panel p+1, beside U2
   }
   e->cur = mainS;
   return order_after(e, bulkS, mainS);
+}
+
+// what the caller of a factorisation asks for beyond the matrix
+struct CholOpts {
+  bool masked_ok = false;  // the masked look-ahead may be chosen (the training factorisation only: C has never been factored on it)
+  bool trace = false;      // a whole-matrix tile launch stamps its tasks (gmb_chol_task_trace)
+  int lose = 0;            // ... and loses its first tickets (gmb_debug_chol_lose_tickets); `res->injected` says it took them
+};
+
+// f -> L in place on e->stream, by the schedule its size asks for: the persistent tile kernel from tiles_min_blocks to
+// tiles_max_blocks block columns (or under scheme 3), the masked look-ahead where allowed, else the plain recursion with its
+// bottom panels as launches of the tile kernel.  Nothing is synchronised; `res` (cleared by the caller) says what to read back.
+int chol_factor(gmb_engine* e, const FactorRef& f, const CholOpts& o, CholResult* res) {
+  const int nblocks = (int)(f.Np / TILE), nrt = (int)(f.Nr / TILE);
+  const bool tiles = !e->naive_leaf && (e->chol_scheme == 3 || (e->chol_scheme < 0 && nblocks >= e->tiles_min_blocks &&
+                                                                 nblocks <= e->tiles_max_blocks));
+  const bool masked = o.masked_ok && !tiles && e->lookahead && e->aux_shared && nblocks > e->panel_blocks &&
+                      (e->chol_scheme == 2 || (e->chol_scheme < 0 && nblocks <= e->masked_max_blocks));
+  e->cur = e->stream;
+  if (tiles) return chol_tiles(e, f, o.trace, o.lose, res);
+  if (masked) return chol_lookahead_masked(e, f);
+  const bool tile_panels = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
+  if (tile_panels) {
+    int rc;
+    if ((rc = ensure(e, f.ct, f.cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * nrt))) return rc;
+    HIP_TRY(e, hipMemsetAsync(*f.ct, 0, 4 * sizeof(uint32_t), e->stream));  // (the abort word: once per factorisation)
+  }
+  return chol_cols(e, f, 0, nblocks, nrt, EV_CHOL_UPDATE, tile_panels ? res : nullptr);
 }
 
 // ---- predict recursion: V <- W L^-T over column blocks [c0, c1) ------------------------------
 // lfirst / lstride (optional): row tile t of V stands for block row lfirst + t*lstride of a matrix
 // whose rows are zero left of their own diagonal block (rows of the identity being solved into
 // rows of L^-T): the update products then skip the structurally zero part of their contraction.
-int trsm_cols(gmb_engine* e, double* V, int64_t ldz, int ntm, int c0, int c1, int kind_gemm, int kind_strip,
-              int lfirst, int lstride) {
+int trsm_cols(gmb_engine* e, const FactorRef& f, double* V, int64_t ldz, int ntm, int c0, int c1, EvKind kind_gemm, EvKind kind_strip,
+              int lfirst = -1, int lstride = 0) {
   if (c1 - c0 == 1)
     return launch_trsm_strip(e, V + (int64_t)c0 * TILE * ldz, ldz, (int64_t)ntm * TILE,
-                             e->dA + (int64_t)c0 * TILE * (e->ld + 1), e->ld, e->dDinv16 + (int64_t)c0 * 8 * 256,
-                             (int)std::min<int64_t>(TILE, e->N - (int64_t)c0 * TILE), kind_strip);
+                             f.A + (int64_t)c0 * TILE * (f.ld + 1), f.ld, f.dinv16 + (int64_t)c0 * 8 * 256,
+                             (int)std::min<int64_t>(TILE, f.N - (int64_t)c0 * TILE), kind_strip);
   const int mid = c0 + (c1 - c0 + 1) / 2;
-  int rc = trsm_cols(e, V, ldz, ntm, c0, mid, kind_gemm, kind_strip, lfirst, lstride);
+  int rc = trsm_cols(e, f, V, ldz, ntm, c0, mid, kind_gemm, kind_strip, lfirst, lstride);
   if (rc) return rc;
   GemmArgs g{};
   g.C = V + (int64_t)mid * TILE * ldz;
   g.ldc = ldz;
-  g.A = e->dA + (int64_t)mid * TILE + (int64_t)c0 * TILE * e->ld;
-  g.lda = e->ld;
+  g.A = f.A + (int64_t)mid * TILE + (int64_t)c0 * TILE * f.ld;
+  g.lda = f.ld;
   g.B = V + (int64_t)c0 * TILE * ldz;
   g.ldb = ldz;
   g.mt = c1 - mid;
@@ -1417,7 +1450,7 @@ int trsm_cols(gmb_engine* e, double* V, int64_t ldz, int ntm, int c0, int c1, in
   }
   rc = launch_gemm(e, g, kind_gemm);
   if (rc) return rc;
-  return trsm_cols(e, V, ldz, ntm, mid, c1, kind_gemm, kind_strip, lfirst, lstride);
+  return trsm_cols(e, f, V, ldz, ntm, mid, c1, kind_gemm, kind_strip, lfirst, lstride);
 }
 
 // ---- NLML gradient ---------------------------------------------------------------------------
@@ -1561,8 +1594,8 @@ int winv_node(gmb_engine* e, int c0, int c1, bool recurse) {
   GemmArgs gt, gw;
   TransposeJob tr;
   winv_node_products(e, c0, c1, gt, gw, tr);
-  if ((rc = launch_gemm(e, gt, 4))) return rc;
-  if ((rc = launch_gemm(e, gw, 4))) return rc;
+  if ((rc = launch_gemm(e, gt, EV_GRAD_GEMM))) return rc;
+  if ((rc = launch_gemm(e, gw, EV_GRAD_GEMM))) return rc;
   return launch_transpose(e, tr.src, e->Np, tr.dst, e->ld, tr.rows, tr.cols);
 }
 
@@ -1650,7 +1683,7 @@ int winv_level_batched(gmb_engine* e, const gmb_engine::InvLevelPlan& lp) {
     if (lp.grid_x[b] <= 0) continue;
     const GemmArgs* batch = e->dplan_gemm + lp.off[b];
     const dim3 grid(lp.grid_x[b], lp.count);
-    ev_begin(e, 4, lp.flops[b], lp.count, 0, 0, (lp.variant[b] << 8) | 64);
+    ev_begin(e, EV_GRAD_GEMM, lp.flops[b], lp.count, 0, 0, (lp.variant[b] << 8) | 64);
     switch (lp.variant[b]) {
       case 0: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, e->cur, batch); break;
       case 1: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 2, 2, 2>), grid, dim3(256), 0, e->cur, batch); break;
@@ -1733,7 +1766,7 @@ int grad_sigma_inv_rows(gmb_engine* e, int shard, int nshards, double* Z, int64_
   g.cblk_stride = packed ? 1 : 0;
   g.alpha = 1.0;
   g.beta = 0.0;
-  return launch_gemm(e, g, 4);
+  return launch_gemm(e, g, EV_GRAD_GEMM);
 }
 
 int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t ldz, bool packed,
@@ -1892,7 +1925,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
     EvalLandArgs la{};
     la.scal = e->dscal;
     la.info = e->dinfo;
-    la.abort = e->ct_used ? e->dct + 1 : nullptr;
+    la.abort = e->chol.tiles ? e->dct + 1 : nullptr;
     la.gacc = e->dgpart;
     la.nterms = (int)e->terms.size();
     la.region = GACC_REGION;
@@ -2347,7 +2380,6 @@ void gmb_destroy(gmb_engine* e) {
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
                   e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
                   e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage};
-  if (e->cap_A == 0) ptrs[11] = nullptr;  // (e->dA may be a virtual base of the capacity driver: nothing of ours to free)
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int a = 0; a < 3; ++a)
@@ -2584,11 +2616,6 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
     const int nct = (int)(e->Np / TILE);
     e->panel_blocks = std::max(8, ((nct / 16 + 4) / 8) * 8);
   }
-  const int nblocks = (int)(e->Np / TILE);
-  const bool tiles = !e->naive_leaf && (e->chol_scheme == 3 || (e->chol_scheme < 0 && nblocks >= e->tiles_min_blocks &&
-                                                                 nblocks <= e->tiles_max_blocks));
-  const bool masked = !tiles && e->lookahead && e->aux_shared && e->Np / TILE > e->panel_blocks &&
-                      (e->chol_scheme == 2 || (e->chol_scheme < 0 && e->Np / TILE <= e->masked_max_blocks));
   // the fused evaluation launch pays at every size (per evaluation, stream schedules -> fused: N = 100: 0.21 -> 0.14 ms, N = 392:
   // 0.44 -> 0.27, N = 1000: 0.76 -> 0.45; tools/gpu_small_eval.py), the tile Cholesky on its own only from six block columns
   const bool fused = with_grad && eval_will_fuse(e);
@@ -2608,9 +2635,7 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   if (events) HIP_TRY(e, hipEventRecord(e->fe[1], e->stream));
   // 2. Cholesky
   if (events) HIP_TRY(e, hipEventRecord(e->fe[2], e->stream));
-  e->chol_update_kind = 7;
-  e->ct_used = false;
-  e->ct_traced = false;
+  e->chol = CholResult{};
   e->cur = e->stream;
   e->et_fused = false;
   if (fused) {
@@ -2619,21 +2644,12 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
     if ((rc = eval_tiles(e, true))) return rc;
     e->et_fused = true;
   } else {
-    e->ct_panels = false;
-    if (tiles) {
-      rc = chol_tiles(e);
-    } else if (masked) {
-      rc = chol_lookahead_masked(e);
-    } else {
-      // the plain recursion; its bottom panels as launches of the tile kernel (chol_tiles_panel)
-      e->panel_tiles_on = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
-      if (e->panel_tiles_on) {
-        if ((rc = ensure(e, &e->dct, &e->cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * (e->Nr / TILE)))) return rc;
-        HIP_TRY(e, hipMemsetAsync(e->dct, 0, 4 * sizeof(uint32_t), e->stream));  // (the abort word: once per factorisation)
-      }
-      rc = chol_cols(e, 0, nblocks, (int)(e->Nr / TILE));
-      e->panel_tiles_on = false;
-    }
+    CholOpts o;
+    o.masked_ok = true;
+    o.trace = e->ct_trace;
+    o.lose = e->ct_lose;
+    rc = chol_factor(e, train_factor(e), o, &e->chol);
+    if (e->chol.injected) e->ct_lose = 0;  // (one shot)
     if (rc) return rc;
     // 3. v = L^-1 y is row N of the factor
     hipLaunchKernelGGL(extract_v_kernel, dim3(EXTRACT_V_BLOCKS), dim3(TILE), 0, e->stream, e->dA, e->ld, e->N, e->dv,
@@ -2650,7 +2666,7 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   if (!e->light) {
     HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (e->ct_used) HIP_TRY(e, hipMemcpyAsync(&e->hl->abort, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (e->chol.tiles) HIP_TRY(e, hipMemcpyAsync(&e->hl->abort, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   }
   e->fact_in_flight = true;
   return GMB_OK;
@@ -2699,7 +2715,7 @@ int factorize_finish(gmb_engine* e) {
 // for seconds) says nothing about the matrix: factor it once more with the plain recursion before reporting an error.
 // Injected faults (gmb_debug_chol_lose_tickets) are reported as they are -- the tests want to see the bounded wait.
 static int factorize_retry_after_abort(gmb_engine* e, int rc) {
-  if (rc != GMB_EHIP || !e->ct_used || !e->hl || e->hl->abort == 0 || e->ct_injected) return rc;
+  if (rc != GMB_EHIP || !e->chol.tiles || !e->hl || e->hl->abort == 0 || e->chol.injected) return rc;
   fprintf(stderr, "libgumbi_hip: tile Cholesky abandoned after a time-out; refactorising with the plain recursion\n");
   const int scheme = e->chol_scheme;
   e->chol_scheme = 0;  // (scheme 0 = launches only: no tile kernel anywhere, the recursion's bottom panels included)
@@ -2918,9 +2934,9 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
     g.alpha = 1.0;
     g.beta = 0.0;
     g.khi_n = 1;
-    if ((rc = launch_gemm(e, g, 3))) return rc;
-  } else if ((rc = tiles ? trsm_tiles(e, e->dV, mpad, (int)(mpad / TILE), 3)
-                         : trsm_cols(e, e->dV, mpad, (int)(mpad / TILE), 0, nblocks, 3, 6)))
+    if ((rc = launch_gemm(e, g, EV_PREDICT_GEMM))) return rc;
+  } else if ((rc = tiles ? trsm_tiles(e, train_factor(e), e->dV, mpad, (int)(mpad / TILE), EV_PREDICT_GEMM)
+                         : trsm_cols(e, train_factor(e), e->dV, mpad, (int)(mpad / TILE), 0, nblocks, EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
     return rc;
   if (e->tt_used) {  // a launch that gave up waiting must not be mistaken for a prediction
     uint32_t ab = 0;
@@ -2956,44 +2972,8 @@ int predict_reduce(gmb_engine* e, int64_t mc, int64_t mpad, bool gemm_form) {
 
 // ---- the joint posterior (joint_predict.hpp): full covariance and correlated draws ----------------------------------------------
 
-// While C is factored its matrix, sub-block inverses, scalar block, info word and control block stand in for the training
-// factor's: the Cholesky's host routines (chol_tiles, chol_cols, chol_tiles_panel, chol_leaf) read them from the engine.
-// Everything is put back on every way out, so the training factorisation -- factor, log-determinant, flags -- survives.
-struct JointScope {
-  gmb_engine* e;
-  int64_t N, Np, Nr, ld, cap_A, cap_dinv16, cap_ct;
-  double *dA, *dDinv16, *dscal;
-  int32_t* dinfo;
-  uint32_t* dct;
-  bool ct_used, ct_panels, ct_traced, ct_trace, ct_injected, panel_tiles_on;
-  int ct_ntasks, ct_lose, chol_update_kind;
-  explicit JointScope(gmb_engine* e_)
-      : e(e_), N(e_->N), Np(e_->Np), Nr(e_->Nr), ld(e_->ld), cap_A(e_->cap_A), cap_dinv16(e_->cap_dinv16), cap_ct(e_->cap_ct),
-        dA(e_->dA), dDinv16(e_->dDinv16), dscal(e_->dscal), dinfo(e_->dinfo), dct(e_->dct), ct_used(e_->ct_used),
-        ct_panels(e_->ct_panels), ct_traced(e_->ct_traced), ct_trace(e_->ct_trace), ct_injected(e_->ct_injected),
-        panel_tiles_on(e_->panel_tiles_on), ct_ntasks(e_->ct_ntasks), ct_lose(e_->ct_lose), chol_update_kind(e_->chol_update_kind) {
-    const JointState& jt = e->jt;
-    e->N = jt.M, e->Np = jt.Mp, e->Nr = e->ld = jt.Mr;
-    e->dA = jt.dC, e->cap_A = jt.cap_C;
-    e->dDinv16 = jt.dDinv16, e->cap_dinv16 = jt.cap_dinv16;
-    e->dscal = jt.dscal, e->dinfo = reinterpret_cast<int32_t*>(jt.dscal + SCAL_INFO_AT);
-    e->dct = jt.dct, e->cap_ct = jt.cap_ct;
-    e->ct_used = e->ct_panels = e->ct_traced = e->ct_trace = e->ct_injected = e->panel_tiles_on = false;
-    e->ct_lose = 0;
-    e->chol_update_kind = 7;
-  }
-  ~JointScope() {
-    e->jt.dct = e->dct, e->jt.cap_ct = e->cap_ct;  // (the launches size the control block themselves)
-    e->N = N, e->Np = Np, e->Nr = Nr, e->ld = ld;
-    e->dA = dA, e->cap_A = cap_A;
-    e->dDinv16 = dDinv16, e->cap_dinv16 = cap_dinv16;
-    e->dscal = dscal, e->dinfo = dinfo;
-    e->dct = dct, e->cap_ct = cap_ct;
-    e->ct_used = ct_used, e->ct_panels = ct_panels, e->ct_traced = ct_traced, e->ct_trace = ct_trace, e->ct_injected = ct_injected;
-    e->panel_tiles_on = panel_tiles_on;
-    e->ct_ntasks = ct_ntasks, e->ct_lose = ct_lose, e->chol_update_kind = chol_update_kind;
-  }
-};
+// C as the Cholesky's routines take it (buffers and capacities stay JointState's)
+FactorRef joint_factor_ref(JointState& jt) { return FactorRef{jt.dC, jt.Mr, jt.M, jt.Mp, jt.Mr, jt.dDinv16, jt.dscal, &jt.dct, &jt.cap_ct}; }
 
 // what both calls ask of the engine: a complete single-engine factor on this device
 int joint_ready(gmb_engine* e, const char* what) {
@@ -3110,38 +3090,25 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   g.beta = 1.0;
   g.tri = 1;
   e->cur = e->stream;
-  return launch_gemm(e, g, 3);
+  return launch_gemm(e, g, EV_PREDICT_GEMM);
 }
 
-// C -> L* in place, by the schedule gmb_factorize would give a matrix of this size (the persistent tile kernel from six block
-// columns on, the recursion with tile-kernel panels otherwise).  Synchronises; an abandoned tile launch is an error.
+// C -> L* in place, by the schedule gmb_factorize would give a matrix of this size (chol_factor: the persistent tile kernel from
+// six block columns on, the recursion with tile-kernel panels otherwise; never the masked look-ahead, untraced, no injected
+// faults).  The factorisation is told its matrix, so nothing of the training factorisation is read or written.  Synchronises;
+// an abandoned tile launch is an error.
 int joint_factor(gmb_engine* e) {
   JointState& jt = e->jt;
   HIP_TRY(e, hipMemsetAsync(jt.dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), e->stream));
+  const FactorRef f = joint_factor_ref(jt);
+  CholResult res;
+  int rc = chol_factor(e, f, CholOpts{}, &res);
+  if (rc) return rc;
   int32_t info = 0;
   uint32_t ab = 0;
-  {
-    JointScope scope(e);
-    int rc;
-    const int nblocks = (int)(e->Np / TILE);
-    const bool tiles = !e->naive_leaf && (e->chol_scheme == 3 || (e->chol_scheme < 0 && nblocks >= e->tiles_min_blocks &&
-                                                                   nblocks <= e->tiles_max_blocks));
-    e->cur = e->stream;
-    if (tiles) {
-      rc = chol_tiles(e);
-    } else {
-      e->panel_tiles_on = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
-      if (e->panel_tiles_on) {
-        if ((rc = ensure(e, &e->dct, &e->cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * (e->Nr / TILE)))) return rc;
-        HIP_TRY(e, hipMemsetAsync(e->dct, 0, 4 * sizeof(uint32_t), e->stream));
-      }
-      rc = chol_cols(e, 0, nblocks, (int)(e->Nr / TILE));
-    }
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(&info, e->dinfo, sizeof info, hipMemcpyDeviceToHost, e->stream));
-    if (e->ct_used) HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof ab, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-  }
+  HIP_TRY(e, hipMemcpyAsync(&info, f.info(), sizeof info, hipMemcpyDeviceToHost, e->stream));
+  if (res.tiles) HIP_TRY(e, hipMemcpyAsync(&ab, jt.dct + 1, sizeof ab, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (ab != 0)
     return fail(e, GMB_EHIP, "joint posterior: the tile Cholesky of the predictive covariance waited longer than its time-out for a tile (launch abandoned)");
   if (info != 0) {
@@ -3533,7 +3500,7 @@ int64_t gmb_chol_task_trace(gmb_engine* e, int32_t enable, uint64_t* out, int64_
   if (!e) return GMB_EINVAL;
   if (enable >= 0) e->ct_trace = enable != 0;
   // only the stamps of the LAST factorisation count: 0 when it did not run on the tile kernel or ran untraced
-  const int64_t n = (e->ct_used && e->ct_traced && e->dct_trace && e->cap_ct_trace >= 4 * (int64_t)e->ct_ntasks) ? e->ct_ntasks : 0;
+  const int64_t n = (e->chol.tiles && e->chol.traced && e->dct_trace && e->cap_ct_trace >= 4 * (int64_t)e->chol.ntasks) ? e->chol.ntasks : 0;
   if (out && n > 0) {
     HIP_TRY(e, hipSetDevice(e->device));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -3673,7 +3640,7 @@ int gmb_blk_trsm(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, const dou
       nvalid > TILE)
     return fail(e, GMB_EINVAL, "bad trsm arguments (rows must be a multiple of 16)");
   HIP_TRY(e, hipSetDevice(e->device));
-  return launch_trsm_strip(e, B, ldb, nrows, Lkk, ldl, dinv16, nvalid, 5);
+  return launch_trsm_strip(e, B, ldb, nrows, Lkk, ldl, dinv16, nvalid, EV_CHOL_STRIP);
 }
 
 int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int64_t lda, const double* B,
@@ -3697,7 +3664,7 @@ int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int6
   g.beta = beta;
   g.tri = tri;
   g.tri_off = (int)(tri_shift * TILE);
-  return launch_gemm(e, g, 0);
+  return launch_gemm(e, g, EV_CHOL_PANEL_GEMM);
 }
 
 }  // extern "C"
@@ -3723,11 +3690,11 @@ int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
     if (e->dA && e->cap_A > 0) {
       if (hipSetDevice(e->device) == hipSuccess) (void)hipStreamSynchronize(e->stream);
       release(e, e->dA);
+      e->dA = nullptr;
+      e->cap_A = 0;
       e->factored = false;
       e->factor_kind = gmb_engine::FK_NONE;
     }
-    e->dA = nullptr;
-    e->cap_A = 0;
   }
   return old;
 }

@@ -22,10 +22,10 @@
 
 namespace gmb {
 
-// Everything the factorisation of C owns.  The host routines of the Cholesky (chol_tiles, chol_cols, ...) read the matrix, its
-// 16 x 16 diagonal inverses, the scalar block, the info word and the tile kernel's control block from the engine; while C is
-// factored these stand in for the training factor's (engine.hip: JointScope), so nothing of the training factorisation -- its
-// factor, log-determinant, failure index, control words -- is written by a draw.
+// Everything the factorisation of C owns.  The host routines of the Cholesky (chol_factor, chol_tiles, chol_cols, ...) are told
+// the matrix they work on -- its 16 x 16 diagonal inverses, scalar block, info word and tile-kernel control block with it
+// (engine.hip: FactorRef, joint_factor_ref) -- so nothing of the training factorisation -- its factor, log-determinant, failure
+// index, control words -- is written by a draw.
 struct JointState {
   int64_t M = 0, Mp = 0, Mr = 0;  // test points; padded to 128; rows of the bordered layout the Cholesky kernels expect ((M + 1) up)
   double* dC = nullptr;           // Mr x Mp column-major, leading dimension Mr: lower-triangle tiles of C, then of L*
