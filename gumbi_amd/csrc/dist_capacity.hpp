@@ -136,7 +136,6 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   hipStream_t mainS = e->stream, bulkS = e->aux[2], commS = e->aux[0];
   e->sync_next = 0;
   e->time_next = 0;
-  e->cur = mainS;
   DistDeferred bad;
   DistProbe probe;
   bool tail_in_flight = false;  // a TAIL has been issued on the communication stream since the last FORK
@@ -203,8 +202,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
       case DIST_SQUARE: {  // the diagonal square's block rows from their owners, then every rank factors it
         gathered = true;
         if ((rc = cap_gather_panel(e, comm, mainS, panel, s.c0, s.c1, s.lo, s.hi, true, &probe, e->dsend2, e->drecv2))) break;
-        e->cur = mainS;
-        rc = chol_cols(e, cap_window(e, panel, s.c0), s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);
+        rc = chol_cols(e, mainS, cap_window(e, panel, s.c0), s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);
         // the owners' copies of the square's rows become L too (they are read again when L is streamed)
         int f, c;
         dist_owned(rank, G, s.lo, s.hi, &f, &c);
@@ -218,8 +216,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
       case DIST_SOLVE: {  // my rows below the square: solved in place in dAown, and copied into the panel buffer (U1 reads them there
                           // before the TAIL has delivered everybody's)
         if (s.count <= 0) break;
-        e->cur = mainS;
-        if ((rc = trsm_cols(e, cap_window(e, panel, s.c0), e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE, e->ld_own, s.count, s.c0, s.c1,
+        if ((rc = trsm_cols(e, mainS, cap_window(e, panel, s.c0), e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE, e->ld_own, s.count, s.c0, s.c1,
                             EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP)))
           break;
         rc = dist_pack(e, mainS, panel, e->ld, e->dAown + (int64_t)cap_packed(s.first, rank, G) * TILE + (int64_t)s.c0 * TILE * e->ld_own, e->ld_own, 0,
@@ -256,9 +253,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         g.tri = 1;
         g.tri_off = (s.first - s.lo) * TILE;
         g.nblk_stride = G;
-        e->cur = s.stream ? bulkS : mainS;
-        rc = launch_gemm(e, g, EV_CHOL_UPDATE);
-        e->cur = mainS;
+        rc = launch_gemm(e, s.stream ? bulkS : mainS, g, EV_CHOL_UPDATE);
         break;
       }
       case DIST_FORK:  // U2 reads the whole panel column: the chain's part (main stream) and the TAIL (communication stream)
@@ -288,7 +283,6 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     }
   }
   bad.note(e, order_after(e, commS, mainS));  // the last TAIL (the y row travels in it)
-  e->cur = mainS;
   double hs[2] = {0.0, 0.0};
   int32_t info = 0;
   if (!bad.rc) {
@@ -410,7 +404,6 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   PhaseTimer tg(e);
   e->sync_next = 0;
   e->time_next = 0;
-  e->cur = mainS;
   DistDeferred bad;
   DistProbe probe;
   auto hip_ok = [&](hipError_t st, const char* what) {
@@ -445,7 +438,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
     dist_owned(rank, G, 0, k1, &f2, &mine);
     const int mc = dist_max_owned(G, 0, k1);
     // 2. this rank's rows of U in these columns
-    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, v, V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
+    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, mainS, v, V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
     if (!bad.rc && k1 == nt && e->Np > e->N && owned > 0) {  // (the last chunk holds the padding columns)
       hipLaunchKernelGGL(cap_reset_pad_cols_kernel, dim3((unsigned)(((int64_t)owned * TILE + 255) / 256)), dim3(256), 0, mainS, V, ldv, e->N, e->Np,
                          first, G, owned);
@@ -475,7 +468,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.klo_n = 1;
       g.krow_stride = G;
       g.krow_off = (first - k0) * TILE;
-      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
+      bad.note(e, launch_gemm(e, mainS, g, EV_GRAD_GEMM));
     }
     // alpha = U v, this chunk's columns (the chunk's columns of V are overwritten below)
     if (!bad.rc && owned > 0) {
@@ -510,7 +503,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.nblk_stride = G;
       g.alpha = 1.0;
       g.beta = 1.0;
-      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
+      bad.note(e, launch_gemm(e, mainS, g, EV_GRAD_GEMM));
     }
   }
   // alpha = U v: this rank's rows (the chunks' parts in chunk order), then everybody's
@@ -569,7 +562,6 @@ int cap_solve(gmb_engine* e, const gmb_comm* comm, double* V, int64_t ldv, int n
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   const int cw = cap_chunk(nct);
   hipStream_t st = e->stream, commS = e->aux[0];
-  e->cur = st;
   // panel c + 1 travels on the communication stream while panel c is solved against and applied (two buffers; the gathers of a
   // pass are issued on that one stream, in panel order, on every rank)
   const int64_t pbuf = e->Nr * (int64_t)cw * TILE;
@@ -585,7 +577,7 @@ int cap_solve(gmb_engine* e, const gmb_comm* comm, double* V, int64_t ldv, int n
     }
     if (bad.rc || ntm <= 0) continue;
     const FactorRef v = cap_window(e, Lbuf[ci & 1], c0);
-    bad.note(e, trsm_cols(e, v, V, ldv, ntm, c0, c1, EV_PREDICT_GEMM, EV_SOLVE_STRIP));
+    bad.note(e, trsm_cols(e, st, v, V, ldv, ntm, c0, c1, EV_PREDICT_GEMM, EV_SOLVE_STRIP));
     if (!bad.rc && c1 < nct) {
       GemmArgs g{};
       g.C = V + (int64_t)c1 * TILE * ldv;
@@ -599,7 +591,7 @@ int cap_solve(gmb_engine* e, const gmb_comm* comm, double* V, int64_t ldv, int n
       g.k = (c1 - c0) * TILE;
       g.alpha = -1.0;
       g.beta = 1.0;
-      bad.note(e, launch_gemm(e, g, EV_PREDICT_GEMM));
+      bad.note(e, launch_gemm(e, st, g, EV_PREDICT_GEMM));
     }
   }
   bad.note(e, order_after(e, commS, st));  // (nothing of this pass is left on the other stream when the caller goes on)

@@ -368,7 +368,6 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   hipStream_t mainS = e->stream, bulkS = e->aux[2], commS = e->aux[0];
   e->sync_next = 0;
   e->time_next = 0;
-  e->cur = mainS;
   const FactorRef F = train_factor(e);
   DistDeferred bad;
   DistProbe probe;
@@ -423,8 +422,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         gathered = true;
         if ((rc = dist_all_gather(e, comm, mainS, e->dsend, e->drecv, s.elems, &probe))) break;
         if ((rc = dist_pack(e, mainS, cols, e->ld, e->drecv, ldp, s.elems, (int)W, false, G, 0, 0, G, s.lo, s.hi, s.maxcount))) break;
-        e->cur = mainS;
-        rc = chol_cols(e, F, s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);  // the square only (rows below are PANEL's): in-panel products
+        rc = chol_cols(e, mainS, F, s.c0, s.c1, s.c1, EV_CHOL_PANEL_GEMM);  // the square only (rows below are PANEL's): in-panel products
         break;
       }
       case DIST_SOLVE: {  // my rows below the square, solved in the packed staging buffer and put back: no communication
@@ -432,8 +430,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         const int64_t ldp = (int64_t)s.maxcount * TILE;
         if (s.count <= 0) break;
         if ((rc = dist_pack(e, mainS, cols, e->ld, e->dsend, ldp, 0, (int)W, true, 0, s.first, s.count, G, 0, 0, s.maxcount))) break;
-        e->cur = mainS;
-        if ((rc = trsm_cols(e, F, e->dsend - (int64_t)s.c0 * TILE * ldp, ldp, s.count, s.c0, s.c1, EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP))) break;
+        if ((rc = trsm_cols(e, mainS, F, e->dsend - (int64_t)s.c0 * TILE * ldp, ldp, s.count, s.c0, s.c1, EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP))) break;
         rc = dist_pack(e, mainS, cols, e->ld, e->dsend, ldp, 0, (int)W, false, 0, s.first, s.count, G, 0, 0, s.maxcount);
         break;
       }
@@ -471,9 +468,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         g.tri = 1;
         g.tri_off = (s.first - s.lo) * TILE;
         g.nblk_stride = G;
-        e->cur = s.stream ? bulkS : mainS;
-        rc = launch_gemm(e, g, EV_CHOL_UPDATE);
-        e->cur = mainS;
+        rc = launch_gemm(e, s.stream ? bulkS : mainS, g, EV_CHOL_UPDATE);
         break;
       }
       case DIST_FORK:  // U2 reads the whole panel column: the chain's part (main stream) and the TAIL (communication stream)
@@ -499,7 +494,6 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     }
   }
   bad.note(e, order_after(e, commS, mainS));  // the last TAIL (the y row travels in it)
-  e->cur = mainS;
   // v = L^-1 y is row N of the (now complete, replicated) factor
   double hs[2] = {0.0, 0.0};
   int32_t info = 0;
@@ -608,7 +602,6 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   PhaseTimer tg(e);
   e->sync_next = 0;
   e->time_next = 0;
-  e->cur = mainS;
   e->factor_consumed = true;  // the upper triangle (and the diagonal squares) of the factor buffer become U
   DistDeferred bad;
   DistProbe probe;
@@ -627,7 +620,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
     int f2, mine;
     dist_owned(rank, G, 0, k1, &f2, &mine);
     const int mc = dist_max_owned(G, 0, k1);
-    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, train_factor(e), V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
+    if (!bad.rc && mine > 0) bad.note(e, trsm_cols(e, mainS, train_factor(e), V, ldv, mine, k0, k1, EV_GRAD_GEMM, EV_SOLVE_STRIP, first, G));
     bad.note(e, order_after(e, mainS, commS));  // the chunk is final
     if (!bad.rc && mine > 0 && k1 < nt) {  // right-looking: V[:, k1:] -= V[:, k0:k1] L[k1:, k0:k1]^T, structural zeros skipped
       GemmArgs g{};
@@ -645,7 +638,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
       g.klo_n = 1;
       g.krow_stride = G;
       g.krow_off = (first - k0) * TILE;
-      bad.note(e, launch_gemm(e, g, EV_GRAD_GEMM));
+      bad.note(e, launch_gemm(e, mainS, g, EV_GRAD_GEMM));
     }
     // ship the finished chunk while the update above runs (it only READS the chunk, and the unpack writes
     // rows < k1 of the factor buffer's chunk columns, the update reads rows >= k1 of them): rows b < k1 of
@@ -676,7 +669,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   }
   // this rank's block rows of Sigma^-1 = U U^T, packed, into the buffer V occupied; reductions over them
   std::vector<double> h;
-  if (!bad.rc) bad.note(e, grad_sigma_inv_rows(e, rank, G, e->dW, ldv, true));
+  if (!bad.rc) bad.note(e, grad_sigma_inv_rows(e, mainS, rank, G, e->dW, ldv, true));
   if (!bad.rc) bad.note(e, grad_reduce(e, rank, G, e->dW, ldv, true, h));
   // accumulators of all ranks, summed in rank order on every rank (bit-identical results everywhere)
   if (!bad.rc) hip_ok(hipMemcpyAsync(e->dsend, e->dgpart, GACC_DOUBLES * sizeof(double), hipMemcpyDeviceToDevice, mainS), "hipMemcpyAsync");

@@ -67,6 +67,7 @@ enum EvKind : int {
 
 struct EventPair {
   hipEvent_t a, b;
+  hipStream_t s;  // the stream the pair was opened on: ev_end closes it there
   EvKind kind;
   double flops;
   int mt, nt, k, flags;
@@ -229,10 +230,9 @@ struct gmb_engine {
   long long wg_slots = 512;  // resident GEMM workgroups: two per compute unit
   bool force_variant = false;  // tuning: GMB_GEMM_VARIANT pins the tile shape of every out-of-place GEMM
 
-  // concurrency inside one factorisation / gradient: `cur` is the stream the launch helpers use;
-  // it is `stream` except inside the look-ahead Cholesky (panel chain on aux[0]) and the
-  // level-parallel triangular inverse (independent merges dealt over stream + aux[0..2])
-  hipStream_t cur = nullptr;
+  // concurrency inside one factorisation / gradient: the launch helpers take their stream as an argument; the orchestrators
+  // pass `stream`, except the look-ahead Cholesky (bulk updates on aux[2]) and the level-parallel triangular inverse
+  // (independent merges dealt over stream + aux[0..2])
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};
   // -1 = by size; 0 = plain recursion; 2 = masked look-ahead; 3 = persistent tile kernel (chol_tiles.hpp)
   int chol_scheme = -1;
@@ -243,7 +243,6 @@ struct gmb_engine {
   int64_t cap_ct_trace = 0;
   bool ct_trace = false;
   CholResult chol;           // what the tile kernel did in the last TRAINING factorisation
-  bool tt_used = false;      // the current prediction ran its triangular solve on the tile kernel (same abort word)
   int ct_lose = 0;           // fault injection (gmb_debug_chol_lose_tickets): one shot
   bool fact_in_flight = false;  // factorize_enqueue has run, factorize_finish has not
   // a factorisation that has been enqueued but not checked yet (factorize_enqueue / factorize_finish): where its scalars
@@ -430,7 +429,7 @@ struct PhaseTimer {
   }
 };
 
-void ev_begin(gmb_engine* e, EvKind kind, double flops, int mt = 0, int nt = 0, int k = 0, int flags = 0) {
+void ev_begin(gmb_engine* e, hipStream_t s, EvKind kind, double flops, int mt = 0, int nt = 0, int k = 0, int flags = 0) {
   if (!e->profiling) return;
   EventPair p;
   p.mt = mt;
@@ -441,13 +440,14 @@ void ev_begin(gmb_engine* e, EvKind kind, double flops, int mt = 0, int nt = 0, 
   (void)hipEventCreate(&p.b);
   p.kind = kind;
   p.flops = flops;
-  p.masked = e->aux_shared && e->cur == e->aux[2];
-  (void)hipEventRecord(p.a, e->cur);
+  p.s = s;
+  p.masked = e->aux_shared && s == e->aux[2];
+  (void)hipEventRecord(p.a, s);
   e->evs.push_back(p);
 }
 void ev_end(gmb_engine* e) {
   if (!e->profiling) return;
-  (void)hipEventRecord(e->evs.back().b, e->cur);
+  (void)hipEventRecord(e->evs.back().b, e->evs.back().s);
 }
 void ev_collect(gmb_engine* e) {  // stream already synchronised
   static FILE* trace = nullptr;
@@ -581,17 +581,12 @@ long long gemm_nact128(const GemmArgs& g) {
   return nact;
 }
 
-int launch_gemm(gmb_engine* e, const GemmArgs& g_in, EvKind ev_kind) {
+int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_kind) {
   if (g_in.mt <= 0 || g_in.nt <= 0 || g_in.k <= 0) return GMB_OK;
   GemmArgs g = g_in;
   // tiles the 128 x 128 tiling would compute
   if (g.nblk_stride < 1) g.nblk_stride = 1;
-  long long nact = 0;
-  for (int tm = 0; tm < g.mt; ++tm) {
-    int f = g.tri ? gemm_first_tn((int64_t)tm * TILE - g.tri_off - (TILE - 1), TILE, g.nblk_stride) : 0;
-    f = f > g.nt ? g.nt : f;
-    nact += g.nt - f;
-  }
+  const long long nact = gemm_nact128(g);
   const bool in_place = (const double*)g.C == g.B;  // the block must own every column of its rows
   // variant: 0 = 128x128, 1 = 64x64, 2 = 128x64, 3 = 128x32 (all 4 waves, two workgroups per compute unit)
   int variant = e->gemm_variant;
@@ -652,31 +647,31 @@ int launch_gemm(gmb_engine* e, const GemmArgs& g_in, EvKind ev_kind) {
   const bool bulk_update = ev_kind == EV_CHOL_UPDATE && variant == 0 && !in_place;
   const int was_update = ev_kind == EV_CHOL_UPDATE ? (1 << 16) : 0;  // issued AS a trailing update, whatever tile shape it runs (total_chol_update_all_*)
   if (ev_kind == EV_CHOL_UPDATE && !bulk_update) ev_kind = EV_CHOL_PANEL_GEMM;
-  ev_begin(e, ev_kind, flops, g_in.mt, g_in.nt, g.k,
+  ev_begin(e, s, ev_kind, flops, g_in.mt, g_in.nt, g.k,
            g.tri | (g.klo_n << 3) | (g.khi_n << 4) | (g.klo_m << 5) | (variant << 8) | was_update);
   const dim3 grid(nblocks);
   const bool pfc = g.beta != 0.0 && g.k <= 1024 && !in_place;
   switch (variant) {
     case 0:
-      if (e->gemm_dma && bulk_update) hipLaunchKernelGGL(gemm_f64_dma_chol_update_kernel, grid, dim3(256), 0, e->cur, g);
-      else if (e->gemm_dma && !in_place) hipLaunchKernelGGL(gemm_f64_dma_kernel, grid, dim3(256), 0, e->cur, g);
-      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, e->cur, g);
+      if (e->gemm_dma && bulk_update) hipLaunchKernelGGL(gemm_f64_dma_chol_update_kernel, grid, dim3(256), 0, s, g);
+      else if (e->gemm_dma && !in_place) hipLaunchKernelGGL(gemm_f64_dma_kernel, grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, s, g);
       break;
 #ifdef GMB_TUNING
-    case 4: hipLaunchKernelGGL((gemm_f64_kernel<4, 2, 4, 4, 1>), grid, dim3(512), 0, e->cur, g); break;
+    case 4: hipLaunchKernelGGL((gemm_f64_kernel<4, 2, 4, 4, 1>), grid, dim3(512), 0, s, g); break;
 #endif
     // small tiles with a short contraction and beta != 0: the C-prefetching instantiations (gemm_f64.hpp)
     case 1:
-      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 2, 2, 2, true>), grid, dim3(256), 0, e->cur, g);
-      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 2, 2, 2>), grid, dim3(256), 0, e->cur, g);
+      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 2, 2, 2, true>), grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 2, 2, 2>), grid, dim3(256), 0, s, g);
       break;
     case 2:
-      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 2, 2, true>), grid, dim3(256), 0, e->cur, g);
-      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 2, 2>), grid, dim3(256), 0, e->cur, g);
+      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 2, 2, true>), grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 2, 2>), grid, dim3(256), 0, s, g);
       break;
     default:
-      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 1, 2, true>), grid, dim3(256), 0, e->cur, g);
-      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 1, 2>), grid, dim3(256), 0, e->cur, g);
+      if (pfc) hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 1, 2, true>), grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 1, 2>), grid, dim3(256), 0, s, g);
       break;
   }
   ev_end(e);
@@ -685,7 +680,7 @@ int launch_gemm(gmb_engine* e, const GemmArgs& g_in, EvKind ev_kind) {
 }
 
 // B <- B inv(L_kk)^T on `nrows` rows (multiple of 16): one wavefront per 16 rows
-int launch_trsm_strip(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, const double* L, int64_t ldl,
+int launch_trsm_strip(gmb_engine* e, hipStream_t s, double* B, int64_t ldb, int64_t nrows, const double* L, int64_t ldl,
                       const double* dinv16, int nvalid, EvKind ev_kind) {
   if (nrows <= 0) return GMB_OK;
   TrsmArgs t;
@@ -696,19 +691,19 @@ int launch_trsm_strip(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, cons
   t.ldl = ldl;
   t.dinv16 = dinv16;
   t.nvalid = nvalid;
-  ev_begin(e, ev_kind, (double)nrows * TILE * TILE);
-  hipLaunchKernelGGL(trsm_strip_kernel, dim3((unsigned)((nrows / 16 + 3) / 4)), dim3(256), 0, e->cur, t);
+  ev_begin(e, s, ev_kind, (double)nrows * TILE * TILE);
+  hipLaunchKernelGGL(trsm_strip_kernel, dim3((unsigned)((nrows / 16 + 3) / 4)), dim3(256), 0, s, t);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
 
-int launch_leaf(gmb_engine* e, const LeafArgs& a) {
-  ev_begin(e, EV_LEAF, 0.0);
+int launch_leaf(gmb_engine* e, hipStream_t s, const LeafArgs& a) {
+  ev_begin(e, s, EV_LEAF, 0.0);
   if (e->naive_leaf)
-    hipLaunchKernelGGL(potrf_leaf_naive_kernel, dim3(1), dim3(256), 0, e->cur, a);
+    hipLaunchKernelGGL(potrf_leaf_naive_kernel, dim3(1), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL(potrf_leaf_kernel, dim3(1), dim3(512), 0, e->cur, a);
+    hipLaunchKernelGGL(potrf_leaf_kernel, dim3(1), dim3(512), 0, s, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
@@ -1024,7 +1019,7 @@ int build_sigma(gmb_engine* e, double* out, int64_t ldo) {
 // ---- Cholesky recursion -------------------------------------------------------------------
 // `rend`: block row where the panel solve / updates stop (the whole matrix, or the end of a
 // diagonal square when the rows below are solved later in bulk)
-int chol_leaf(gmb_engine* e, const FactorRef& f, int c, int rend) {
+int chol_leaf(gmb_engine* e, hipStream_t s, const FactorRef& f, int c, int rend) {
   LeafArgs a{};
   a.A = f.A + (int64_t)c * TILE + (int64_t)c * TILE * f.ld;
   a.lda = f.ld;
@@ -1034,23 +1029,23 @@ int chol_leaf(gmb_engine* e, const FactorRef& f, int c, int rend) {
   a.info = f.info();
   a.row0 = (int64_t)c * TILE;
   a.dbg = nullptr;
-  int rc = launch_leaf(e, a);
+  int rc = launch_leaf(e, s, a);
   if (rc) return rc;
   // panel rows below the diagonal block:  P <- P inv(L_cc)^T   (in place, 16 rows per wavefront)
-  return launch_trsm_strip(e, f.A + (int64_t)(c + 1) * TILE + (int64_t)c * TILE * f.ld, f.ld,
+  return launch_trsm_strip(e, s, f.A + (int64_t)(c + 1) * TILE + (int64_t)c * TILE * f.ld, f.ld,
                            (int64_t)(rend - c - 1) * TILE, a.A, f.ld, a.dinv16, a.nvalid, EV_CHOL_STRIP);
 }
 
-int chol_tiles_panel(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, CholResult* res);
+int chol_tiles_panel(gmb_engine* e, hipStream_t s, const FactorRef& f, int c0, int c1, int rend, CholResult* res);
 
 // `update_kind`: what the trailing updates are timed as -- EV_CHOL_UPDATE (bulk) for the plain recursion over the whole matrix,
 // EV_CHOL_PANEL_GEMM (in-panel product of the latency-bound chain) inside the look-ahead schedules' panels.  `tile_panels`, if
 // given: panels of <= panel_tiles_w block columns go to the tile kernel (chol_tiles_panel), which reports there.
-int chol_cols(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, EvKind update_kind, CholResult* tile_panels = nullptr) {
-  if (c1 - c0 == 1) return chol_leaf(e, f, c0, rend);
-  if (tile_panels && c1 - c0 <= e->panel_tiles_w) return chol_tiles_panel(e, f, c0, c1, rend, tile_panels);
+int chol_cols(gmb_engine* e, hipStream_t s, const FactorRef& f, int c0, int c1, int rend, EvKind update_kind, CholResult* tile_panels = nullptr) {
+  if (c1 - c0 == 1) return chol_leaf(e, s, f, c0, rend);
+  if (tile_panels && c1 - c0 <= e->panel_tiles_w) return chol_tiles_panel(e, s, f, c0, c1, rend, tile_panels);
   const int mid = c0 + (c1 - c0 + 1) / 2;
-  int rc = chol_cols(e, f, c0, mid, rend, update_kind, tile_panels);
+  int rc = chol_cols(e, s, f, c0, mid, rend, update_kind, tile_panels);
   if (rc) return rc;
   GemmArgs g{};
   g.C = f.A + (int64_t)mid * TILE + (int64_t)mid * TILE * f.ld;
@@ -1065,9 +1060,9 @@ int chol_cols(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, EvKin
   g.alpha = -1.0;
   g.beta = 1.0;
   g.tri = 1;
-  rc = launch_gemm(e, g, update_kind);
+  rc = launch_gemm(e, s, g, update_kind);
   if (rc) return rc;
-  return chol_cols(e, f, mid, c1, rend, update_kind, tile_panels);
+  return chol_cols(e, s, f, mid, c1, rend, update_kind, tile_panels);
 }
 
 // The ragged last block of the persistent launches (chol_tiles.hpp: ct_ksum<.., RAG>): the fraction of a tile's contraction that
@@ -1121,35 +1116,35 @@ CholTilesArgs tiles_args(const FactorRef& f, int c0, int nct, int nrt, int ntask
 
 // fault injection (gmb_debug_chol_lose_tickets): tickets 0 .. lose-1 of the launch behind the cleared control block are never
 // handed out
-int tiles_lose_tickets(gmb_engine* e, uint32_t* ctl, int lose) {
+int tiles_lose_tickets(gmb_engine* e, hipStream_t s, uint32_t* ctl, int lose) {
   const uint32_t first = (uint32_t)lose;
-  HIP_TRY(e, hipMemcpyAsync(ctl, &first, sizeof first, hipMemcpyHostToDevice, e->cur));
-  HIP_TRY(e, hipStreamSynchronize(e->cur));  // (`first` lives on this stack frame)
+  HIP_TRY(e, hipMemcpyAsync(ctl, &first, sizeof first, hipMemcpyHostToDevice, s));
+  HIP_TRY(e, hipStreamSynchronize(s));  // (`first` lives on this stack frame)
   return GMB_OK;
 }
 
 // a traced launch stamps its tasks into the engine's trace buffer (gmb_chol_task_trace), cleared here
-int tiles_trace_buffer(gmb_engine* e, CholTilesArgs& a) {
+int tiles_trace_buffer(gmb_engine* e, hipStream_t s, CholTilesArgs& a) {
   int rc;
   if ((rc = ensure(e, &e->dct_trace, &e->cap_ct_trace, 4 * (int64_t)a.ntasks))) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)a.ntasks * 4 * sizeof(unsigned long long), e->cur));
+  HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)a.ntasks * 4 * sizeof(unsigned long long), s));
   a.dbg = e->dct_trace;
   return GMB_OK;
 }
 
 // `trace`, `lose`: task stamps and injected faults, as the caller of the factorisation asks for them
-int chol_tiles(gmb_engine* e, const FactorRef& f, bool trace, int lose, CholResult* res) {
+int chol_tiles(gmb_engine* e, hipStream_t s, const FactorRef& f, bool trace, int lose, CholResult* res) {
   const int nct = (int)(f.Np / TILE), nrt = (int)(f.Nr / TILE);
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
   if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
-  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), e->cur));
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), s));
   res->injected = lose > 0;
-  if (lose > 0 && (rc = tiles_lose_tickets(e, *f.ct, lose))) return rc;
+  if (lose > 0 && (rc = tiles_lose_tickets(e, s, *f.ct, lose))) return rc;
   CholTilesArgs a = tiles_args(f, 0, nct, nrt, ntasks);
   res->traced = trace;
-  if (trace && (rc = tiles_trace_buffer(e, a))) return rc;
+  if (trace && (rc = tiles_trace_buffer(e, s, a))) return rc;
   const double flops = chol_tiles_flops(f, nct, nrt);
   // eight-wave workgroups, one per compute unit: every phase of the latency chain has the whole compute unit (N = 10k:
   // 6.8 ms against 8.7 ms with four-wave workgroups, two per compute unit -- which stay available to the tuning build)
@@ -1161,9 +1156,9 @@ int chol_tiles(gmb_engine* e, const FactorRef& f, bool trace, int lose, CholResu
 #ifdef GMB_TUNING
   if (const char* cg = getenv("GMB_CT_GRID")) grid = std::max(1, std::min(grid, atoi(cg)));
 #endif
-  ev_begin(e, EV_CHOL_TILES, flops, nct, nrt, (int)f.Np, 0);
-  if (nw == 8) hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
-  else hipLaunchKernelGGL(chol_tiles_kernel<4>, dim3(grid), dim3(256), 0, e->cur, a);
+  ev_begin(e, s, EV_CHOL_TILES, flops, nct, nrt, (int)f.Np, 0);
+  if (nw == 8) hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL(chol_tiles_kernel<4>, dim3(grid), dim3(256), 0, s, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
   res->tiles = true;
@@ -1177,19 +1172,19 @@ int chol_tiles(gmb_engine* e, const FactorRef& f, bool trace, int lose, CholResu
 // (the 64 x 64-tile products that run at 45 TF/s: profiles/r05_bench_c3_kernel_stats.csv).  The control block is the tile
 // Cholesky's; its ABORT word is not cleared between the panels of one factorisation (chol_factor clears it once), so a
 // panel that gave up waiting makes every later one drain and the host sees it at the end.
-int chol_tiles_panel(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend, CholResult* res) {
+int chol_tiles_panel(gmb_engine* e, hipStream_t s, const FactorRef& f, int c0, int c1, int rend, CholResult* res) {
   const int nct = c1 - c0, nrt = rend - c0;
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
   if ((rc = ensure(e, f.ct, f.cap_ct, std::max<int64_t>(words, 4 + (int64_t)(e->panel_tiles_w + 3) * (f.Nr / TILE))))) return rc;  // (one size for every panel of the matrix)
-  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, sizeof(uint32_t), e->cur));                                       // the ticket counter
-  HIP_TRY(e, hipMemsetAsync(*f.ct + 2, 0, (size_t)(words - 2) * sizeof(uint32_t), e->cur));            // flags and chain words
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, sizeof(uint32_t), s));                                  // the ticket counter
+  HIP_TRY(e, hipMemsetAsync(*f.ct + 2, 0, (size_t)(words - 2) * sizeof(uint32_t), s));       // flags and chain words
   const CholTilesArgs a = tiles_args(f, c0, nct, nrt, ntasks);
   const double flops = chol_tiles_flops(f, nct, nrt, rend == (int)(f.Nr / TILE));
   const int grid = (int)std::min<long long>(ntasks, e->wg_slots / 2);
-  ev_begin(e, EV_CHOL_TILES_PANEL, flops, nct, nrt, nct * TILE, 0);
-  hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
+  ev_begin(e, s, EV_CHOL_TILES_PANEL, flops, nct, nrt, nct * TILE, 0);
+  hipLaunchKernelGGL(chol_tiles_kernel<8>, dim3(grid), dim3(512), 0, s, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
   res->tiles = true;  // (the abort word is read back with the factorisation's scalars)
@@ -1197,14 +1192,14 @@ int chol_tiles_panel(gmb_engine* e, const FactorRef& f, int c0, int c1, int rend
 }
 
 // V <- V L^-T (V: ntm x Np/128 tiles, leading dimension ldv) as one persistent launch (chol_tiles.hpp: trsm_tiles_kernel)
-int trsm_tiles(gmb_engine* e, const FactorRef& f, double* V, int64_t ldv, int ntm, EvKind ev_kind) {
+int trsm_tiles(gmb_engine* e, hipStream_t s, const FactorRef& f, double* V, int64_t ldv, int ntm, EvKind ev_kind, bool* launched) {
   const int nct = (int)(f.Np / TILE);
   const long long ntasks = (long long)ntm * nct;
   if (ntasks <= 0) return GMB_OK;
   const int64_t words = 4 + (int64_t)ntm * nct;
   int rc;
   if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
-  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), e->cur));
+  HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), s));
   CholTilesArgs a = tiles_args(f, 0, nct, nct, (int)ntasks, false);
   a.V = V;
   a.ldv = ldv;
@@ -1213,11 +1208,11 @@ int trsm_tiles(gmb_engine* e, const FactorRef& f, double* V, int64_t ldv, int nt
   for (int c = 0; c < nct; ++c)
     flops += (double)ntm * (2.0 * TILE * TILE * TILE * c * (c == nct - 1 ? ragged_col_frac(f) : 1.0) + (double)TILE * TILE * TILE);
   const int grid = (int)std::min<long long>(ntasks, e->wg_slots / 2);
-  ev_begin(e, ev_kind, flops, nct, ntm, (int)f.Np, 0);
-  hipLaunchKernelGGL(trsm_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a);
+  ev_begin(e, s, ev_kind, flops, nct, ntm, (int)f.Np, 0);
+  hipLaunchKernelGGL(trsm_tiles_kernel<8>, dim3(grid), dim3(512), 0, s, a);
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
-  e->tt_used = true;
+  *launched = true;
   return GMB_OK;
 }
 
@@ -1235,7 +1230,7 @@ bool eval_will_fuse(const gmb_engine* e) {
          nblocks <= e->tiles_max_blocks && (e->grad_scheme == 2 ? nblocks >= 1 : nblocks >= e->et_min_blocks);
 }
 
-int eval_tiles(gmb_engine* e, bool with_chol) {
+int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
   const FactorRef f = train_factor(e);
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   int rc;
@@ -1271,18 +1266,18 @@ int eval_tiles(gmb_engine* e, bool with_chol) {
   if ((rc = ensure(e, &e->dUdiag, &e->cap_udiag, (int64_t)nct * TILE * TILE))) return rc;
   if ((rc = ensure(e, &e->dApart, &e->cap_apart, (int64_t)nct * nct * TILE + nct))) return rc;  // (+ the partials of |v|^2)
   if ((rc = grad_workspace(e))) return rc;
-  if (!(with_chol && e->prezeroed)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), e->cur));
+  if (!(with_chol && e->prezeroed)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), s));
   // a factor that is final already: every tile flag reads "final" (any non-zero word)
-  if (!with_chol) HIP_TRY(e, hipMemsetAsync(e->dct + 4, 1, (size_t)nrt * nct * sizeof(uint32_t), e->cur));
+  if (!with_chol) HIP_TRY(e, hipMemsetAsync(e->dct + 4, 1, (size_t)nrt * nct * sizeof(uint32_t), s));
   const int lose = with_chol ? e->ct_lose : 0;
   e->chol.injected = lose > 0;
   if (lose > 0) {
     e->ct_lose = 0;
-    if ((rc = tiles_lose_tickets(e, e->dct, lose))) return rc;
+    if ((rc = tiles_lose_tickets(e, s, e->dct, lose))) return rc;
   }
   CholTilesArgs a = tiles_args(f, 0, nct, nrt, ntasks);
   e->chol.traced = e->ct_trace;
-  if (e->ct_trace && (rc = tiles_trace_buffer(e, a))) return rc;
+  if (e->ct_trace && (rc = tiles_trace_buffer(e, s, a))) return rc;
   EvalTilesArgs x{};
   x.tasks = e->det_tasks;
   x.ntasks = ntasks;
@@ -1303,10 +1298,10 @@ int eval_tiles(gmb_engine* e, bool with_chol) {
     flops += 2.0 * TILE * TILE * TILE * 0.5 * (double)c * (double)(c + 1) * (c == nct - 1 ? ragged_col_frac(f) : 1.0);
   for (int I = 0; I < nct; ++I) flops += 2.0 * TILE * TILE * TILE * (double)(nct - I) * (double)(I + 1);             // ZZ block row I
   const int grid = (int)std::min<long long>(ntasks, nw == 8 ? e->wg_slots / 2 : e->wg_slots);
-  ev_begin(e, EV_EVAL_TILES, flops, nct, nrt, (int)e->Np, with_chol ? 1 : 0);
-  if (nw == 8) hipLaunchKernelGGL(eval_tiles_kernel<8>, dim3(grid), dim3(512), 0, e->cur, a, x);
+  ev_begin(e, s, EV_EVAL_TILES, flops, nct, nrt, (int)e->Np, with_chol ? 1 : 0);
+  if (nw == 8) hipLaunchKernelGGL(eval_tiles_kernel<8>, dim3(grid), dim3(512), 0, s, a, x);
 #ifdef GMB_TUNING
-  else hipLaunchKernelGGL(eval_tiles_kernel<4>, dim3(grid), dim3(256), 0, e->cur, a, x);
+  else hipLaunchKernelGGL(eval_tiles_kernel<4>, dim3(grid), dim3(256), 0, s, a, x);
 #endif
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
@@ -1354,13 +1349,12 @@ int chol_lookahead_masked(gmb_engine* e, const FactorRef& f) {
   hipStream_t mainS = e->stream, bulkS = e->aux[2];
   e->sync_next = 0;
   int rc;
-  e->cur = mainS;
-  if ((rc = chol_cols(e, f, 0, std::min(w, nct), nrt, EV_CHOL_PANEL_GEMM))) return rc;  // (panels: their products belong to the chain)
+  if ((rc = chol_cols(e, mainS, f, 0, std::min(w, nct), nrt, EV_CHOL_PANEL_GEMM))) return rc;  // (panels: their products belong to the chain)
   for (int c0 = 0; c0 < nct; c0 += w) {
     const int c1 = std::min(c0 + w, nct);
     const int n0 = c1, n1 = std::min(c1 + w, nct);
     if (n0 >= nct) break;
-    auto update = [&](int col_lo, int col_hi) {
+    auto update = [&](hipStream_t s, int col_lo, int col_hi) {
       GemmArgs g{};
       g.C = f.A + (int64_t)col_lo * TILE + (int64_t)col_lo * TILE * f.ld;
       g.ldc = f.ld;
@@ -1374,19 +1368,14 @@ int chol_lookahead_masked(gmb_engine* e, const FactorRef& f) {
       g.alpha = -1.0;
       g.beta = 1.0;
       g.tri = 1;
-      return launch_gemm(e, g, EV_CHOL_UPDATE);
+      return launch_gemm(e, s, g, EV_CHOL_UPDATE);
     };
-    e->cur = mainS;
     if ((rc = order_after(e, bulkS, mainS))) return rc;   // U2(p-1) reached these columns
-    if ((rc = update(n0, n1))) return rc;                 // U1
+    if ((rc = update(mainS, n0, n1))) return rc;          // U1
     if ((rc = order_after(e, mainS, bulkS))) return rc;
-    e->cur = bulkS;
-    rc = (n1 < nct) ? update(n1, nct) : 0;          // U2, on the compute units its mask allows
-    e->cur = mainS;
-    if (rc) return rc;
-    if ((rc = chol_cols(e, f, n0, n1, nrt, EV_CHOL_PANEL_GEMM))) return rc;  // panel p+1, beside U2
+    if (n1 < nct && (rc = update(bulkS, n1, nct))) return rc;  // U2, on the compute units its mask allows
+    if ((rc = chol_cols(e, mainS, f, n0, n1, nrt, EV_CHOL_PANEL_GEMM))) return rc;  // panel p+1, beside U2
   }
-  e->cur = mainS;
   return order_after(e, bulkS, mainS);
 }
 
@@ -1406,8 +1395,7 @@ int chol_factor(gmb_engine* e, const FactorRef& f, const CholOpts& o, CholResult
                                                                  nblocks <= e->tiles_max_blocks));
   const bool masked = o.masked_ok && !tiles && e->lookahead && e->aux_shared && nblocks > e->panel_blocks &&
                       (e->chol_scheme == 2 || (e->chol_scheme < 0 && nblocks <= e->masked_max_blocks));
-  e->cur = e->stream;
-  if (tiles) return chol_tiles(e, f, o.trace, o.lose, res);
+  if (tiles) return chol_tiles(e, e->stream, f, o.trace, o.lose, res);
   if (masked) return chol_lookahead_masked(e, f);
   const bool tile_panels = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
   if (tile_panels) {
@@ -1415,21 +1403,21 @@ int chol_factor(gmb_engine* e, const FactorRef& f, const CholOpts& o, CholResult
     if ((rc = ensure(e, f.ct, f.cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * nrt))) return rc;
     HIP_TRY(e, hipMemsetAsync(*f.ct, 0, 4 * sizeof(uint32_t), e->stream));  // (the abort word: once per factorisation)
   }
-  return chol_cols(e, f, 0, nblocks, nrt, EV_CHOL_UPDATE, tile_panels ? res : nullptr);
+  return chol_cols(e, e->stream, f, 0, nblocks, nrt, EV_CHOL_UPDATE, tile_panels ? res : nullptr);
 }
 
 // ---- predict recursion: V <- W L^-T over column blocks [c0, c1) ------------------------------
 // lfirst / lstride (optional): row tile t of V stands for block row lfirst + t*lstride of a matrix
 // whose rows are zero left of their own diagonal block (rows of the identity being solved into
 // rows of L^-T): the update products then skip the structurally zero part of their contraction.
-int trsm_cols(gmb_engine* e, const FactorRef& f, double* V, int64_t ldz, int ntm, int c0, int c1, EvKind kind_gemm, EvKind kind_strip,
+int trsm_cols(gmb_engine* e, hipStream_t s, const FactorRef& f, double* V, int64_t ldz, int ntm, int c0, int c1, EvKind kind_gemm, EvKind kind_strip,
               int lfirst = -1, int lstride = 0) {
   if (c1 - c0 == 1)
-    return launch_trsm_strip(e, V + (int64_t)c0 * TILE * ldz, ldz, (int64_t)ntm * TILE,
+    return launch_trsm_strip(e, s, V + (int64_t)c0 * TILE * ldz, ldz, (int64_t)ntm * TILE,
                              f.A + (int64_t)c0 * TILE * (f.ld + 1), f.ld, f.dinv16 + (int64_t)c0 * 8 * 256,
                              (int)std::min<int64_t>(TILE, f.N - (int64_t)c0 * TILE), kind_strip);
   const int mid = c0 + (c1 - c0 + 1) / 2;
-  int rc = trsm_cols(e, f, V, ldz, ntm, c0, mid, kind_gemm, kind_strip, lfirst, lstride);
+  int rc = trsm_cols(e, s, f, V, ldz, ntm, c0, mid, kind_gemm, kind_strip, lfirst, lstride);
   if (rc) return rc;
   GemmArgs g{};
   g.C = V + (int64_t)mid * TILE * ldz;
@@ -1448,9 +1436,9 @@ int trsm_cols(gmb_engine* e, const FactorRef& f, double* V, int64_t ldz, int ntm
     g.krow_stride = lstride;
     g.krow_off = (lfirst - c0) * TILE;
   }
-  rc = launch_gemm(e, g, kind_gemm);
+  rc = launch_gemm(e, s, g, kind_gemm);
   if (rc) return rc;
-  return trsm_cols(e, f, V, ldz, ntm, mid, c1, kind_gemm, kind_strip, lfirst, lstride);
+  return trsm_cols(e, s, f, V, ldz, ntm, mid, c1, kind_gemm, kind_strip, lfirst, lstride);
 }
 
 // ---- NLML gradient ---------------------------------------------------------------------------
@@ -1462,17 +1450,17 @@ int trsm_cols(gmb_engine* e, const FactorRef& f, double* V, int64_t ldz, int ntm
 //              off-diagonal blocks of L stay intact in the lower triangle).
 //   [[A,0],[B,C]]^-1 = [[A^-1,0],[-C^-1 B A^-1, C^-1]]:
 //     T^T = U_A B^T (scratch, mirrored region of dW),  W21 = -W_C T,  U12 = W21^T (transpose).
-int launch_transpose(gmb_engine* e, const double* src, int64_t lds_, double* dst, int64_t ldd, int rows,
+int launch_transpose(gmb_engine* e, hipStream_t s, const double* src, int64_t lds_, double* dst, int64_t ldd, int rows,
                      int cols) {
-  hipLaunchKernelGGL(transpose_kernel, dim3((rows + 31) / 32, (cols + 31) / 32), dim3(256), 0, e->cur, src,
+  hipLaunchKernelGGL(transpose_kernel, dim3((rows + 31) / 32, (cols + 31) / 32), dim3(256), 0, s, src,
                      lds_, dst, ldd, rows, cols);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
 
-int winv_node(gmb_engine* e, int c0, int c1, bool recurse);
+int winv_node(gmb_engine* e, hipStream_t s, int c0, int c1, bool recurse);
 
-int winv_cols(gmb_engine* e, int c0, int c1) { return winv_node(e, c0, c1, true); }
+int winv_cols(gmb_engine* e, hipStream_t s, int c0, int c1) { return winv_node(e, s, c0, c1, true); }
 
 // The two halves of a node are independent (both read only L and the inv(L_kk) blocks), so the
 // whole recursion tree can be executed level by level, bottom-up, with the nodes of a level dealt
@@ -1491,7 +1479,7 @@ void collect_inv_nodes(int c0, int c1, int depth, std::vector<std::vector<InvNod
   }
 }
 int build_inv_plan(gmb_engine* e, const std::vector<std::vector<InvNode>>& levels);
-int winv_level_batched(gmb_engine* e, const gmb_engine::InvLevelPlan& lp);
+int winv_level_batched(gmb_engine* e, hipStream_t s, const gmb_engine::InvLevelPlan& lp);
 
 int winv_levels(gmb_engine* e, int nt) {
   std::vector<std::vector<InvNode>> levels;
@@ -1511,8 +1499,8 @@ int winv_levels(gmb_engine* e, int nt) {
     if (batched && e->inv_plan[depth].count > 0) {
       // consecutive batched levels live on the main stream alone: no event traffic between them (an
       // event record + three stream waits per level showed up as 20-25 us bubbles in the timeline)
-      e->cur = e->stream;  // every stream was joined into the main one after the previous level
-      if ((rc = winv_level_batched(e, e->inv_plan[depth]))) return rc;
+      // (every stream was joined into the main one after the previous level)
+      if ((rc = winv_level_batched(e, streams[0], e->inv_plan[depth]))) return rc;
       aux_behind = true;
       continue;
     }
@@ -1522,14 +1510,8 @@ int winv_levels(gmb_engine* e, int nt) {
       aux_behind = false;
     }
     int idx = 0;
-    for (const InvNode& nd : levels[depth]) {
-      e->cur = streams[levels[depth].size() > 1 ? (idx++ & 3) : 0];
-      if ((rc = winv_node(e, nd.c0, nd.c1, false))) {
-        e->cur = e->stream;
-        return rc;
-      }
-    }
-    e->cur = e->stream;
+    for (const InvNode& nd : levels[depth])
+      if ((rc = winv_node(e, streams[levels[depth].size() > 1 ? (idx++ & 3) : 0], nd.c0, nd.c1, false))) return rc;
     for (int a = 1; a < 4; ++a)
       if ((rc = order_after(e, streams[a], streams[0]))) return rc;
     if (depth > 0)
@@ -1583,20 +1565,20 @@ void winv_node_products(gmb_engine* e, int c0, int c1, GemmArgs& gt, GemmArgs& g
   tr.cols = n1 * TILE;
 }
 
-int winv_node(gmb_engine* e, int c0, int c1, bool recurse) {
+int winv_node(gmb_engine* e, hipStream_t s, int c0, int c1, bool recurse) {
   if (c1 - c0 == 1) return GMB_OK;  // leaf_invert_kernel wrote both diagonal blocks already
   const int mid = c0 + (c1 - c0 + 1) / 2;
   int rc;
   if (recurse) {
-    if ((rc = winv_node(e, c0, mid, true))) return rc;
-    if ((rc = winv_node(e, mid, c1, true))) return rc;
+    if ((rc = winv_node(e, s, c0, mid, true))) return rc;
+    if ((rc = winv_node(e, s, mid, c1, true))) return rc;
   }
   GemmArgs gt, gw;
   TransposeJob tr;
   winv_node_products(e, c0, c1, gt, gw, tr);
-  if ((rc = launch_gemm(e, gt, EV_GRAD_GEMM))) return rc;
-  if ((rc = launch_gemm(e, gw, EV_GRAD_GEMM))) return rc;
-  return launch_transpose(e, tr.src, e->Np, tr.dst, e->ld, tr.rows, tr.cols);
+  if ((rc = launch_gemm(e, s, gt, EV_GRAD_GEMM))) return rc;
+  if ((rc = launch_gemm(e, s, gw, EV_GRAD_GEMM))) return rc;
+  return launch_transpose(e, s, tr.src, e->Np, tr.dst, e->ld, tr.rows, tr.cols);
 }
 
 // ---- batched levels ---------------------------------------------------------------------------
@@ -1678,22 +1660,22 @@ int build_inv_plan(gmb_engine* e, const std::vector<std::vector<InvNode>>& level
   return GMB_OK;
 }
 
-int winv_level_batched(gmb_engine* e, const gmb_engine::InvLevelPlan& lp) {
+int winv_level_batched(gmb_engine* e, hipStream_t s, const gmb_engine::InvLevelPlan& lp) {
   for (int b = 0; b < 2; ++b) {
     if (lp.grid_x[b] <= 0) continue;
     const GemmArgs* batch = e->dplan_gemm + lp.off[b];
     const dim3 grid(lp.grid_x[b], lp.count);
-    ev_begin(e, EV_GRAD_GEMM, lp.flops[b], lp.count, 0, 0, (lp.variant[b] << 8) | 64);
+    ev_begin(e, s, EV_GRAD_GEMM, lp.flops[b], lp.count, 0, 0, (lp.variant[b] << 8) | 64);
     switch (lp.variant[b]) {
-      case 0: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, e->cur, batch); break;
-      case 1: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 2, 2, 2>), grid, dim3(256), 0, e->cur, batch); break;
-      default: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 4, 2, 2>), grid, dim3(256), 0, e->cur, batch); break;
+      case 0: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, s, batch); break;
+      case 1: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 2, 2, 2>), grid, dim3(256), 0, s, batch); break;
+      default: hipLaunchKernelGGL((gemm_f64_batched_kernel<2, 2, 4, 2, 2>), grid, dim3(256), 0, s, batch); break;
     }
     ev_end(e);
     HIP_TRY(e, hipGetLastError());
   }
   hipLaunchKernelGGL(transpose_batched_kernel, dim3((lp.tr_rows + 31) / 32, (lp.tr_cols + 31) / 32, lp.count),
-                     dim3(256), 0, e->cur, e->dplan_tr + lp.toff, e->Np, e->ld);
+                     dim3(256), 0, s, e->dplan_tr + lp.toff, e->Np, e->ld);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
@@ -1745,7 +1727,7 @@ int grad_workspace(gmb_engine* e) {
   return GMB_OK;  // (the accumulators live in the engine's scalar block)
 }
 
-int grad_sigma_inv_rows(gmb_engine* e, int shard, int nshards, double* Z, int64_t ldz, bool packed) {
+int grad_sigma_inv_rows(gmb_engine* e, hipStream_t s, int shard, int nshards, double* Z, int64_t ldz, bool packed) {
   const int nt = (int)(e->Np / TILE);
   const int owned = shard < nt ? (nt - shard + nshards - 1) / nshards : 0;
   GemmArgs g{};
@@ -1766,7 +1748,7 @@ int grad_sigma_inv_rows(gmb_engine* e, int shard, int nshards, double* Z, int64_
   g.cblk_stride = packed ? 1 : 0;
   g.alpha = 1.0;
   g.beta = 0.0;
-  return launch_gemm(e, g, EV_GRAD_GEMM);
+  return launch_gemm(e, s, g, EV_GRAD_GEMM);
 }
 
 int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t ldz, bool packed,
@@ -1999,8 +1981,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
     std::unique_ptr<PhaseTimer> tgt(timed ? new PhaseTimer(e) : nullptr);
     bool own_launch = false;
     if (!e->et_fused) {
-      e->cur = e->stream;
-      if ((rc = eval_tiles(e, false))) return rc;
+      if ((rc = eval_tiles(e, e->stream, false))) return rc;
       own_launch = true;
     }
     e->et_fused = false;
@@ -2057,7 +2038,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   if (!e->fact_in_flight) e->sync_next = 0;  // (gmb_evaluate: the factorisation's cross-stream waits may still be pending on pooled events)
   if (e->par_inverse) {
     if ((rc = winv_levels(e, nt))) return rc;
-  } else if ((rc = winv_cols(e, 0, nt))) {
+  } else if ((rc = winv_cols(e, e->stream, 0, nt))) {
     return rc;
   }
   // 2. alpha = W^T v = Sigma^-1 y   (before Sigma^-1 overwrites W)
@@ -2072,7 +2053,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
                        e->dA, e->ld, e->N, e->Np);
   HIP_TRY(e, hipGetLastError());
   // 3. Sigma^-1 = U U^T (lower triangle) into dW -- the last reader of U: the factor's diagonal blocks go back
-  if ((rc = grad_sigma_inv_rows(e, 0, 1, e->dW, e->Np, false))) return rc;
+  if ((rc = grad_sigma_inv_rows(e, e->stream, 0, 1, e->dW, e->Np, false))) return rc;
   hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 0);
   HIP_TRY(e, hipGetLastError());
   // 4. fused trace reductions
@@ -2301,7 +2282,6 @@ int gmb_create_impl(gmb_engine** out, int32_t device, void* stream, const gmb_en
   const char* pc = getenv("GMB_PART_CUS");
   if (pc) part = atoi(pc);
 #endif
-  e->cur = e->stream;
   // Exactly four streams per engine (beyond four hardware queues the runtime multiplexes streams and every
   // kernel of the process slows down -- measured): the caller's, aux[0] / aux[1] at the highest queue
   // priority (panel chain of the unmasked look-ahead; independent merges of the triangular inverse), and
@@ -2636,12 +2616,11 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   // 2. Cholesky
   if (events) HIP_TRY(e, hipEventRecord(e->fe[2], e->stream));
   e->chol = CholResult{};
-  e->cur = e->stream;
   e->et_fused = false;
   if (fused) {
     // the gradient's inverse and Sigma^-1 ride in the factorisation's launch (eval_tiles.hpp); v = L^-1 y (row N of the factor)
     // and |v|^2 come out of the launch that adds up alpha
-    if ((rc = eval_tiles(e, true))) return rc;
+    if ((rc = eval_tiles(e, e->stream, true))) return rc;
     e->et_fused = true;
   } else {
     CholOpts o;
@@ -2902,8 +2881,7 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
   const bool by_size = nblocks >= e->tiles_trsm_min_blocks && nblocks <= e->tiles_max_blocks &&
                        (ntm >= 32 || (long long)ntm * nblocks >= 576);
   const bool tiles = !e->naive_leaf && ntm <= 96 && (e->chol_scheme == 3 || (e->chol_scheme < 0 && by_size));
-  e->cur = e->stream;
-  e->tt_used = false;
+  bool tile_solve = false;  // the solve ran on the tile kernel, whose abort word is read back below
   if (e->solve_hook) {
     if ((rc = e->solve_hook(e->dV, mpad, (int)(mpad / TILE)))) return rc;
   } else if (use_gemm_form) {
@@ -2934,11 +2912,11 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
     g.alpha = 1.0;
     g.beta = 0.0;
     g.khi_n = 1;
-    if ((rc = launch_gemm(e, g, EV_PREDICT_GEMM))) return rc;
-  } else if ((rc = tiles ? trsm_tiles(e, train_factor(e), e->dV, mpad, (int)(mpad / TILE), EV_PREDICT_GEMM)
-                         : trsm_cols(e, train_factor(e), e->dV, mpad, (int)(mpad / TILE), 0, nblocks, EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
+    if ((rc = launch_gemm(e, e->stream, g, EV_PREDICT_GEMM))) return rc;
+  } else if ((rc = tiles ? trsm_tiles(e, e->stream, train_factor(e), e->dV, mpad, ntm, EV_PREDICT_GEMM, &tile_solve)
+                         : trsm_cols(e, e->stream, train_factor(e), e->dV, mpad, ntm, 0, nblocks, EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
     return rc;
-  if (e->tt_used) {  // a launch that gave up waiting must not be mistaken for a prediction
+  if (tile_solve) {  // a launch that gave up waiting must not be mistaken for a prediction
     uint32_t ab = 0;
     HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -3042,7 +3020,7 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   if ((rc = predict_reduce(e, M, Mr, gemm_form))) return rc;
   // the product form leaves V with the training index fastest: turned into the update's k-major layout (the cross-covariance
   // in dV has served the mean)
-  if (gemm_form && (rc = launch_transpose(e, e->dV2, e->Np, e->dV, Mr, (int)e->Np, (int)Mr))) return rc;
+  if (gemm_form && (rc = launch_transpose(e, e->stream, e->dV2, e->Np, e->dV, Mr, (int)e->Np, (int)Mr))) return rc;
   // Columns N .. Np-1 of V belong to no training point.  gmb_predict never reads them (its reductions stop at N); the update
   // below contracts over all Np, so they are cleared, whichever form produced them.
   if (e->Np > e->N)
@@ -3089,8 +3067,7 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   g.alpha = -1.0;
   g.beta = 1.0;
   g.tri = 1;
-  e->cur = e->stream;
-  return launch_gemm(e, g, EV_PREDICT_GEMM);
+  return launch_gemm(e, e->stream, g, EV_PREDICT_GEMM);
 }
 
 // C -> L* in place, by the schedule gmb_factorize would give a matrix of this size (chol_factor: the persistent tile kernel from
@@ -3614,7 +3591,7 @@ int gmb_blk_potrf(gmb_engine* e, double* Akk, int64_t lda, int32_t nvalid, doubl
 #else
   a.dbg = nullptr;
 #endif
-  return launch_leaf(e, a);
+  return launch_leaf(e, e->stream, a);
 }
 
 int gmb_blk_invert(gmb_engine* e, const double* Lkk, int64_t lda, int32_t nvalid, const double* dinv16,
@@ -3640,7 +3617,7 @@ int gmb_blk_trsm(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, const dou
       nvalid > TILE)
     return fail(e, GMB_EINVAL, "bad trsm arguments (rows must be a multiple of 16)");
   HIP_TRY(e, hipSetDevice(e->device));
-  return launch_trsm_strip(e, B, ldb, nrows, Lkk, ldl, dinv16, nvalid, EV_CHOL_STRIP);
+  return launch_trsm_strip(e, e->stream, B, ldb, nrows, Lkk, ldl, dinv16, nvalid, EV_CHOL_STRIP);
 }
 
 int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int64_t lda, const double* B,
@@ -3664,7 +3641,7 @@ int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int6
   g.beta = beta;
   g.tri = tri;
   g.tri_off = (int)(tri_shift * TILE);
-  return launch_gemm(e, g, EV_CHOL_PANEL_GEMM);
+  return launch_gemm(e, e->stream, g, EV_CHOL_PANEL_GEMM);
 }
 
 }  // extern "C"

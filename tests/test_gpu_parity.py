@@ -906,6 +906,39 @@ def test_evaluation_schedules_agree_with_each_other_and_the_oracle(gpu, N, kind)
     eng.close()
 
 
+def test_launch_tree_inverse_over_four_streams(gpu):
+    """The gradient's inverse as a tree of launches on a matrix of MORE than 64 block columns (N = 8321: 66, ragged), where
+    csrc/engine.hip: winv_levels deals the merge nodes of the unbatched top levels over four streams -- otherwise reached only by
+    the N = 50k / 100k tests.  Plain recursion for the factor, so every launch of the evaluation is one of the launch helpers on
+    a stream its caller names.  Twice = the same bits (a launch on the wrong stream races); NLML and gradient against the oracle
+    at the bounds of test_c3_midsize_parity, the gradient against the tile schedule of the same engine at the bound of the
+    schedules test above, and a prediction from the factor afterwards (direct distances, as in the schedules test)."""
+    N, d = 8321, 3
+    X, y, ls = O.synthetic_table(N, d, seed=31)
+    spec = O.make_spec(d, range(d), kind="Matern52")
+    theta = O.pack_theta(spec, ls, 1.15, 0.22)
+    Xs = np.random.default_rng(2).standard_normal((200, d))
+    eng = make_engine(spec, theta, X, y)
+    eng.set_chol_scheme(eng.CHOL_RECURSION)
+    eng.set_grad_scheme(eng.GRAD_LAUNCH_TREE)
+    val, g = eng.evaluate(theta)
+    val2, g2 = eng.evaluate(theta)
+    assert np.float64(val2).tobytes() == np.float64(val).tobytes() and g2.tobytes() == g.tobytes()
+    assert eng.factor_is_current()
+    mu, var = eng.predict(Xs)
+    eng.set_grad_scheme(eng.GRAD_TILES)
+    val_t, g_t = eng.evaluate(theta)
+    eng.close()
+    val_r, grad_r = O.nlml_and_grad(spec, theta, X, y)
+    mu_r, var_r = O.predict(spec, theta, X, y, Xs, dist_mode="direct")
+    print("nlml rel", abs(val - val_r) / abs(val_r), "grad abs", np.max(np.abs(g - grad_r)), "of", np.max(np.abs(grad_r)),
+          "tree vs tiles", rel(g, g_t), "mean rel", rel(mu, mu_r), "var abs", np.max(np.abs(var - var_r)))
+    assert np.isclose(val, val_r, rtol=1e-10, atol=0.0)
+    assert np.max(np.abs(g - grad_r)) < 1e-8 * max(1.0, np.max(np.abs(grad_r)))
+    assert rel(g, g_t) < 1e-10
+    assert rel(mu, mu_r) < 1e-8 and np.max(np.abs(var - var_r)) < 1e-9
+
+
 @pytest.mark.parametrize("N,kind", [(300, "ExpQuad"), (2689, "Matern52"), (5200, "ExpQuad"), (9300, "Matern32")])
 def test_paired_sigma_inverse_tasks_change_no_bit(gpu, N, kind):
     """gmb_set_eval_pairs: Sigma^-1 as 128 x 256 tasks (two tiles per pass over the task's own block row of U; by default for
