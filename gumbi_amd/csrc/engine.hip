@@ -581,7 +581,17 @@ long long gemm_nact128(const GemmArgs& g) {
   return nact;
 }
 
-int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_kind) {
+// The test door's pins (gmb_blk_gemm_ex): every field -1 = decide as always.  A pinned combination that launch_gemm could not
+// arrive at by itself under any engine setting is refused (GMB_EINVAL) before anything is launched.  `launched` receives what ran:
+//   bits 0-1 tile shape (variant) | bit 2 LDS-DMA staging | bit 3 PFC | bit 4 in place | bits 5-6 order | bits 8-15 strip |
+//   bits 16-30 grid size (saturating at 0x7fff)
+struct GemmPin {
+  int variant = -1, staging = -1, pfc = -1, order = -1, strip = -1;
+  int32_t* launched = nullptr;
+};
+
+int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_kind, const GemmPin* pin = nullptr) {
+  if (pin && pin->launched) *pin->launched = 0;
   if (g_in.mt <= 0 || g_in.nt <= 0 || g_in.k <= 0) return GMB_OK;
   GemmArgs g = g_in;
   // tiles the 128 x 128 tiling would compute
@@ -611,6 +621,13 @@ int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_ki
       variant = 0;
       if (score(2) > score(variant)) variant = 2;
       if (score(3) > score(variant)) variant = 3;
+      if (pin && pin->variant >= 0) {
+        if (pin->variant != 0 && pin->variant != 2 && pin->variant != 3) return fail(e, GMB_EINVAL, "gemm pin: the in-place form runs on the 128-row tiles (variants 0, 2, 3)");
+        variant = pin->variant;
+      }
+    } else if (pin && pin->variant >= 0) {
+      if (pin->variant > 3) return fail(e, GMB_EINVAL, "gemm pin: variant %d", pin->variant);
+      variant = pin->variant;
     } else if (!e->force_variant) {
       variant = 0;
       if (e->small_tiles) {
@@ -635,8 +652,31 @@ int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_ki
   g.order = 0;
   if (e->lpt_order && nact <= e->lpt_max_tiles && g.nblk_stride == 1 && g.tri_off >= 0 && !g.klo_m && (g.klo_n != 0) != (g.khi_n != 0))
     g.order = g.klo_n ? 1 : 2;
+  if (pin && pin->order >= 0) {  // 1 / 2 only where the rule above could choose them, whatever the engine's settings
+    const bool lpt_ok = g.nblk_stride == 1 && g.tri_off >= 0 && !g.klo_m && (g.klo_n != 0) != (g.khi_n != 0);
+    if (pin->order > 2 || (pin->order != 0 && (!lpt_ok || pin->order != (g.klo_n ? 1 : 2))))
+      return fail(e, GMB_EINVAL, "gemm pin: order %d is not one launch_gemm chooses for this product", pin->order);
+    g.order = pin->order;
+  }
   // L2-aware rasterisation of the XCD runs for launches that are several patches large (GemmArgs::strip)
   g.strip = (g.order == 0 && e->tile_strip > 0 && g.mt >= 2 && !in_place && !g.klo_m) ? e->tile_strip : 0;
+  if (pin && pin->strip >= 0) {
+    if (pin->strip > 255 || (pin->strip > 0 && !(g.order == 0 && g.mt >= 2 && !in_place && !g.klo_m)))
+      return fail(e, GMB_EINVAL, "gemm pin: strip %d is not one launch_gemm chooses for this product", pin->strip);
+    g.strip = pin->strip;
+  }
+  bool pfc = g.beta != 0.0 && g.k <= 1024 && !in_place;
+  bool dma = e->gemm_dma && variant == 0 && !in_place;
+  if (pin && pin->pfc >= 0) {  // (a pinned PFC may sit on either side of the rule's k <= 1024: a speed threshold, not a limit of the kernel)
+    if (pin->pfc > 1 || (pin->pfc == 1 && (g.beta == 0.0 || in_place || variant == 0)))
+      return fail(e, GMB_EINVAL, "gemm pin: C prefetch needs beta != 0, an out-of-place product and a small tile");
+    pfc = pin->pfc == 1;
+  }
+  if (pin && pin->staging >= 0) {
+    if (pin->staging > 1 || (pin->staging == 1 && (variant != 0 || in_place)))
+      return fail(e, GMB_EINVAL, "gemm pin: LDS-DMA staging exists for the out-of-place 128 x 128 tile only");
+    dma = pin->staging == 1;
+  }
   double flops = 0.0;
   const int nblocks = gemm_schedule(g, bm, bn, &flops);
   if (nblocks <= 0) return GMB_OK;
@@ -650,11 +690,13 @@ int launch_gemm(gmb_engine* e, hipStream_t s, const GemmArgs& g_in, EvKind ev_ki
   ev_begin(e, s, ev_kind, flops, g_in.mt, g_in.nt, g.k,
            g.tri | (g.klo_n << 3) | (g.khi_n << 4) | (g.klo_m << 5) | (variant << 8) | was_update);
   const dim3 grid(nblocks);
-  const bool pfc = g.beta != 0.0 && g.k <= 1024 && !in_place;
+  if (pin && pin->launched)
+    *pin->launched = variant | (dma ? 4 : 0) | (variant != 0 && pfc ? 8 : 0) | (in_place ? 16 : 0) | (g.order << 5) | ((g.strip & 0xff) << 8) |
+                     (std::min(nblocks, 0x7fff) << 16);
   switch (variant) {
     case 0:
-      if (e->gemm_dma && bulk_update) hipLaunchKernelGGL(gemm_f64_dma_chol_update_kernel, grid, dim3(256), 0, s, g);
-      else if (e->gemm_dma && !in_place) hipLaunchKernelGGL(gemm_f64_dma_kernel, grid, dim3(256), 0, s, g);
+      if (dma && bulk_update) hipLaunchKernelGGL(gemm_f64_dma_chol_update_kernel, grid, dim3(256), 0, s, g);
+      else if (dma) hipLaunchKernelGGL(gemm_f64_dma_kernel, grid, dim3(256), 0, s, g);
       else hipLaunchKernelGGL((gemm_f64_kernel<2, 2, 4, 4, 2>), grid, dim3(256), 0, s, g);
       break;
 #ifdef GMB_TUNING
@@ -3642,6 +3684,57 @@ int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int6
   g.tri = tri;
   g.tri_off = (int)(tri_shift * TILE);
   return launch_gemm(e, e->stream, g, EV_CHOL_PANEL_GEMM);
+}
+
+// The same product with every field of GemmArgs and every choice of launch_gemm in the caller's hands (tests): see the header.
+int gmb_blk_gemm_ex(gmb_engine* e, double* C, const double* A, const double* B, const gmb_gemm_desc* d, int32_t* launched) {
+  if (launched) *launched = 0;
+  if (!e) return GMB_EINVAL;
+  if (!C || !A || !B || !d) return fail(e, GMB_EINVAL, "null gemm operand");
+  if (d->m % TILE || d->n % TILE || d->k % KT || d->m < 0 || d->n < 0 || d->k < 0 || d->m > (1 << 24) || d->n > (1 << 24) || d->k > (1 << 24))
+    return fail(e, GMB_EINVAL, "gemm sizes must be multiples of 128 (m, n) and 16 (k)");
+  // the kernels move operands 16 bytes at a time
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)(d->lda * 8) | (uintptr_t)(d->ldb * 8)) & 15u)
+    return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: A and B must be 16-byte aligned, lda and ldb even");
+  if (d->nblk_stride < 0 || d->cblk_stride < 0 || d->krow_stride < 0 || d->nblk_stride > 4096 || d->cblk_stride > 4096 || d->krow_stride > 4096 ||
+      (d->klo_m | d->klo_n | d->khi_n | d->tri) < 0 || (d->klo_m | d->klo_n | d->khi_n | d->tri) > 1)
+    return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: strides must be >= 0, tri / klo_m / klo_n / khi_n 0 or 1");
+  if (d->tri_off % 32 || d->krow_off % TILE) return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: tri_off must be a multiple of 32, krow_off of 128");
+  const int64_t bs = d->nblk_stride < 1 ? 1 : d->nblk_stride, cs = d->cblk_stride > 0 ? d->cblk_stride : bs;
+  const int64_t brows = d->n ? ((d->n / TILE - 1) * bs + 1) * TILE : 0, crows = d->n ? ((d->n / TILE - 1) * cs + 1) * TILE : 0;
+  if (d->lda < d->m || d->ldb < brows || d->ldc < crows) return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: a leading dimension is smaller than its operand");
+  if ((const double*)C == B && d->ldc != d->ldb) return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: in place needs ldc == ldb");
+  if (d->variant < -1 || d->staging < -1 || d->pfc < -1 || d->order < -1 || d->strip < -1) return fail(e, GMB_EINVAL, "gmb_blk_gemm_ex: a pin below -1");
+  HIP_TRY(e, hipSetDevice(e->device));
+  GemmArgs g{};
+  g.C = C;
+  g.ldc = d->ldc;
+  g.A = A;
+  g.lda = d->lda;
+  g.B = B;
+  g.ldb = d->ldb;
+  g.mt = (int)(d->m / TILE);
+  g.nt = (int)(d->n / TILE);
+  g.k = (int)d->k;
+  g.alpha = d->alpha;
+  g.beta = d->beta;
+  g.tri = d->tri;
+  g.tri_off = d->tri_off;
+  g.nblk_stride = d->nblk_stride;
+  g.cblk_stride = d->cblk_stride;
+  g.klo_m = d->klo_m;
+  g.klo_n = d->klo_n;
+  g.khi_n = d->khi_n;
+  g.krow_off = d->krow_off;
+  g.krow_stride = d->krow_stride;
+  GemmPin pin;
+  pin.variant = d->variant;
+  pin.staging = d->staging;
+  pin.pfc = d->pfc;
+  pin.order = d->order;
+  pin.strip = d->strip;
+  pin.launched = launched;
+  return launch_gemm(e, e->stream, g, EV_CHOL_PANEL_GEMM, &pin);
 }
 
 }  // extern "C"

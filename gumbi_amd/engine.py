@@ -248,6 +248,19 @@ class DistStep(C.Structure):
         return d
 
 
+class GemmDesc(C.Structure):
+    """``gmb_gemm_desc`` (ABI 13): one GEMM launch with every descriptor field and every choice of the launcher pinned or left
+    (-1) -- the test door :meth:`Engine.blk_gemm_ex`."""
+
+    _fields_ = [(n, C.c_int64) for n in ("ldc", "lda", "ldb", "m", "n", "k")] + [("alpha", C.c_double), ("beta", C.c_double)] + [
+        (n, C.c_int32) for n in ("tri", "tri_off", "nblk_stride", "cblk_stride", "klo_m", "klo_n", "khi_n", "krow_off",
+                                 "krow_stride", "variant", "staging", "pfc", "order", "strip")]
+
+
+#: block tile (BM, BN) of each GEMM tile shape (``variant`` of gmb_gemm_desc)
+GEMM_TILE_SHAPES = ((128, 128), (64, 64), (128, 64), (128, 32))
+
+
 _SIGNATURES = {
     "gmb_abi_version": (C.c_int, []),
     "gmb_device_count": (C.c_int, []),
@@ -315,6 +328,7 @@ _SIGNATURES = {
     "gmb_blk_gemm_nt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                   C.c_int32, C.c_int64]),
+    "gmb_blk_gemm_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
 }
 
 
@@ -354,8 +368,9 @@ def _preload_hip_runtime():
 #: tools' door ``gmb_debug_assume_factored``, the guards between single-engine and capacity-mode factorisations, ``gmb_set_eval_pairs``;
 #: version 10 ``gmb_set_predict_form`` (GEMM-form prediction behind a fit), ``total_chol_update_all_*`` / ``predict_gemm_form`` in
 #: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
-#: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``)
-ABI_VERSION = 12
+#: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``; version 13 the GEMM test door
+#: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``)
+ABI_VERSION = 13
 
 
 def load_library():
@@ -763,6 +778,21 @@ class Engine:
         self._check(self._lib.gmb_blk_gemm_nt(self._h, C.c_void_p(c_ptr), ldc, C.c_void_p(a_ptr), lda,
                                               C.c_void_p(b_ptr), ldb, m, n, k, alpha, beta, tri, tri_shift),
                     "gmb_blk_gemm_nt")
+
+    def blk_gemm_ex(self, c_ptr, a_ptr, b_ptr, ldc, lda, ldb, m, n, k, alpha, beta, tri=0, tri_off=0, nblk_stride=1,
+                    cblk_stride=0, klo_m=0, klo_n=0, khi_n=0, krow_off=0, krow_stride=0, variant=-1, staging=-1, pfc=-1,
+                    order=-1, strip=-1):
+        """One GEMM launch with every field of its descriptor given and the launcher's choices pinned (-1 = left to it);
+        ``c_ptr == b_ptr`` selects the in-place form.  Returns what ran: ``dict(variant, dma, pfc, in_place, order, strip,
+        grid)``; raises ``ValueError`` for a combination the launcher could not produce (nothing is launched)."""
+        d = GemmDesc(ldc, lda, ldb, m, n, k, alpha, beta, tri, tri_off, nblk_stride, cblk_stride, klo_m, klo_n, khi_n,
+                     krow_off, krow_stride, variant, staging, pfc, order, strip)
+        w = C.c_int32(0)
+        self._check(self._lib.gmb_blk_gemm_ex(self._h, C.c_void_p(c_ptr), C.c_void_p(a_ptr), C.c_void_p(b_ptr),
+                                              C.byref(d), C.byref(w)), "gmb_blk_gemm_ex")
+        w = w.value
+        return dict(variant=w & 3, dma=(w >> 2) & 1, pfc=(w >> 3) & 1, in_place=(w >> 4) & 1, order=(w >> 5) & 3,
+                    strip=(w >> 8) & 0xFF, grid=(w >> 16) & 0x7FFF)
 
 
 def chol_task(t: int, nct: int, nrt: int):

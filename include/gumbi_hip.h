@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 12
+#define GMB_ABI_VERSION 13
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -418,6 +418,32 @@ int gmb_blk_trsm(gmb_engine* e, double* B, int64_t ldb, int64_t nrows, const dou
 int gmb_blk_gemm_nt(gmb_engine* e, double* C, int64_t ldc, const double* A, int64_t lda,
                     const double* B, int64_t ldb, int64_t m, int64_t n, int64_t k, double alpha,
                     double beta, int32_t tri, int64_t tri_shift);
+/* (ABI 13) The same product with every field of the launch's descriptor and every choice the launcher makes in the caller's
+ * hands, so that a test can run each kernel form on its own (tests/test_gpu_gemm.py).  Column-major, device pointers:
+ *   C[nc(i) + j*ldc] = beta * C[..] + alpha * sum_{k in [k_lo, k_hi)} A[j + k*lda] * B[nb(i) + k*ldb],   i < n, j < m
+ * nb(i) / nc(i) = (i / 128) * stride * 128 + i % 128 with stride = nblk_stride (B; 0 = 1) and cblk_stride (C; 0 = as B).
+ * Per TILE (tm, tn) of the block tile BM x BN the launch runs:  R = (row of the tile's first n index with stride krow_stride, 0 =
+ * as B) + krow_off;  k_hi = khi_n ? min(k, R + BN) : k;  k_lo = klo_m*tm*BM + klo_n*R clamped to [0, k_hi];  with tri the tile
+ * is skipped (C untouched) when nb(first i) + BN - 1 + tri_off < tm*BM.  C == B selects the in-place form (m == 128, ldc == ldb).
+ * Pins: -1 leaves the choice to the launcher; a pinned combination the launcher could not produce itself (C prefetch with
+ * beta == 0, in place or on the 128 x 128 tile; LDS-DMA staging on another tile or in place; order 1 / 2 where the launcher's
+ * rule excludes them; a strip on a launch the rule gives none; the in-place form on the 64 x 64 tile or with m != 128) returns
+ * GMB_EINVAL and launches nothing.  *launched (may be NULL) = what ran:  bits 0-1 variant | bit 2 LDS-DMA | bit 3 C prefetch |
+ * bit 4 in place | bits 5-6 order | bits 8-15 strip | bits 16-30 grid size (saturating at 0x7fff); 0 when nothing was launched. */
+typedef struct gmb_gemm_desc {
+  int64_t ldc, lda, ldb, m, n, k;   /* m, n multiples of 128, k of 16 */
+  double alpha, beta;
+  int32_t tri, tri_off;             /* tri_off in elements (a multiple of 32) */
+  int32_t nblk_stride, cblk_stride;
+  int32_t klo_m, klo_n, khi_n, krow_off, krow_stride;
+  int32_t variant;                  /* -1 = the launch model's choice; 0 = 128 x 128, 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 32 */
+  int32_t staging;                  /* -1 = engine default; 0 = register-staged; 1 = LDS-DMA (variant 0 only) */
+  int32_t pfc;                      /* -1 = by the launcher's rule (beta != 0, k <= 1024, out of place); 0 / 1 = pin */
+  int32_t order;                    /* -1 = by the rule; 0 / 1 / 2 = pin */
+  int32_t strip;                    /* -1 = by the rule; >= 0 = pin (m-tiles per strip, <= 255) */
+} gmb_gemm_desc;
+int gmb_blk_gemm_ex(gmb_engine* e, double* C, const double* A, const double* B, const gmb_gemm_desc* d,
+                    int32_t* launched);
 /* -- ONE GP over the GPUs of a node (no reference counterpart -- the reference is
  * single-process; the work replaced is what pm.find_MAP / Marginal.predict do per evaluation,
  * pymc/GP.py:811, 845-847) -------------------------------------------------------------------------------

@@ -46,6 +46,12 @@ def test_struct_layouts_match_header():
     assert engine.C.sizeof(engine.Timings) == 8 * len(fields) == 56 * 8
     # gmb_comm {int32 rank, world; void* ctx; fn* all_gather} and gmb_dist_step {9 x int32, pad, int64}
     assert engine.C.sizeof(engine.GmbComm) == 24 and engine.C.sizeof(engine.DistStep) == 48
+    # gmb_gemm_desc {6 x int64, 2 x double, 14 x int32}: names and order as in the header
+    body = re.search(r"typedef struct gmb_gemm_desc \{(.*?)\} gmb_gemm_desc;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n.strip() for decl in re.findall(r"\b(?:double|int64_t|int32_t)\s+([a-z_0-9, ]+);", body) for n in decl.split(",")]
+    assert names == [n for n, _ in engine.GemmDesc._fields_]
+    assert engine.C.sizeof(engine.GemmDesc) == 6 * 8 + 2 * 8 + 14 * 4
     spec = engine.KernelSpec(D=6, idx_cont=[0, 1, 2], idx_lin=[1], coreg=[(3, 4)], out_col=5, n_out=2)
     cs = spec.to_c()
     assert (cs.n_cont, cs.n_lin, cs.n_coreg, cs.out_col, cs.n_out, cs.hetero_noise) == (3, 1, 1, 5, 2, 1)
