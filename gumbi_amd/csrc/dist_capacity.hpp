@@ -126,6 +126,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   e->factor_kind = gmb_engine::FK_CAPACITY;
   e->factor_consumed = false;
   e->have_alpha = false;
+  e->bs_valid = false;
   e->notpd = -1;
   e->own_world = G;
   e->own_rank = rank;

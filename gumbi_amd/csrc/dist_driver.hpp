@@ -360,6 +360,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   e->factor_kind = gmb_engine::FK_REPLICATED;
   e->factor_consumed = false;
   e->have_alpha = false;
+  e->bs_valid = false;
   e->notpd = -1;
   tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
   tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;

@@ -39,6 +39,7 @@
 #include "eval_tiles.hpp"
 #include "predict_form.hpp"
 #include "joint_predict.hpp"
+#include "predict_grad.hpp"
 
 using namespace gmb;
 
@@ -62,8 +63,13 @@ enum EvKind : int {
   EV_CHOL_UPDATE = 7,       // Cholesky: bulk trailing update
   EV_CHOL_TILES = 8,        // the persistent tile Cholesky, whole matrix
   EV_EVAL_TILES = 9,        // the persistent evaluation launch
-  EV_CHOL_TILES_PANEL = 10  // the tile kernel on a panel at the recursion's bottom
+  EV_CHOL_TILES_PANEL = 10, // the tile kernel on a panel at the recursion's bottom
+  // (ABI 14) launches that are no products: logged to GMB_TRACE_FILE while profiling, counted in no field of gmb_timings
+  EV_PREDICT_COV = 11,        // a prediction's cross-covariance launch K(X*, X) (first term)
+  EV_PREDICT_GRAD = 12,       // gmb_predict_grad: the partial + finishing launches of one term
+  EV_PREDICT_GRAD_ALPHA = 13  // gmb_predict_grad: the back substitution for alpha
 };
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || k == EV_PREDICT_GRAD || k == EV_PREDICT_GRAD_ALPHA; }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -183,6 +189,20 @@ struct gmb_engine {
   double* dmean = nullptr;
   double* dvar = nullptr;
   int64_t cap_part = 0;
+  // gmb_predict_grad (predict_grad.hpp): workspaces of its own -- a prediction's (Mt x Np and friends) stay as they are --
+  // and alpha by back substitution for the states in which no gradient evaluation left one (`have_alpha` false); `bs_valid`
+  // falls wherever the factorisation does
+  double* pg_Xs = nullptr;
+  double* pg_xs = nullptr;
+  double* pg_xl = nullptr;
+  int32_t* pg_cat = nullptr;
+  double* pg_grad = nullptr;
+  int64_t pg_cap = 0;
+  double* pg_part = nullptr;
+  int64_t cap_pg_part = 0;
+  double* dalpha_bs = nullptr;  // Np: alpha, then Np: the running right-hand side
+  int64_t cap_alpha_bs = 0;
+  bool bs_valid = false;
 
   // gradient workspace
   double* dW = nullptr;  // Np x Np column-major: L^-1 then Sigma^-1
@@ -492,7 +512,7 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
     float t = 0.f;
     (void)hipEventElapsedTime(&t, p.a, p.b);
     if (trace) fprintf(trace, "%d %d %d %d %d %.5f %.1f\n", (int)p.kind, p.mt, p.nt, p.k, p.flags, t, p.flops / 1e9);
-    if (p.kind != EV_LEAF && p.kind != EV_CHOL_STRIP && p.kind != EV_SOLVE_STRIP) {  // every product and persistent launch
+    if (p.kind != EV_LEAF && p.kind != EV_CHOL_STRIP && p.kind != EV_SOLVE_STRIP && !ev_trace_only(p.kind)) {  // every product and persistent launch
       e->tm.total_gemm_ms += t;
       e->tm.total_gemm_flops += p.flops;
       e->tm.total_gemm_launches += 1;
@@ -559,6 +579,9 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
         e->tm.grad_gemm_flops += p.flops;
         break;
       case EV_SOLVE_STRIP: break;
+      case EV_PREDICT_COV:
+      case EV_PREDICT_GRAD:
+      case EV_PREDICT_GRAD_ALPHA: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -2401,7 +2424,8 @@ void gmb_destroy(gmb_engine* e) {
                   e->dnoise, e->dscal, e->dv, e->dV, e->dXs, e->txs, e->txl,
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
                   e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
-                  e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage};
+                  e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage,
+                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int a = 0; a < 3; ++a)
@@ -2445,6 +2469,8 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   HIP_TRY(e, hipSetDevice(e->device));
   // not ready until every allocation below has succeeded; workspaces sized for the previous N / D are dropped
   e->factored = false;
+  e->bs_valid = false;
+  e->pg_cap = 0;
   e->factor_kind = gmb_engine::FK_NONE;  // (no factorisation of THIS data has been attempted: gmb_debug_assume_factored must refuse)
   e->have_theta = false;
   e->N = 0;
@@ -2490,6 +2516,7 @@ int gmb_set_y(gmb_engine* e, const double* y, int32_t memspace) {
   HIP_TRY(e, hipSetDevice(e->device));
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   e->factored = false;  // the y row of the factor (v = L^-1 y) belongs to the old observations
+  e->bs_valid = false;
   e->factor_kind = gmb_engine::FK_NONE;
   HIP_TRY(e, hipMemcpyAsync(e->dy, y, e->N * sizeof(double), kind, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller may reuse its buffer
@@ -2504,6 +2531,7 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->have_spec = true;
   e->have_theta = false;
   e->factored = false;
+  e->bs_valid = false;
   e->factor_kind = gmb_engine::FK_NONE;
   e->nc_pad = pick_nc(spec->n_cont);
   e->periodic = 0;
@@ -2533,6 +2561,7 @@ int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t
   // the prepared coordinates and everything factored from them belong to the previous feature map
   e->have_theta = false;
   e->factored = false;
+  e->bs_valid = false;
   e->factor_kind = gmb_engine::FK_NONE;
   e->u_valid = e->linv_valid = false;
   return GMB_OK;
@@ -2549,6 +2578,7 @@ int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) {
   HIP_TRY(e, hipSetDevice(e->device));
   e->theta.assign(theta, theta + n);
   e->factored = false;
+  e->bs_valid = false;
   e->factor_kind = gmb_engine::FK_NONE;
   int rc = apply_theta(e);
   if (rc) return rc;
@@ -2622,6 +2652,7 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   e->factor_kind = gmb_engine::FK_SINGLE;
   e->factor_consumed = false;
   e->have_alpha = false;
+  e->bs_valid = false;
   e->u_valid = e->linv_valid = false;
   e->notpd = -1;
   if ((rc = ensure_factor_buffer(e))) return rc;
@@ -2874,7 +2905,10 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     a.ti = (int)(mpad / TILE);
     a.tj = (int)(e->Np / TILE);
     a.mode = COV_CROSS;
-    if ((rc = launch_cov(e, a))) return rc;
+    ev_begin(e, e->stream, EV_PREDICT_COV, 0.0, a.ti, a.tj);  // (while profiling: the launch on its own in GMB_TRACE_FILE)
+    rc = launch_cov(e, a);
+    ev_end(e);
+    if (rc) return rc;
   }
   KssArgs k{};
   k.p = e->cp;
@@ -3147,6 +3181,129 @@ int launch_draw(gmb_engine* e, const DrawArgs& a) {
   return GMB_OK;
 }
 
+// ---- gradient of the posterior mean (predict_grad.hpp) ----------------------------------------------------------------------------
+
+template <int KIND, bool GEN>
+void launch_predict_grad_nc(gmb_engine* e, const PredGradArgs& a, dim3 grid) {
+  const dim3 block(256);
+  switch (e->nc_pad) {
+    case 1: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 1, GEN>), grid, block, 0, e->stream, a); break;
+    case 2: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 2, GEN>), grid, block, 0, e->stream, a); break;
+    case 4: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 4, GEN>), grid, block, 0, e->stream, a); break;
+    case 8: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 8, GEN>), grid, block, 0, e->stream, a); break;
+    default: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 16, GEN>), grid, block, 0, e->stream, a); break;
+  }
+}
+
+// one term's partials for the prepared test points in pg_xs / pg_xl / pg_cat (dispatched as launch_cov dispatches the tiles)
+int launch_predict_grad(gmb_engine* e, const PredGradArgs& a, int nchunk) {
+  const dim3 grid((unsigned)(a.test.npad / PG_PTS), (unsigned)nchunk);
+  const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
+  switch (a.p.kind) {
+    case GMB_EXPQUAD: gen ? launch_predict_grad_nc<0, true>(e, a, grid) : launch_predict_grad_nc<0, false>(e, a, grid); break;
+    case GMB_MATERN52: gen ? launch_predict_grad_nc<1, true>(e, a, grid) : launch_predict_grad_nc<1, false>(e, a, grid); break;
+    case GMB_MATERN32: gen ? launch_predict_grad_nc<2, true>(e, a, grid) : launch_predict_grad_nc<2, false>(e, a, grid); break;
+    case GMB_MATERN12: gen ? launch_predict_grad_nc<3, true>(e, a, grid) : launch_predict_grad_nc<3, false>(e, a, grid); break;
+    case GMB_EXPONENTIAL: gen ? launch_predict_grad_nc<4, true>(e, a, grid) : launch_predict_grad_nc<4, false>(e, a, grid); break;
+    default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// alpha = L^-T v into dalpha_bs by blocked back substitution against the resident factor (lower triangle of dA, diagonal tiles
+// in place: the state every caller has checked -- complete single-engine factor, not consumed)
+int backsub_alpha(gmb_engine* e) {
+  int rc;
+  if ((rc = ensure(e, &e->dalpha_bs, &e->cap_alpha_bs, 2 * e->Np))) return rc;
+  double* alpha = e->dalpha_bs;
+  double* w = e->dalpha_bs + e->Np;
+  const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
+  const int nb = (int)(e->Np / TILE);
+  ev_begin(e, e->stream, EV_PREDICT_GRAD_ALPHA, (double)e->N * (double)e->N, nb);
+  HIP_TRY(e, hipMemcpyAsync(w, e->dv, e->N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  for (int b = nb - 1; b >= 0; --b) {
+    hipLaunchKernelGGL(backsub_diag_kernel, dim3(1), dim3(256), 0, e->stream, L, (int64_t)b, e->N, w, alpha);
+    if (b > 0) hipLaunchKernelGGL(backsub_update_kernel, dim3((unsigned)(32 * b)), dim3(256), 0, e->stream, L, (int64_t)b, e->N, alpha, w);
+  }
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  e->bs_valid = true;
+  return GMB_OK;
+}
+
+// workspaces of gmb_predict_grad for M-tiles of Mt rows (a multiple of 128)
+int predict_grad_workspace(gmb_engine* e, int64_t Mt) {
+  int rc;
+  if (e->pg_cap < Mt) {
+    e->pg_cap = 0;
+    if ((rc = alloc(e, &e->pg_Xs, Mt * (int64_t)e->D))) return rc;
+    if ((rc = alloc(e, &e->pg_xs, (int64_t)17 * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_xl, (int64_t)MAX_LIN * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_cat, (int64_t)MAX_TABS * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_grad, Mt * (int64_t)e->D))) return rc;
+    e->pg_cap = Mt;
+  }
+  // every M-tile of mpad <= Mt rows runs nchunk <= PG_TARGET_WGS / (mpad / 64) + 1 chunks (predict_grad_chunk), so its partials
+  // -- nchunk x (nc_pad + n_lin) x mpad doubles -- fit in this whatever its size
+  const int64_t need = ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
+  return ensure(e, &e->pg_part, &e->cap_pg_part, need);
+}
+
+// d mu / d x* of one M-tile (mc points, first row Xs) into pg_grad (mc x D, row-major)
+int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, const double* alpha, hipMemcpyKind in_kind) {
+  int rc;
+  HIP_TRY(e, hipMemcpy2DAsync(e->pg_Xs, e->D * sizeof(double), Xs, ldxs * sizeof(double), e->D * sizeof(double), mc, in_kind, e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->pg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  int64_t chunk;
+  int nchunk;
+  predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
+  const PointSet test{e->pg_xs, e->pg_xl, e->pg_cat, mc, mpad};
+  for (size_t t = 0; t < e->terms.size(); ++t) {
+    const gmb_engine::Term& tr = e->terms[t];
+    // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
+    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, e->pg_Xs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
+    PredGradArgs a{};
+    a.p = tr.cp;
+    a.test = test;
+    a.train = train_set(e);
+    a.alpha = alpha;
+    a.part = e->pg_part;
+    a.chunk = chunk;
+    ev_begin(e, e->stream, EV_PREDICT_GRAD, 0.0, (int)(mpad / PG_PTS), nchunk);
+    rc = launch_predict_grad(e, a, nchunk);
+    if (!rc) {
+      PredGradFinishArgs f{};
+      f.part = e->pg_part;
+      f.nchunk = nchunk;
+      f.nc = tr.pa.nc;
+      f.nc_pad = e->nc_pad;
+      f.n_lin = tr.cp.n_lin;
+      f.periodic = tr.pa.periodic;
+      f.D = e->D;
+      f.mpad = mpad;
+      f.mc = mc;
+      f.txs = e->pg_xs;
+      for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k];
+      if (tr.pa.periodic) {
+        for (int d = 0; 2 * d < tr.pa.nc; ++d) f.scale[d] = 2.0 * M_PI * tr.pa.two_over_T[d];  // 2 * (2 pi / T_d)
+      } else {
+        for (int k = 0; k < tr.pa.nc; ++k) f.scale[k] = 2.0 * tr.pa.inv_ls[k];
+      }
+      for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
+      f.tau = tr.cp.tau;
+      f.grad = e->pg_grad;
+      hipLaunchKernelGGL(predict_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, f);
+    }
+    ev_end(e);
+    if (rc) return rc;
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+  return GMB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3204,6 +3361,39 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   tm.predict_ms = tp.ms();
   ev_collect(e);
+  return GMB_OK;
+}
+
+int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_predict_grad");
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !grad)) || ldxs < e->D || ldg < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/grad/ldg");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  // 16384 points per tile: 256 blocks of 64, i.e. four chunks of the training set -- partials of 4 x the tile's gradient
+  const int64_t Mt = std::min<int64_t>(round_up(M, TILE), 16384);
+  if ((rc = predict_grad_workspace(e, Mt))) return rc;
+  // alpha: the gradient evaluation's (refined against L) when one is resident, else by back substitution, once per factorisation
+  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) {
+    ev_collect(e);
+    return rc;
+  }
+  const double* alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
+  const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const hipMemcpyKind out_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+    const int64_t mc = std::min<int64_t>(Mt, M - m0);
+    if ((rc = predict_grad_tile(e, Xs + m0 * ldxs, mc, round_up(mc, TILE), ldxs, alpha, in_kind))) break;
+    if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg_grad, e->D * sizeof(double), e->D * sizeof(double), mc, out_kind,
+                         e->stream) != hipSuccess) {
+      rc = fail(e, GMB_EHIP, "gmb_predict_grad: copying the gradient out failed");
+      break;
+    }
+  }
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  ev_collect(e);
+  if (rc) return rc;
+  HIP_TRY(e, sync);
   return GMB_OK;
 }
 
@@ -3751,6 +3941,7 @@ int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
   const int old = e->dist_mode;
   if (old != mode) {
     e->factored = false;
+    e->bs_valid = false;
     e->factor_kind = gmb_engine::FK_NONE;
   }
   e->dist_mode = mode;
@@ -3763,6 +3954,7 @@ int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
       e->dA = nullptr;
       e->cap_A = 0;
       e->factored = false;
+      e->bs_valid = false;
       e->factor_kind = gmb_engine::FK_NONE;
     }
   }

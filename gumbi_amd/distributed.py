@@ -355,6 +355,10 @@ class DistributedEngine:
             self._raise_transport()
             raise
 
+    def predict_grad(self, Xs):
+        raise NotImplementedError("predict_grad: the posterior mean's gradient is not built for distributed GPs (gmb_predict_grad "
+                                  "needs the complete factor of a single-engine factorisation)")
+
     # -- introspection: the resident state is replicated, the single-engine accessors apply ------------
     def notpd_index(self):
         return self.eng.notpd_index()

@@ -286,6 +286,7 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_int64, C.c_int32]),
     "gmb_draw_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                  C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    "gmb_predict_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
     "gmb_ls_limits": (C.c_int, [C.c_int32, _DBL_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_peak": (C.c_int, [C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_sustained": (C.c_int, [C.c_int32, C.c_double, _DBL_P, _DBL_P, _DBL_P, C.POINTER(C.c_int64)]),
@@ -369,8 +370,8 @@ def _preload_hip_runtime():
 #: version 10 ``gmb_set_predict_form`` (GEMM-form prediction behind a fit), ``total_chol_update_all_*`` / ``predict_gemm_form`` in
 #: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
 #: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``; version 13 the GEMM test door
-#: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``)
-ABI_VERSION = 13
+#: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``; version 14 the posterior mean's gradient ``gmb_predict_grad``)
+ABI_VERSION = 14
 
 
 def load_library():
@@ -595,6 +596,18 @@ class Engine:
             "gmb_draw_joint",
         )
         return (Y, mean) if return_mean else Y
+
+    def predict_grad(self, Xs):
+        """Gradient of the posterior mean with respect to the test point at the rows of ``Xs``: ``(M, D)``, one column per
+        column of ``X`` -- the kernel's continuous columns carry the derivative, every other column 0 (``gmb_predict_grad``).
+        Needs the resident factor as ``predict`` does and leaves it, and everything a fit left beside it, untouched."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        grad = np.empty((M, self.D), dtype=np.float64)
+        self._check(self._lib.gmb_predict_grad(self._h, _ptr(Xs), M, self.D, _ptr(grad), self.D, GMB_HOST), "gmb_predict_grad")
+        return grad
 
     def predict_device(self, xs_ptr: int, M: int, ldxs: int, mean_ptr: int, var_ptr: int, with_noise=True):
         self._check(

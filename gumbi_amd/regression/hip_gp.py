@@ -33,6 +33,7 @@ from math import lgamma
 import numpy as np
 
 from ..aggregation import DataSet
+from ..arrays import ParameterArray as parray
 from ..engine import KERNEL_KINDS, MAX_PERIODIC_DIMS, Engine, KernelSpec, resolve_kernel_name
 from . import icm
 from ..utils.gp_utils import get_ls_prior
@@ -529,6 +530,59 @@ class HipGP(Regressor):
         if self.MAP is None or self.engine is None:
             raise ValueError("The model must be fit (find_MAP) before predicting")
         return self.engine.predict(np.asarray(points_array, dtype=np.float64), with_noise=with_noise)
+
+    # -- slope of the fitted surface --------------------------------------------------------------------------------------------
+    def predict_grad(self, points_array, additive_level="total"):
+        """Gradient of the posterior mean with respect to the standardized points, ``(M, D)`` with one column per model
+        dimension in ``dims`` order (categorical columns and the output index: 0) -- the reference's autograd pass
+        (botorch/GP.py:535-576) in closed form: one call into ``gmb_predict_grad`` against the factor left resident by
+        :meth:`find_MAP`."""
+        if additive_level != "total":
+            raise NotImplementedError("Prediction for additive sublevels is not yet supported.")
+        if self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before predicting")
+        return self.engine.predict_grad(np.asarray(points_array, dtype=np.float64))
+
+    def predict_points_grad(self, points, output=None, norm=True):
+        """Slope of the fitted surface at a 1-D parray of points (reference botorch/GP.py:579-622): a parray with one layer
+        ``δ[{y}]/δ[{x}]`` per output and continuous dimension, or, with ``norm=True``, one layer ``|∇|{y}`` per output (the
+        Euclidean norm over the continuous dimensions).
+
+        The slope is taken in the TRANSFORMED space: the standardized gradient times ``σ_y / σ_x`` of the standardizer.  As
+        in the reference, log (or logit) transforms of inputs or outputs are NOT unwound -- for a log-transformed variable
+        the layer is the slope with respect to (or of) its logarithm."""
+        output = self._parse_prediction_output(output)
+        points_array, tall, param_coords = self._prepare_points_for_prediction(points, output=output)
+        grad_z = self.predict_grad(points_array)
+        task = tall[self.out_col].values().squeeze() if param_coords is not None else None
+        partials = {}
+        for i, y_var in enumerate(output):
+            rows = grad_z if task is None else grad_z[np.atleast_1d(task == param_coords[i])]
+            σy = np.sqrt(self.stdzr[y_var]["σ2"])
+            for x_var in self.continuous_dims:
+                σx = np.sqrt(self.stdzr[x_var]["σ2"])
+                partials[f"δ[{y_var}]/δ[{x_var}]"] = rows[:, self.dims.index(x_var)] * σy / σx
+        grad = self.parray(**partials)
+        return self._get_pgrad_norm(grad) if norm else grad
+
+    def predict_grid_grad(self, output=None, categorical_levels=None, norm=True):
+        """:meth:`predict_points_grad` on the grid :meth:`prepare_grid` left behind, in the grid's shape (reference
+        botorch/GP.py:625-633)."""
+        if self.grid_points is None:
+            raise ValueError("Grid must first be specified with `prepare_grid`")
+        points = self.grid_points
+        if self.categorical_dims:
+            points = self.append_categorical_points(points, categorical_levels=categorical_levels)
+        return self.predict_points_grad(points, output=output, norm=norm).reshape(self.grid_parray.shape)
+
+    @staticmethod
+    def _get_pgrad_norm(pgrad):
+        """``|∇|{y}`` per output from the layers ``δ[{y}]/δ[{x}]`` of ``pgrad``."""
+        by_output = {}
+        for name in pgrad.names:
+            by_output.setdefault(name.split("/")[0].removeprefix("δ[").removesuffix("]"), []).append(name)
+        norms = {f"|∇|{y}": np.sqrt(sum(np.square(pgrad[name].values()) for name in names)) for y, names in by_output.items()}
+        return parray(**norms, stdzr=pgrad.stdzr)
 
     # -- joint posterior: covariance and draws ---------------------------------------------------------------------------------
     def _joint_engine(self, additive_level, what):

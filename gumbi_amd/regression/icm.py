@@ -269,6 +269,26 @@ class IcmEngine:
             var += st["sigma"] ** 2 * st["bn"][task]
         return mean, var
 
+    def predict_grad(self, Xs):
+        """Gradient of the posterior mean at the rows of ``Xs``, ``(M, D)``: the Kronecker mean is a fixed linear combination
+        of the P systems' means (:meth:`predict`), so its gradient is the same combination of their gradients; the output
+        column gets 0."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.spec.D:
+            raise ValueError(f"points_array must be (M, {self.spec.D}), got {Xs.shape}")
+        st = self._decompose()
+        M = len(Xs)
+        grad = np.zeros((M, self.spec.D))
+        if M == 0:
+            return grad
+        task = Xs[:, -1].astype(np.int64)
+        x = np.ascontiguousarray(Xs[:, :-1])
+        Q, Dd = st["Q"], st["Dd"]
+        for p in range(self.P):
+            grad[:, :-1] += Q[task, p][:, None] * self._load(p, st).predict_grad(x)
+        grad[:, :-1] *= np.sqrt(Dd[task])[:, None]
+        return grad
+
     def factor_is_current(self):
         """True when every system's factor for the current theta is resident (one engine per system)."""
         if not self._per_system or self._state is None:

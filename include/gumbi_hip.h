@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 13
+#define GMB_ABI_VERSION 14
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -289,6 +289,20 @@ int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, 
  * (gumbi/regression/pymc/GP.py:914-917: draw_point_samples / draw_grid_samples). */
 int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
                    const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace);
+
+/* (ABI 14) Gradient of the posterior mean with respect to the test point, d mu / d x*, at M points (csrc/predict_grad.hpp) --
+ * replaces the autograd pass of the reference's `predict_grad` through its GPyTorch model (gumbi/regression/botorch/GP.py:535-576).
+ * In closed form from the prepared coordinates, the factor and alpha = Sigma^-1 y: O(M N d) work in one fused launch per model
+ * term, nothing of size M x N is written.  `grad` is M x D row-major with leading dimension ldg >= D, in the memspace of Xs;
+ * EVERY column is written: the continuous (and linear) columns of the kernel with the derivative, all others -- categorical
+ * columns, the output index -- with 0.  Periodic models differentiate through their warp; additive models sum their terms.
+ * Matern-1/2 and Exponential keep PyMC's sqrt(r^2 + 1e-12): their gradient is smooth and 0 at a coincident point.
+ * Readiness as gmb_predict (a valid, unconsumed, complete single-engine factor); GMB_EINVAL for bad arguments (ldg < D, ldxs < D),
+ * engines with a multi-GPU factorisation (gmb_dist_*) and capacity mode; M == 0 is GMB_OK.  Behind a gradient evaluation
+ * (gmb_evaluate / gmb_nlml with grad) it uses that evaluation's alpha; behind a bare gmb_factorize it solves L^T alpha = v once per
+ * factorisation by blocked back substitution into a buffer of its own.  The factor, v, alpha (gmb_copy_alpha), the inverse
+ * factor, gmb_factor_valid and the joint state are left as found; the same bits call after call.  M is tiled (16384 rows). */
+int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace);
 
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
