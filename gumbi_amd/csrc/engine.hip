@@ -40,6 +40,7 @@
 #include "predict_form.hpp"
 #include "joint_predict.hpp"
 #include "predict_grad.hpp"
+#include "predict_var_grad.hpp"
 
 using namespace gmb;
 
@@ -67,9 +68,12 @@ enum EvKind : int {
   // (ABI 14) launches that are no products: logged to GMB_TRACE_FILE while profiling, counted in no field of gmb_timings
   EV_PREDICT_COV = 11,        // a prediction's cross-covariance launch K(X*, X) (first term)
   EV_PREDICT_GRAD = 12,       // gmb_predict_grad: the partial + finishing launches of one term
-  EV_PREDICT_GRAD_ALPHA = 13  // gmb_predict_grad: the back substitution for alpha
+  EV_PREDICT_GRAD_ALPHA = 13, // gmb_predict_grad: the back substitution for alpha
+  // (ABI 15)
+  EV_PREDICT_VGRAD = 14,      // gmb_predict_with_grad: the fused partial + finishing launches of one term
+  EV_PREDICT_VGRAD_SOLVE = 15 // gmb_predict_with_grad: the second triangular pass W = V L^-1 of one M-tile
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || k == EV_PREDICT_GRAD || k == EV_PREDICT_GRAD_ALPHA; }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_PREDICT_VGRAD_SOLVE); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -203,6 +207,11 @@ struct gmb_engine {
   double* dalpha_bs = nullptr;  // Np: alpha, then Np: the running right-hand side
   int64_t cap_alpha_bs = 0;
   bool bs_valid = false;
+  // gmb_predict_with_grad (predict_var_grad.hpp): the variance gradient of an M-tile and the doubled partials
+  double* vg_grad = nullptr;
+  int64_t cap_vg_grad = 0;
+  double* vg_part = nullptr;
+  int64_t cap_vg_part = 0;
 
   // gradient workspace
   double* dW = nullptr;  // Np x Np column-major: L^-1 then Sigma^-1
@@ -581,7 +590,9 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_SOLVE_STRIP: break;
       case EV_PREDICT_COV:
       case EV_PREDICT_GRAD:
-      case EV_PREDICT_GRAD_ALPHA: break;
+      case EV_PREDICT_GRAD_ALPHA:
+      case EV_PREDICT_VGRAD:
+      case EV_PREDICT_VGRAD_SOLVE: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -2425,7 +2436,7 @@ void gmb_destroy(gmb_engine* e) {
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
                   e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
                   e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage,
-                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs};
+                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->vg_part};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int a = 0; a < 3; ++a)
@@ -3304,6 +3315,123 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
   return GMB_OK;
 }
 
+// ---- gradients of mean and variance in one call (predict_var_grad.hpp) -------------------------------------------------------------
+
+template <int KIND, bool GEN>
+void launch_predict_var_grad_nc(gmb_engine* e, const PredVarGradArgs& a, dim3 grid) {
+  const dim3 block(256);
+  switch (e->nc_pad) {
+    case 1: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 1, GEN>), grid, block, 0, e->stream, a); break;
+    case 2: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 2, GEN>), grid, block, 0, e->stream, a); break;
+    case 4: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 4, GEN>), grid, block, 0, e->stream, a); break;
+    case 8: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 8, GEN>), grid, block, 0, e->stream, a); break;
+    default: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 16, GEN>), grid, block, 0, e->stream, a); break;
+  }
+}
+
+int launch_predict_var_grad(gmb_engine* e, const PredVarGradArgs& a, int nchunk) {
+  const dim3 grid((unsigned)(a.test.npad / PG_PTS), (unsigned)nchunk);
+  const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
+  switch (a.p.kind) {
+    case GMB_EXPQUAD: gen ? launch_predict_var_grad_nc<0, true>(e, a, grid) : launch_predict_var_grad_nc<0, false>(e, a, grid); break;
+    case GMB_MATERN52: gen ? launch_predict_var_grad_nc<1, true>(e, a, grid) : launch_predict_var_grad_nc<1, false>(e, a, grid); break;
+    case GMB_MATERN32: gen ? launch_predict_var_grad_nc<2, true>(e, a, grid) : launch_predict_var_grad_nc<2, false>(e, a, grid); break;
+    case GMB_MATERN12: gen ? launch_predict_var_grad_nc<3, true>(e, a, grid) : launch_predict_var_grad_nc<3, false>(e, a, grid); break;
+    case GMB_EXPONENTIAL: gen ? launch_predict_var_grad_nc<4, true>(e, a, grid) : launch_predict_var_grad_nc<4, false>(e, a, grid); break;
+    default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// workspaces of gmb_predict_with_grad for M-tiles of Mt rows, beside a prediction's and gmb_predict_grad's
+int predict_var_grad_workspace(gmb_engine* e, int64_t Mt) {
+  int rc;
+  if ((rc = predict_workspace(e, Mt))) return rc;
+  if ((rc = predict_grad_workspace(e, Mt))) return rc;
+  if ((rc = ensure(e, &e->vg_grad, &e->cap_vg_grad, Mt * (int64_t)e->D))) return rc;
+  // two accumulator sets: twice predict_grad_workspace's bound
+  const int64_t need = 2 * ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
+  return ensure(e, &e->vg_part, &e->cap_vg_part, need);
+}
+
+// W <- V L^-1 in dV (mpad rows, test index fastest) against the resident factor: block columns from the last
+int predict_solve_w(gmb_engine* e, int64_t mpad) {
+  const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
+  const int nb = (int)(e->Np / TILE);
+  ev_begin(e, e->stream, EV_PREDICT_VGRAD_SOLVE, (double)mpad * (double)e->N * (double)e->N, (int)(mpad / TILE), nb);
+  for (int b = nb - 1; b >= 0; --b) {
+    hipLaunchKernelGGL(vsolve_diag_kernel, dim3((unsigned)(mpad / VS_ROWS)), dim3(VS_ROWS), 0, e->stream, L, (int64_t)b, e->N, e->dV, mpad);
+    if (b > 0)
+      hipLaunchKernelGGL(vsolve_update_kernel, dim3((unsigned)(mpad / VS_PTS), (unsigned)b), dim3(256), 0, e->stream, L, (int64_t)b, e->N,
+                         e->dV, mpad);
+  }
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// d mu / d x* and d sigma^2 / d x* of one M-tile into pg_grad and vg_grad (mc x D, row-major): the tile's raw points are in dXs
+// (predict_cross_cov), W = K(X*, X) Sigma^-1 in dV
+int predict_var_grad_tile(gmb_engine* e, int64_t mc, int64_t mpad, const double* alpha) {
+  int rc;
+  HIP_TRY(e, hipMemsetAsync(e->pg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->vg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  int64_t chunk;
+  int nchunk;
+  predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
+  const PointSet test{e->pg_xs, e->pg_xl, e->pg_cat, mc, mpad};
+  for (size_t t = 0; t < e->terms.size(); ++t) {
+    const gmb_engine::Term& tr = e->terms[t];
+    // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
+    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
+    PredVarGradArgs a{};
+    a.p = tr.cp;
+    a.test = test;
+    a.train = train_set(e);
+    a.alpha = alpha;
+    a.W = e->dV;
+    a.part = e->vg_part;
+    a.chunk = chunk;
+    ev_begin(e, e->stream, EV_PREDICT_VGRAD, 0.0, (int)(mpad / PG_PTS), nchunk);
+    rc = launch_predict_var_grad(e, a, nchunk);
+    if (!rc) {
+      PredVarGradFinishArgs v{};
+      PredGradFinishArgs& f = v.f;
+      f.part = e->vg_part;
+      f.nchunk = nchunk;
+      f.nc = tr.pa.nc;
+      f.nc_pad = e->nc_pad;
+      f.n_lin = tr.cp.n_lin;
+      f.periodic = tr.pa.periodic;
+      f.D = e->D;
+      f.mpad = mpad;
+      f.mc = mc;
+      f.txs = e->pg_xs;
+      for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k];
+      if (tr.pa.periodic) {
+        for (int d = 0; 2 * d < tr.pa.nc; ++d) f.scale[d] = 2.0 * M_PI * tr.pa.two_over_T[d];  // 2 * (2 pi / T_d)
+      } else {
+        for (int k = 0; k < tr.pa.nc; ++k) f.scale[k] = 2.0 * tr.pa.inv_ls[k];
+      }
+      for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
+      f.tau = tr.cp.tau;
+      f.grad = e->pg_grad;
+      v.dvar = e->vg_grad;
+      v.p = tr.cp;
+      v.txl = e->pg_xl;
+      v.tcat = e->pg_cat;
+      hipLaunchKernelGGL(predict_var_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, v);
+    }
+    ev_end(e);
+    if (rc) return rc;
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+  return GMB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3391,6 +3519,53 @@ int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, d
     }
   }
   const hipError_t sync = hipStreamSynchronize(e->stream);
+  ev_collect(e);
+  if (rc) return rc;
+  HIP_TRY(e, sync);
+  return GMB_OK;
+}
+
+int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
+                          double* dmean, double* dvar, int64_t ldg, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_predict_with_grad");
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !mean || !var || !dmean || !dvar)) || ldxs < e->D || ldg < e->D)
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var/dmean/dvar/ldg");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  gmb_timings& tm = e->tm;
+  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
+  tm.predict_gemm_launches = 0;
+  tm.predict_gemm_form = 0;  // V is always solved for: W = V L^-1 follows in place, and neither dW nor U is touched
+  const int64_t Mt = predict_tile_rows(e, M);
+  if ((rc = predict_var_grad_workspace(e, Mt))) return rc;
+  // alpha as in gmb_predict_grad
+  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) {
+    ev_collect(e);
+    return rc;
+  }
+  const double* alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
+  const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const hipMemcpyKind out_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t row = e->D * sizeof(double);
+  PhaseTimer tp(e);
+  for (int64_t m0 = 0; m0 < M && !rc; m0 += Mt) {
+    const int64_t mc = std::min<int64_t>(Mt, M - m0);
+    const int64_t mpad = round_up(mc, TILE);
+    if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, in_kind))) break;
+    if ((rc = predict_solve_v(e, mpad, false))) break;
+    if ((rc = predict_reduce(e, mc, mpad, false))) break;
+    if ((rc = predict_solve_w(e, mpad))) break;
+    if ((rc = predict_var_grad_tile(e, mc, mpad, alpha))) break;
+    if (hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), out_kind, e->stream) != hipSuccess ||
+        hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), out_kind, e->stream) != hipSuccess ||
+        hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, out_kind, e->stream) != hipSuccess ||
+        hipMemcpy2DAsync(dvar + m0 * ldg, ldg * sizeof(double), e->vg_grad, row, row, mc, out_kind, e->stream) != hipSuccess)
+      rc = fail(e, GMB_EHIP, "gmb_predict_with_grad: copying the results out failed");
+  }
+  tp.stop();
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  if (!rc && sync == hipSuccess) tm.predict_ms = tp.ms();
   ev_collect(e);
   if (rc) return rc;
   HIP_TRY(e, sync);

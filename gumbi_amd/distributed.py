@@ -359,6 +359,10 @@ class DistributedEngine:
         raise NotImplementedError("predict_grad: the posterior mean's gradient is not built for distributed GPs (gmb_predict_grad "
                                   "needs the complete factor of a single-engine factorisation)")
 
+    def predict_with_grad(self, Xs, with_noise=True):
+        raise NotImplementedError("predict_with_grad: the posterior's gradients are not built for distributed GPs "
+                                  "(gmb_predict_with_grad needs the complete factor of a single-engine factorisation)")
+
     # -- introspection: the resident state is replicated, the single-engine accessors apply ------------
     def notpd_index(self):
         return self.eng.notpd_index()

@@ -287,6 +287,8 @@ _SIGNATURES = {
     "gmb_draw_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                  C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "gmb_predict_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_predict_with_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_int32]),
     "gmb_ls_limits": (C.c_int, [C.c_int32, _DBL_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_peak": (C.c_int, [C.c_int32, _DBL_P, _DBL_P]),
     "gmb_mfma_f64_sustained": (C.c_int, [C.c_int32, C.c_double, _DBL_P, _DBL_P, _DBL_P, C.POINTER(C.c_int64)]),
@@ -370,8 +372,9 @@ def _preload_hip_runtime():
 #: version 10 ``gmb_set_predict_form`` (GEMM-form prediction behind a fit), ``total_chol_update_all_*`` / ``predict_gemm_form`` in
 #: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
 #: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``; version 13 the GEMM test door
-#: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``; version 14 the posterior mean's gradient ``gmb_predict_grad``)
-ABI_VERSION = 14
+#: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``; version 14 the posterior mean's gradient ``gmb_predict_grad``; version 15 mean and
+#: variance with both gradients in one call, ``gmb_predict_with_grad``)
+ABI_VERSION = 15
 
 
 def load_library():
@@ -608,6 +611,21 @@ class Engine:
         grad = np.empty((M, self.D), dtype=np.float64)
         self._check(self._lib.gmb_predict_grad(self._h, _ptr(Xs), M, self.D, _ptr(grad), self.D, GMB_HOST), "gmb_predict_grad")
         return grad
+
+    def predict_with_grad(self, Xs, with_noise=True):
+        """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with
+        respect to the test point, ``(M, D)`` each with the columns of :meth:`predict_grad` (``gmb_predict_with_grad``) -- one
+        engine call per evaluation of an acquisition function and its gradient.  ``with_noise`` changes ``var`` only.  Needs
+        the resident factor as ``predict`` does and leaves it, and everything a fit left beside it, untouched."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        mean, var = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.float64)
+        dmean, dvar = np.empty((M, self.D), dtype=np.float64), np.empty((M, self.D), dtype=np.float64)
+        self._check(self._lib.gmb_predict_with_grad(self._h, _ptr(Xs), M, self.D, int(bool(with_noise)), _ptr(mean), _ptr(var),
+                                                    _ptr(dmean), _ptr(dvar), self.D, GMB_HOST), "gmb_predict_with_grad")
+        return mean, var, dmean, dvar
 
     def predict_device(self, xs_ptr: int, M: int, ldxs: int, mean_ptr: int, var_ptr: int, with_noise=True):
         self._check(

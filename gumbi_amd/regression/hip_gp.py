@@ -584,6 +584,122 @@ class HipGP(Regressor):
         norms = {f"|∇|{y}": np.sqrt(sum(np.square(pgrad[name].values()) for name in names)) for y, names in by_output.items()}
         return parray(**norms, stdzr=pgrad.stdzr)
 
+    # -- gradient-based proposal over the continuous inputs ---------------------------------------------------------------------
+    def _acquisition_problem(self, output, acquisition, maximize, categorical_levels, beta):
+        """What :meth:`acquisition_with_grad` and :meth:`propose_continuous` share: the acquisition ``f(mu, var, maximize)``,
+        the continuous dims with their columns of a model point, and ``full(Z)``, which completes (M, n_cont) standardized
+        continuous coordinates to (M, D) points with the fixed columns (categories, the output index)."""
+        from .. import acquisition as acq
+
+        if self.distributed:
+            raise NotImplementedError("the acquisition's gradient is not built for distributed GPs (the factor is spread over ranks)")
+        if self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before proposing")
+        outputs = self._parse_prediction_output(output)
+        if len(outputs) != 1:
+            raise ValueError(f"an acquisition is optimised for ONE output: pass output= one of {outputs}")
+        cont = list(self.continuous_dims)
+        cols = [self.dims.index(d) for d in cont]
+        template = self.parray(**{d: np.array([0.0]) for d in cont}, stdzd=True)
+        if set(self.categorical_dims) - {self.out_col}:
+            if categorical_levels is None:
+                raise AttributeError("Must specify level for every categorical dimension")
+            template = self.append_categorical_points(template, categorical_levels)
+        row, _, _ = self._prepare_points_for_prediction(template, output=outputs)
+        row = np.asarray(row, float)[0]
+
+        def full(Z):
+            P = np.tile(row, (len(Z), 1))
+            P[:, cols] = Z
+            return P
+
+        kwargs = {}
+        if acquisition == "EI":  # the incumbent: the best observed standardized value of this output
+            y = np.asarray(self.model.y, float)
+            if self.out_col in self.categorical_dims:
+                oc = self.dims.index(self.out_col)
+                y = y[np.asarray(self.model.X, float)[:, oc] == row[oc]]
+            kwargs["best"] = float(np.max(y) if maximize else np.min(y))
+        elif beta is not None:
+            kwargs["beta"] = beta
+        return acq.get(acquisition, **kwargs), cont, cols, full
+
+    def acquisition_with_grad(self, points_z, output=None, acquisition="EI", maximize=True, categorical_levels=None, beta=None,
+                              _problem=None):
+        """Acquisition value (M,) and its gradient (M, n_cont) with respect to the STANDARDIZED continuous coordinates
+        ``points_z`` (M, n_cont, in ``continuous_dims`` order), on the noise-free posterior: ONE ``engine.predict_with_grad``
+        call, chained with the acquisition's gradient in (mu, sigma^2).  Larger is better for both settings of ``maximize``
+        (``"EI"`` is log-EI).  This is the objective :meth:`propose_continuous` optimises."""
+        f, cont, cols, full = _problem or self._acquisition_problem(output, acquisition, maximize, categorical_levels, beta)
+        Z = np.asarray(points_z, float).reshape(-1, len(cont))
+        mu, var, dmu, dvar = self.engine.predict_with_grad(full(Z), with_noise=False)
+        value, d_mu, d_var = f(mu, var, maximize)
+        return value, d_mu[:, None] * dmu[:, cols] + d_var[:, None] * dvar[:, cols]
+
+    def propose_continuous(self, output=None, acquisition="EI", maximize=True, bounds=None, categorical_levels=None,
+                           num_restarts=10, raw_samples=512, seed=None, q=1, **optim_kwargs):
+        """Next point to measure by optimising an acquisition function over the CONTINUOUS inputs (the reference's
+        ``BotorchGP.propose``, botorch/GP.py, whose keywords this follows): multi-start L-BFGS-B on analytic ``"EI"`` (in its log
+        form) or ``"UCB"`` (``beta=`` in ``optim_kwargs``, default 2) of the noise-free posterior, in standardized units.
+
+        ``raw_samples`` seeded uniform points inside ``bounds`` are scored in one ``predict`` call and the best
+        ``num_restarts`` become the starts; the restarts are then optimised in lock step -- one ``scipy.optimize.minimize``
+        over their concatenated coordinates with the summed negative acquisition -- and every objective evaluation is ONE
+        ``engine.predict_with_grad`` call at ``M = num_restarts`` (:meth:`acquisition_with_grad`) against the factor
+        :meth:`find_MAP` left resident.
+
+        ``bounds``: a parray with two entries (lower, upper) per continuous dimension; default: the range of the training data.
+        Categorical coordinates are fixed through ``categorical_levels`` (as in :meth:`append_categorical_points`); with
+        several outputs ``output`` names the one to optimise.  The incumbent of EI is the best observed standardized value of
+        that output.  Returns the best candidate -- of the optimised restarts and their starts -- as a parray in natural units
+        and sets :attr:`proposal`, :attr:`proposal_acquisition` (its acquisition value) and :attr:`optimization_bounds`
+        (standardized ``(lower, upper)`` in ``continuous_dims`` order); for diagnosis also :attr:`proposal_result` (scipy's
+        result of the lock-step run) and :attr:`proposal_raw_acquisition` (the raw samples' scores).  Remaining
+        ``optim_kwargs`` go to L-BFGS-B's ``options``."""
+        from scipy.optimize import minimize
+
+        if q != 1:
+            raise NotImplementedError("propose_continuous: q > 1 needs a Monte-Carlo batch acquisition, which is not built")
+        beta = optim_kwargs.pop("beta", None)
+        problem = self._acquisition_problem(output, acquisition, maximize, categorical_levels, beta)
+        f, cont, cols, full = problem
+        num_restarts, raw_samples = int(num_restarts), max(int(raw_samples), int(num_restarts))
+
+        # standardized bounds, one entry per continuous dim
+        if bounds is None:
+            Xc = np.asarray(self.model.X, float)[:, cols]
+            lo, hi = Xc.min(axis=0), Xc.max(axis=0)
+        else:
+            bz = bounds.z
+            both = np.array([np.asarray(bz[d + "_z"].values(), float).ravel() for d in cont])
+            if both.shape != (len(cont), 2):
+                raise ValueError("bounds must hold two entries (lower, upper) per continuous dimension")
+            lo, hi = both.min(axis=1), both.max(axis=1)
+        self.optimization_bounds = (lo.copy(), hi.copy())
+
+        rng = np.random.default_rng(self.seed if seed is None else seed)
+        raw = lo + (hi - lo) * rng.random((raw_samples, len(cont)))
+        mu, var = self.engine.predict(full(raw), with_noise=False)
+        raw_value = f(mu, var, maximize)[0]
+        starts = raw[np.argsort(-raw_value, kind="stable")[:num_restarts]]
+
+        def objective(z):
+            value, grad = self.acquisition_with_grad(z.reshape(num_restarts, len(cont)), maximize=maximize, _problem=problem)
+            return -float(np.sum(value)), -grad.ravel()
+
+        options = {"maxiter": 200, **optim_kwargs.pop("options", {}), **optim_kwargs}
+        res = minimize(objective, starts.ravel(), jac=True, method="L-BFGS-B",
+                       bounds=list(zip(np.tile(lo, num_restarts), np.tile(hi, num_restarts))), options=options)
+        cand = np.clip(np.vstack([res.x.reshape(num_restarts, len(cont)), starts]), lo, hi)
+        mu, var = self.engine.predict(full(cand), with_noise=False)
+        value = f(mu, var, maximize)[0]
+        best = int(np.argmax(value))
+        self.proposal_result = res
+        self.proposal_acquisition = float(value[best])
+        self.proposal_raw_acquisition = raw_value
+        self.proposal = self.parray(**{d: np.array([cand[best, k]]) for k, d in enumerate(cont)}, stdzd=True)
+        return self.proposal
+
     # -- joint posterior: covariance and draws ---------------------------------------------------------------------------------
     def _joint_engine(self, additive_level, what):
         if additive_level != "total":

@@ -289,6 +289,37 @@ class IcmEngine:
         grad[:, :-1] *= np.sqrt(Dd[task])[:, None]
         return grad
 
+    def predict_with_grad(self, Xs, with_noise=True):
+        """``(mean, var, dmean, dvar)`` at the rows of ``Xs`` (``Engine.predict_with_grad``): mean and variance are the fixed
+        combinations of the P systems' of :meth:`predict` -- ``sqrt(Dd) sum_p Q_p mu_p`` and ``Dd sum_p Q_p^2 v_p`` -- so their
+        gradients are the same combinations of the systems' gradients; the output column gets 0, the noise has no gradient."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.spec.D:
+            raise ValueError(f"points_array must be (M, {self.spec.D}), got {Xs.shape}")
+        st = self._decompose()
+        M = len(Xs)
+        mean, var = np.zeros(M), np.zeros(M)
+        dmean, dvar = np.zeros((M, self.spec.D)), np.zeros((M, self.spec.D))
+        if M == 0:
+            return mean, var, dmean, dvar
+        task = Xs[:, -1].astype(np.int64)
+        x = np.ascontiguousarray(Xs[:, :-1])
+        Q, Dd = st["Q"], st["Dd"]
+        for p in range(self.P):
+            m_p, v_p, dm_p, dv_p = self._load(p, st).predict_with_grad(x, with_noise=False)
+            q = Q[task, p]
+            mean += q * m_p
+            var += q ** 2 * v_p
+            dmean[:, :-1] += q[:, None] * dm_p
+            dvar[:, :-1] += (q ** 2)[:, None] * dv_p
+        mean *= np.sqrt(Dd[task])
+        dmean[:, :-1] *= np.sqrt(Dd[task])[:, None]
+        var *= Dd[task]
+        dvar[:, :-1] *= Dd[task][:, None]
+        if with_noise:
+            var += st["sigma"] ** 2 * st["bn"][task]
+        return mean, var, dmean, dvar
+
     def factor_is_current(self):
         """True when every system's factor for the current theta is resident (one engine per system)."""
         if not self._per_system or self._state is None:

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 14
+#define GMB_ABI_VERSION 15
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -303,6 +303,21 @@ int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int
  * factorisation by blocked back substitution into a buffer of its own.  The factor, v, alpha (gmb_copy_alpha), the inverse
  * factor, gmb_factor_valid and the joint state are left as found; the same bits call after call.  M is tiled (16384 rows). */
 int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace);
+
+/* (ABI 15) Posterior mean and variance at M points WITH their gradients with respect to the test point, d mu / d x* and
+ * d sigma^2 / d x* (csrc/predict_var_grad.hpp): what a gradient-based search of an acquisition function needs per evaluation (the
+ * reference's `propose`, gumbi/regression/botorch/GP.py).  mean, var: length M, the values of gmb_predict (solve form); dmean,
+ * dvar: M x D row-major with leading dimension ldg >= D, all four in the memspace of Xs.  EVERY column of dmean and dvar is
+ * written, categorical columns and the output index with 0, nothing beyond column D.  With W = K(X*, X) Sigma^-1 = V L^-1
+ *   d sigma^2 / d x*_d = d k(x*, x*) / d x*_d - 2 sum_n W_mn d k(x*_m, x_n) / d x*_d
+ * (the prior term is 2 tau (x*_l - c_l) F_mm for a linear dimension, 0 otherwise); with_noise changes var, not dvar.  Per M-tile:
+ * the prediction's cross-covariance and triangular solve, a second blocked triangular pass W = V L^-1 in place, and ONE fused
+ * launch per model term for both gradients.  Readiness, refusals and the state contract are gmb_predict_grad's: a complete,
+ * unconsumed single-engine factor; GMB_EINVAL for bad arguments, distributed engines and capacity mode; M == 0 is GMB_OK; the
+ * factor, v, both alphas, the inverse factor and its flags, the joint state and gmb_factor_valid are left as found; the same bits
+ * call after call.  M is tiled as in gmb_predict. */
+int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
+                          double* dmean, double* dvar, int64_t ldg, int32_t memspace);
 
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
