@@ -841,6 +841,22 @@ __global__ __launch_bounds__(128) void extract_v_kernel(const double* L, int64_t
   }
 }
 
+// out[0] = sum_{i < n} log L_ii of a factor whose leading n columns are kept while the rest is factored again (gmb_append /
+// gmb_truncate): the leaves of the re-factored columns then add their own logarithms to it, as they do to a zeroed slot in a whole
+// factorisation.  ONE workgroup of 256 threads: thread t adds i = t, t + 256, ... in ascending order, then a fixed LDS tree.
+__global__ __launch_bounds__(256) void diag_logdet_kernel(const double* L, int64_t ld, int64_t n, double* out) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += log(L[i * (ld + 1)]);
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = red[0];
+}
+
 // ---------------------------------------------------------------------------------------------
 // pairwise-distance extrema for the lengthscale prior (gumbi/utils/gp_utils.py:34-46)
 // ---------------------------------------------------------------------------------------------

@@ -32,6 +32,7 @@
 #include "../../include/gumbi_hip.h"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
+#include "gemm_splitk.hpp"
 #include "gradient.hpp"
 #include "potrf_leaf.hpp"
 #include "trsm_strip.hpp"
@@ -71,9 +72,11 @@ enum EvKind : int {
   EV_PREDICT_GRAD_ALPHA = 13, // gmb_predict_grad: the back substitution for alpha
   // (ABI 15)
   EV_PREDICT_VGRAD = 14,      // gmb_predict_with_grad: the fused partial + finishing launches of one term
-  EV_PREDICT_VGRAD_SOLVE = 15 // gmb_predict_with_grad: the second triangular pass W = V L^-1 of one M-tile
+  EV_PREDICT_VGRAD_SOLVE = 15, // gmb_predict_with_grad: the second triangular pass W = V L^-1 of one M-tile
+  // (ABI 16)
+  EV_SPLITK = 16              // the split-k product's launch pair (gemm_splitk.hpp): flags = slices
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_PREDICT_VGRAD_SOLVE); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_SPLITK); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -170,6 +173,8 @@ struct gmb_engine {
   bool have_alpha = false;       // dalpha holds Sigma^-1 y of the current factorisation
   double* dDiagSave = nullptr;   // the factor's diagonal blocks while the gradient keeps U in their place
   int64_t cap_diag = 0;
+  double* dsk = nullptr;         // partials of the split-k product (gemm_splitk.hpp): [tile][slice][128 * 128]
+  int64_t cap_sk = 0;
   int64_t notpd = -1;
   double logdet = 0.0, vnorm2 = 0.0;
 
@@ -592,7 +597,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_PREDICT_GRAD:
       case EV_PREDICT_GRAD_ALPHA:
       case EV_PREDICT_VGRAD:
-      case EV_PREDICT_VGRAD_SOLVE: break;
+      case EV_PREDICT_VGRAD_SOLVE:
+      case EV_SPLITK: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -2436,7 +2442,7 @@ void gmb_destroy(gmb_engine* e) {
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
                   e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
                   e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage,
-                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->vg_part};
+                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->vg_part, e->dsk};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int a = 0; a < 3; ++a)
@@ -2847,6 +2853,289 @@ int gmb_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlml, do
 }  // extern "C"
 
 namespace {
+
+// ---- the split-k product (gemm_splitk.hpp) and the bordered update of the resident factor (gmb_append / gmb_truncate) ------------
+
+// C = beta C + alpha A B^T on few tiles with a long contraction: the launch pair, partials in the engine's workspace.  `pin` >= 1
+// fixes the number of slices (refused when a slice would be empty), anything else leaves it to splitk_rule; *used = what ran.
+int launch_gemm_splitk(gmb_engine* e, hipStream_t s, SplitKArgs a, int pin, int32_t* used) {
+  if (used) *used = 0;
+  if (a.mt <= 0 || a.nt <= 0 || a.k <= 0) return GMB_OK;
+  const int tiles = splitk_tile_count(a.mt, a.nt, a.tri);
+  if (tiles <= 0) return GMB_OK;
+  if (tiles > 65535) return fail(e, GMB_EINVAL, "split-k GEMM: %d output tiles (at most 65535: it is the kernel for FEW tiles)", tiles);
+  int len = 0, S = pin;
+  if (pin >= 1) {
+    len = splitk_pinned_len(a.k, pin);
+    if (!len) return fail(e, GMB_EINVAL, "split-k GEMM: %d slices of k = %d leave a slice empty", pin, a.k);
+  } else {
+    S = splitk_rule(tiles, a.k, &len);
+  }
+  int rc;
+  if ((rc = ensure(e, &e->dsk, &e->cap_sk, (int64_t)tiles * S * TILE * TILE))) return rc;
+  a.slices = S;
+  a.slice_len = len;
+  a.ws = e->dsk;
+  ev_begin(e, s, EV_SPLITK, 2.0 * TILE * TILE * (double)a.k * tiles, a.mt, a.nt, a.k, S);
+  hipLaunchKernelGGL(gemm_f64_splitk_partial_kernel, dim3((unsigned)S, (unsigned)tiles), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(gemm_f64_splitk_reduce_kernel, dim3(TILE * TILE / 256, (unsigned)tiles), dim3(256), 0, s, a);
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  if (used) *used = S;
+  return GMB_OK;
+}
+
+// a complete, unconsumed single-engine factor of the current (data, kernel, theta) sits in dA
+bool has_live_factor(const gmb_engine* e) {
+  return e->factored && e->factor_kind == gmb_engine::FK_SINGLE && !e->factor_consumed && e->dA && e->cap_A > 0;
+}
+
+// what gmb_append and gmb_truncate refuse alike
+int resize_ready(gmb_engine* e, const char* what) {
+  int rc = require_ready(e, false);
+  if (rc) return rc;
+  if (e->solve_hook || e->dist_mode != 0 || e->factor_kind == gmb_engine::FK_REPLICATED || e->factor_kind == gmb_engine::FK_CAPACITY)
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode)", what);
+  if (e->factored && e->factor_consumed)
+    return fail(e, GMB_EINVAL, "%s: the factor was consumed by a gradient call: call gmb_factorize again", what);
+  return GMB_OK;
+}
+
+// Block rows >= I0 of the bordered factor from scratch, against the block columns [0, I0) the buffer still holds: covariance
+// rows, panel solve, corner update (split-k), Cholesky of the corner, log-det, v -- and the host's look (factorize_finish).
+// The engine's sizes, points and buffers are the NEW ones already.  I0 = 0 is a whole factorisation by this route.
+int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
+  int rc;
+  const AppendRegions reg = append_regions(lay);
+  const int I0 = (int)lay.I0, nct = (int)reg.nct, nrt = (int)reg.nrt;
+  hipStream_t s = e->stream;
+  e->factored = false;
+  e->factor_kind = gmb_engine::FK_SINGLE;
+  e->factor_consumed = false;
+  e->notpd = -1;
+  e->chol = CholResult{};
+  e->et_fused = false;
+  e->light = false;
+  // phase events as behind gmb_factorize: kbuild_ms = the rebuilt rows of Sigma, chol_ms = panel solve + corner update + corner
+  // factorisation + v (tools/gpu_append.py)
+  for (auto& ev : e->fe)
+    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  e->fe_recorded = true;
+  gmb_timings& tm = e->tm;
+  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
+  tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
+  tm.chol_gemm_launches = 0;
+  HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), s));
+  const FactorRef f = train_factor(e);
+  HIP_TRY(e, hipEventRecord(e->fe[0], s));
+  {  // block rows >= I0 of Sigma: partial block row, new rows, y row, identity padding
+    CovTileArgs a{};
+    a.p = e->cp;
+    a.rows = train_set(e);
+    a.cols = train_set(e);
+    a.out = e->dA;
+    a.ldo = e->ld;
+    a.ti = nrt;
+    a.tj = nct;
+    a.mode = COV_TRAIN;
+    a.lower_only = 1;
+    a.row_first = I0;
+    a.row_stride = 1;
+    a.y = e->dy;
+    if ((rc = launch_cov(e, a))) return rc;
+    for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: accumulating passes
+      if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[t].pa))) return rc;
+      a.p = e->terms[t].cp;
+      a.accumulate = 1;
+      if ((rc = launch_cov(e, a))) return rc;
+    }
+    if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+  }
+  HIP_TRY(e, hipEventRecord(e->fe[1], s));
+  HIP_TRY(e, hipEventRecord(e->fe[2], s));
+  if (I0 > 0) {
+    // P = Sigma[rows >= I0, :I0] L^-T in place in the factor buffer (the y row rides along: its part of v)
+    if ((rc = trsm_cols(e, s, f, e->dA + reg.panel_off, e->ld, (int)reg.panel_row_tiles, 0, I0, EV_CHOL_SOLVE_GEMM, EV_CHOL_STRIP))) return rc;
+    // corner -= P P^T: a handful of tiles contracted over every kept column
+    SplitKArgs k{};
+    k.C = e->dA + reg.corner_off;
+    k.ldc = e->ld;
+    k.A = k.B = e->dA + reg.panel_off;
+    k.lda = k.ldb = e->ld;
+    k.mt = (int)reg.corner_mt;
+    k.nt = (int)reg.corner_nt;
+    k.k = (int)reg.corner_k;
+    k.alpha = -1.0;
+    k.beta = 1.0;
+    k.tri = 1;
+    // ... when the corner IS a handful of tiles, or the rule finds slices to cut; a corner of many tiles (a large K) is the shape
+    // launch_gemm's triangular update is built for: one workgroup per tile fills the chip, no workspace, C touched once
+    const int corner_tiles = splitk_tile_count(k.mt, k.nt, 1);
+    if (corner_tiles <= SPLITK_FEW_TILES || splitk_rule(corner_tiles, k.k, nullptr) > 1) {
+      if ((rc = launch_gemm_splitk(e, s, k, -1, nullptr))) return rc;
+    } else {
+      GemmArgs g{};
+      g.C = k.C;
+      g.ldc = k.ldc;
+      g.A = k.A;
+      g.lda = k.lda;
+      g.B = k.B;
+      g.ldb = k.ldb;
+      g.mt = k.mt;
+      g.nt = k.nt;
+      g.k = k.k;
+      g.alpha = -1.0;
+      g.beta = 1.0;
+      g.tri = 1;
+      if ((rc = launch_gemm(e, s, g, EV_CHOL_UPDATE))) return rc;
+    }
+    // the kept columns' share of the log-determinant; the corner's leaves add theirs
+    hipLaunchKernelGGL(diag_logdet_kernel, dim3(1), dim3(256), 0, s, e->dA, e->ld, (int64_t)I0 * TILE, e->dscal);
+    HIP_TRY(e, hipGetLastError());
+  }
+  // the corner by the plain recursion (launches only: it is a few block columns wide)
+  if (I0 < nct && (rc = chol_cols(e, s, f, I0, nct, nrt, EV_CHOL_PANEL_GEMM))) return rc;
+  hipLaunchKernelGGL(extract_v_kernel, dim3(EXTRACT_V_BLOCKS), dim3(TILE), 0, s, e->dA, e->ld, e->N, e->dv, e->dscal + 1);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->fe[3], s));
+  if (!e->hl) {
+    HIP_TRY(e, hipHostMalloc((void**)&e->hl, sizeof(gmb_engine::HostLanding), hipHostMallocDefault));
+    HIP_TRY(e, hipHostGetDevicePointer((void**)&e->hl_dev, e->hl, 0));
+  }
+  e->hl->info = 0;
+  e->hl->abort = 0;
+  HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  e->fact_in_flight = true;
+  return factorize_finish(e);
+}
+
+// N -> N_new under the engine: K rows appended (Xnew, ynew) or the tail cut (Xnew == nullptr).  Kernel, periods and theta stay.
+// Without a live factor the result is what gmb_set_data on the new arrays + gmb_set_theta would leave; with one, the factor is
+// re-laid when its leading dimension or its capacity asks for it, and updated by refactor_tail.
+int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_t ldx, const double* ynew, int32_t memspace,
+             const char* what) {
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool live = has_live_factor(e);
+  // sizes, kept block columns and copy plan: append_layout.hpp (host arithmetic that tools/append_layout_check.cpp runs under sanitizers)
+  const AppendLayout lay = append_layout(e->N, e->ld, N_new, e->dA ? e->cap_A : 0);
+  const int64_t N_old = lay.N_old, Np_old = lay.Np_old, ld_old = lay.ld_old;
+  const int64_t Np_new = lay.Np_new, Nr_new = lay.Nr_new, ld_new = lay.ld_new;
+  const int I0 = (int)lay.I0;
+  const int D = e->D;
+  int rc;
+  // the re-laid factor first: a device that cannot hold both copies refuses before anything is touched
+  double* newA = nullptr;
+  int64_t cap_newA = 0;
+  if (live && lay.relayout) {
+    const double need = 8.0 * (double)ld_new * (double)Np_new;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+    if (need > (double)free_b)
+      return fail(e, GMB_ENOMEM, "%s: re-laying the factor for N = %lld (leading dimension %lld -> %lld) needs %.0f bytes beside the resident "
+                                 "copy, %.0f are free -- nothing was changed", what, (long long)N_new, (long long)ld_old, (long long)ld_new, need, (double)free_b);
+    if ((rc = ensure(e, &newA, &cap_newA, ld_new * Np_new))) return rc;
+  }
+  e->factored = false;
+  e->have_alpha = false;
+  e->bs_valid = false;
+  e->u_valid = e->linv_valid = false;
+  if (!live) e->factor_kind = gmb_engine::FK_NONE;
+  auto bail = [&](int code) {  // a failure half-way: no factor; the data may be of either size, so nothing is ready
+    if (newA) release(e, newA);
+    e->factored = false;
+    e->factor_kind = gmb_engine::FK_NONE;
+    e->have_theta = false;
+    return code;
+  };
+  const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (Xnew) {  // append: new X and y buffers, the old rows in front
+    double* nX = nullptr;
+    double* ny = nullptr;
+    int64_t c1 = 0, c2 = 0;
+    if ((rc = ensure(e, &nX, &c1, N_new * (int64_t)D)) || (rc = ensure(e, &ny, &c2, Np_new))) {
+      if (nX) release(e, nX);
+      return bail(rc);
+    }
+    hipError_t hs = hipMemcpyAsync(nX, e->dX, (size_t)(N_old * D) * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+    if (hs == hipSuccess) hs = hipMemcpy2DAsync(nX + N_old * D, D * sizeof(double), Xnew, ldx * sizeof(double), D * sizeof(double), K, kind, e->stream);
+    if (hs == hipSuccess) hs = hipMemsetAsync(ny, 0, (size_t)Np_new * sizeof(double), e->stream);
+    if (hs == hipSuccess) hs = hipMemcpyAsync(ny, e->dy, (size_t)N_old * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+    if (hs == hipSuccess) hs = hipMemcpyAsync(ny + N_old, ynew, (size_t)K * sizeof(double), kind, e->stream);
+    if (hs == hipSuccess) hs = hipStreamSynchronize(e->stream);  // the caller may reuse its buffers
+    if (hs != hipSuccess) {
+      release(e, nX);
+      release(e, ny);
+      return bail(fail(e, GMB_EHIP, "%s: copying the new observations failed: %s", what, hipGetErrorString(hs)));
+    }
+    release(e, e->dX);
+    release(e, e->dy);
+    e->dX = nX;
+    e->dy = ny;
+    if (Np_new > Np_old) {
+      if ((rc = alloc(e, &e->dv, Np_new))) return bail(rc);
+      const int64_t need = (Np_new / TILE) * (int64_t)8 * 256;
+      if (e->cap_dinv16 < need) {  // the kept blocks' sub-block inverses move along
+        double* nd = nullptr;
+        int64_t cd = 0;
+        if ((rc = ensure(e, &nd, &cd, need))) return bail(rc);
+        if (live && I0 > 0 && hipMemcpy(nd, e->dDinv16, (size_t)I0 * 8 * 256 * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) {
+          release(e, nd);
+          return bail(fail(e, GMB_EHIP, "%s: copying the kept blocks' sub-block inverses failed", what));
+        }
+        release(e, e->dDinv16);
+        e->dDinv16 = nd;
+        e->cap_dinv16 = cd;
+      }
+    }
+  } else {  // truncate: the buffers stay, y's padding is zero again
+    if (hipMemsetAsync(e->dy + N_new, 0, (size_t)(Np_old - N_new) * sizeof(double), e->stream) != hipSuccess)
+      return bail(fail(e, GMB_EHIP, "%s: clearing the padding of y failed", what));
+  }
+  // sizes, and everything sized by them (as gmb_set_data drops it)
+  e->N = N_new;
+  e->Np = Np_new;
+  e->Nr = Nr_new;
+  e->ld = ld_new;
+  e->Mt_cap = 0;
+  e->Mt2_cap = 0;
+  e->cap_part = 0;
+  e->pg_cap = 0;
+  e->plan_N = -1;
+  e->prep_deferred = false;
+  // the prepared coordinates of ALL rows: their SoA stride is Nr
+  if (e->cap_pts < e->Nr) {
+    e->cap_pts = 0;
+    if ((rc = alloc(e, &e->xs, (int64_t)17 * e->Nr)) || (rc = alloc(e, &e->xl, (int64_t)MAX_LIN * e->Nr)) ||
+        (rc = alloc(e, &e->cat, (int64_t)MAX_TABS * e->Nr)))
+      return bail(rc);
+    e->cap_pts = e->Nr;
+  }
+  if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat))) return bail(rc);
+  if (!live) {
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: preparing the points failed", what));
+    if (e->cap_A < e->ld * e->Np && e->dA) {  // (gmb_set_data: a factor buffer too small for the new size goes)
+      release(e, e->dA);
+      e->dA = nullptr;
+      e->cap_A = 0;
+    }
+    return GMB_OK;
+  }
+  if (newA) {  // the kept lower triangle, block column by block column: rows [128 c, 128 I0) of columns [128 c, 128 c + 128)
+    for (int c = 0; c < I0; ++c) {
+      const AppendCopy cp = append_copy_block(lay, c);
+      const hipError_t hs = hipMemcpy2DAsync(newA + cp.dst, ld_new * sizeof(double), e->dA + cp.src, ld_old * sizeof(double),
+                                             (size_t)cp.rows * sizeof(double), (size_t)cp.cols, hipMemcpyDeviceToDevice, e->stream);
+      if (hs != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: re-laying the factor failed: %s", what, hipGetErrorString(hs)));
+    }
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: re-laying the factor failed", what));
+    release(e, e->dA);
+    e->dA = newA;
+    e->cap_A = cap_newA;
+    newA = nullptr;
+  }
+  return refactor_tail(e, lay);
+}
 
 // M is tiled so that the solved cross-covariance (Mt x Np doubles) stays within ~8 GiB
 int64_t predict_tile_rows(const gmb_engine* e, int64_t M) {
@@ -4100,6 +4389,55 @@ int gmb_blk_gemm_ex(gmb_engine* e, double* C, const double* A, const double* B, 
   pin.strip = d->strip;
   pin.launched = launched;
   return launch_gemm(e, e->stream, g, EV_CHOL_PANEL_GEMM, &pin);
+}
+
+// The split-k product on caller-provided blocks (tests, tools/gpu_append.py): see the header.
+int gmb_blk_gemm_splitk(gmb_engine* e, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t m,
+                        int64_t n, int64_t k, double alpha, double beta, int32_t tri, int32_t slices, int32_t* slices_used) {
+  if (slices_used) *slices_used = 0;
+  if (!e) return GMB_EINVAL;
+  if (!C || !A || !B) return fail(e, GMB_EINVAL, "null gemm operand");
+  if (m % TILE || n % TILE || k % KT || m <= 0 || n <= 0 || k <= 0 || m > (1 << 24) || n > (1 << 24) || k > (1 << 24))
+    return fail(e, GMB_EINVAL, "split-k gemm sizes must be positive multiples of 128 (m, n) and 16 (k)");
+  // (the tile count is formed in 64 bits -- splitk_tile_count -- and bounded by the launch: at most 65535 computed tiles)
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)(lda * 8) | (uintptr_t)(ldb * 8)) & 15u)
+    return fail(e, GMB_EINVAL, "gmb_blk_gemm_splitk: A and B must be 16-byte aligned, lda and ldb even");
+  if (lda < m || ldb < n || ldc < n) return fail(e, GMB_EINVAL, "gmb_blk_gemm_splitk: a leading dimension is smaller than its operand");
+  if (tri < 0 || tri > 1) return fail(e, GMB_EINVAL, "gmb_blk_gemm_splitk: tri must be 0 or 1");
+  if (slices != -1 && slices < 1) return fail(e, GMB_EINVAL, "gmb_blk_gemm_splitk: slices must be -1 (by the rule) or >= 1");
+  HIP_TRY(e, hipSetDevice(e->device));
+  SplitKArgs a{};
+  a.C = C;
+  a.ldc = ldc;
+  a.A = A;
+  a.lda = lda;
+  a.B = B;
+  a.ldb = ldb;
+  a.mt = (int)(m / TILE);
+  a.nt = (int)(n / TILE);
+  a.k = (int)k;
+  a.alpha = alpha;
+  a.beta = beta;
+  a.tri = tri;
+  return launch_gemm_splitk(e, e->stream, a, slices, slices_used);
+}
+
+int gmb_append(gmb_engine* e, const double* Xnew, int64_t K, int64_t ldx, const double* ynew, int32_t memspace) {
+  int rc = resize_ready(e, "gmb_append");
+  if (rc) return rc;
+  if (!Xnew || !ynew || K < 0 || ldx < e->D) return fail(e, GMB_EINVAL, "gmb_append: bad Xnew/K/ldx/ynew");
+  if (K == 0) return GMB_OK;
+  return resize_n(e, e->N + K, Xnew, K, ldx, ynew, memspace, "gmb_append");
+}
+
+int64_t gmb_num_obs(const gmb_engine* e) { return e ? e->N : (int64_t)GMB_EINVAL; }
+
+int gmb_truncate(gmb_engine* e, int64_t n_keep) {
+  int rc = resize_ready(e, "gmb_truncate");
+  if (rc) return rc;
+  if (n_keep < 1 || n_keep > e->N) return fail(e, GMB_EINVAL, "gmb_truncate: n_keep = %lld must be in [1, %lld]", (long long)n_keep, (long long)e->N);
+  if (n_keep == e->N) return GMB_OK;
+  return resize_n(e, n_keep, nullptr, 0, 0, nullptr, GMB_HOST, "gmb_truncate");
 }
 
 }  // extern "C"

@@ -308,6 +308,14 @@ class DistributedEngine:
     def set_data(self, X, y):
         self.eng.set_data(X, y)
 
+    def append(self, X, y):
+        raise NotImplementedError("append: the factor of a distributed GP is spread over the ranks' block rows; the bordered update "
+                                  "(gmb_append) works on one device's complete factor only")
+
+    def truncate(self, n):
+        raise NotImplementedError("truncate: the factor of a distributed GP is spread over the ranks' block rows; gmb_truncate works "
+                                  "on one device's complete factor only")
+
     def set_kernel(self, spec):
         if getattr(spec, "periodic", 0):
             raise NotImplementedError("periodic kernels on a distributed GP: the multi-GPU driver refuses them (gmb_set_periodic)")

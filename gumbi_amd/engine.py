@@ -332,6 +332,11 @@ _SIGNATURES = {
                                   C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                   C.c_int32, C.c_int64]),
     "gmb_blk_gemm_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
+    "gmb_blk_gemm_splitk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "gmb_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
+    "gmb_truncate": (C.c_int, [C.c_void_p, C.c_int64]),
+    "gmb_num_obs": (C.c_int64, [C.c_void_p]),
 }
 
 
@@ -373,8 +378,9 @@ def _preload_hip_runtime():
 #: ``gmb_timings``, ``gmb_debug_assume_factored`` behind GUMBI_HIP_DEBUG_DOORS=1; version 11 the joint posterior:
 #: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``; version 13 the GEMM test door
 #: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``; version 14 the posterior mean's gradient ``gmb_predict_grad``; version 15 mean and
-#: variance with both gradients in one call, ``gmb_predict_with_grad``)
-ABI_VERSION = 15
+#: variance with both gradients in one call, ``gmb_predict_with_grad``; version 16 ``gmb_append`` / ``gmb_truncate`` -- observations
+#: appended to / cut from the resident factor -- and the split-k GEMM's test door ``gmb_blk_gemm_splitk``)
+ABI_VERSION = 16
 
 
 def load_library():
@@ -489,6 +495,26 @@ class Engine:
         if y.shape != (self.N,):
             raise ValueError(f"y must be ({self.N},), got {y.shape}")
         self._check(self._lib.gmb_set_y(self._h, _ptr(y), GMB_HOST), "gmb_set_y")
+
+    def append(self, X, y):
+        """``K`` further observations for the same kernel and theta (``gmb_append``): with a valid resident factor the factor is
+        updated in O(N^2 K) and stays valid (``LinAlgError`` when the grown covariance is not positive definite: the data then has
+        the new N, ``truncate`` + ``factorize`` recovers); without one only the data changes.  No ``set_theta`` is needed."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if X.ndim != 2 or y.ndim != 1 or X.shape[0] != y.shape[0] or X.shape[1] != self.D:
+            raise ValueError(f"X must be (K, {self.D}) and y (K,), got {X.shape} and {y.shape}")
+        try:
+            self._check(self._lib.gmb_append(self._h, _ptr(X), X.shape[0], self.D, _ptr(y), GMB_HOST), "gmb_append")
+        finally:
+            self.N = int(self._lib.gmb_num_obs(self._h))  # (after an error the data may have either size: the engine says which)
+
+    def truncate(self, n: int):
+        """Keep the first ``n`` observations (``gmb_truncate``, ``1 <= n <= N``); a valid resident factor is cut along."""
+        try:
+            self._check(self._lib.gmb_truncate(self._h, int(n)), "gmb_truncate")
+        finally:
+            self.N = int(self._lib.gmb_num_obs(self._h))
 
     def set_data_device(self, x_ptr: int, N: int, D: int, ldx: int, y_ptr: int):
         """Inputs already in HBM (e.g. ``torch.Tensor.data_ptr()``)."""
@@ -824,6 +850,17 @@ class Engine:
         w = w.value
         return dict(variant=w & 3, dma=(w >> 2) & 1, pfc=(w >> 3) & 1, in_place=(w >> 4) & 1, order=(w >> 5) & 3,
                     strip=(w >> 8) & 0xFF, grid=(w >> 16) & 0x7FFF)
+
+    def blk_gemm_splitk(self, c_ptr, ldc, a_ptr, lda, b_ptr, ldb, m, n, k, alpha, beta, tri=0, slices=-1):
+        """The split-k f64 GEMM on device blocks (``gmb_blk_gemm_splitk``; ``slices`` -1 = by the rule, >= 1 = pinned): returns the
+        number of slices that ran, also kept in ``splitk_slices_used`` -- 0 after a refusal (``ValueError``, nothing launched:
+        bad sizes, or a pinned ``slices`` that leaves a slice empty)."""
+        used = C.c_int32(-1)
+        rc = self._lib.gmb_blk_gemm_splitk(self._h, C.c_void_p(c_ptr), ldc, C.c_void_p(a_ptr), lda, C.c_void_p(b_ptr), ldb, m, n, k,
+                                           float(alpha), float(beta), int(tri), int(slices), C.byref(used))
+        self.splitk_slices_used = int(used.value)
+        self._check(rc, "gmb_blk_gemm_splitk")
+        return self.splitk_slices_used
 
 
 def chol_task(t: int, nct: int, nrt: int):

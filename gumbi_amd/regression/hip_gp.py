@@ -637,7 +637,7 @@ class HipGP(Regressor):
         return value, d_mu[:, None] * dmu[:, cols] + d_var[:, None] * dvar[:, cols]
 
     def propose_continuous(self, output=None, acquisition="EI", maximize=True, bounds=None, categorical_levels=None,
-                           num_restarts=10, raw_samples=512, seed=None, q=1, **optim_kwargs):
+                           num_restarts=10, raw_samples=512, seed=None, q=1, sequential=False, fantasy="mean", **optim_kwargs):
         """Next point to measure by optimising an acquisition function over the CONTINUOUS inputs (the reference's
         ``BotorchGP.propose``, botorch/GP.py, whose keywords this follows): multi-start L-BFGS-B on analytic ``"EI"`` (in its log
         form) or ``"UCB"`` (``beta=`` in ``optim_kwargs``, default 2) of the noise-free posterior, in standardized units.
@@ -655,11 +655,32 @@ class HipGP(Regressor):
         and sets :attr:`proposal`, :attr:`proposal_acquisition` (its acquisition value) and :attr:`optimization_bounds`
         (standardized ``(lower, upper)`` in ``continuous_dims`` order); for diagnosis also :attr:`proposal_result` (scipy's
         result of the lock-step run) and :attr:`proposal_raw_acquisition` (the raw samples' scores).  Remaining
-        ``optim_kwargs`` go to L-BFGS-B's ``options``."""
-        from scipy.optimize import minimize
+        ``optim_kwargs`` go to L-BFGS-B's ``options``.
 
-        if q != 1:
-            raise NotImplementedError("propose_continuous: q > 1 needs a Monte-Carlo batch acquisition, which is not built")
+        ``q > 1`` needs ``sequential=True`` (the reference's keyword): a greedy batch.  Each of the ``q`` picks is the single-point
+        search above; the pick is then appended to the resident factor (``engine.append``: a bordered update, no
+        re-factorisation) with its noise-free posterior mean as the observation -- ``fantasy="mean"``, the Kriging believer; for EI
+        the fantasy enters the incumbent when it is better -- so that the next search sees the posterior conditioned on it.
+        After the last pick (which needs no fantasy: ``q - 1`` appends) the engine is truncated back to the real observations,
+        whatever happened in between.  Returns a parray of ``q`` points; :attr:`proposal_acquisition` is then the list of the
+        ``q`` acquisition values, each under the posterior its search saw (a fantasy at the mean of a model WITH observation noise
+        shrinks the variance s^2 at its pick to s^2 sigma^2 / (s^2 + sigma^2) and leaves the mean: where the data have settled the
+        surface the picks of a batch can lie close together), :attr:`proposal_result` and
+        :attr:`proposal_raw_acquisition` those of the last search.  Not for the Kronecker path (pass ``kronecker=False``)."""
+        q = int(q)
+        if q != 1 and not sequential:
+            raise NotImplementedError("propose_continuous: q > 1 needs a Monte-Carlo batch acquisition, which is not built "
+                                      "(sequential=True proposes a greedy batch)")
+        if q < 1:
+            raise ValueError(f"q must be >= 1, got {q}")
+        if q > 1 and fantasy != "mean":
+            raise NotImplementedError(f"propose_continuous: fantasy={fantasy!r}; only 'mean' (the Kriging believer) is built")
+        if q > 1 and self.distributed:
+            raise NotImplementedError("propose_continuous(sequential=True): the factor of a distributed GP is spread over the ranks; "
+                                      "the fantasies' bordered update works on one device's complete factor")
+        if q > 1 and isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError("propose_continuous(sequential=True): the Kronecker path holds P systems over the SAME inputs; "
+                                      "a fantasy of one output would break that alignment (pass kronecker=False)")
         beta = optim_kwargs.pop("beta", None)
         problem = self._acquisition_problem(output, acquisition, maximize, categorical_levels, beta)
         f, cont, cols, full = problem
@@ -678,6 +699,63 @@ class HipGP(Regressor):
         self.optimization_bounds = (lo.copy(), hi.copy())
 
         rng = np.random.default_rng(self.seed if seed is None else seed)
+        options = {"maxiter": 200, **optim_kwargs.pop("options", {}), **optim_kwargs}
+        if q == 1:
+            z, value = self._propose_one(problem, lo, hi, rng, num_restarts, raw_samples, maximize, options)
+            self.proposal_acquisition = value
+            self.proposal = self.parray(**{d: np.array([z[k]]) for k, d in enumerate(cont)}, stdzd=True)
+            return self.proposal
+
+        # greedy batch: condition the resident factor on each pick's posterior mean before the next search
+        n_real, X_real, y_real = len(self.model.y), self.model.X, self.model.y
+        picks, values, grown = [], [], False
+        try:
+            for i in range(q):
+                if i > 0:  # (the incumbent of EI follows the fantasies)
+                    problem = self._acquisition_problem(output, acquisition, maximize, categorical_levels, beta)
+                    full = problem[3]
+                z, value = self._propose_one(problem, lo, hi, rng, num_restarts, raw_samples, maximize, options)
+                picks.append(z)
+                values.append(value)
+                if i + 1 < q:
+                    point = full(z[None, :])
+                    mean, _ = self.engine.predict(point, with_noise=False)
+                    grown = True  # (also when the append fails half-way: the engine's data may have the new size)
+                    self.engine.append(point, mean)
+                    self.model.X = np.vstack([self.model.X, point])
+                    self.model.y = np.concatenate([self.model.y, np.asarray(mean, float)])
+        except BaseException:
+            # the search's (or a fantasy's) error is the one to report: the clean-up below must not replace it
+            self.model.X, self.model.y = X_real, y_real
+            if grown:
+                try:
+                    self._drop_fantasies(n_real)
+                except Exception as err:  # noqa: BLE001
+                    warnings.warn(f"propose_continuous: restoring the engine to its {n_real} observations failed ({err}); "
+                                  "call build_model / find_MAP again", RuntimeWarning, stacklevel=2)
+            raise
+        self.model.X, self.model.y = X_real, y_real
+        if grown:
+            self._drop_fantasies(n_real)
+        picks = np.array(picks)
+        self.proposal_acquisition = values
+        self.proposal = self.parray(**{d: picks[:, k] for k, d in enumerate(cont)}, stdzd=True)
+        return self.proposal
+
+    def _drop_fantasies(self, n_real):
+        """Back to the ``n_real`` real observations with a valid factor: a truncation of the resident factor, or -- behind a
+        fantasy whose append was not positive definite, which leaves no factor -- the cut data factorised again (as
+        :meth:`condition_on` does)."""
+        self.engine.truncate(n_real)
+        if not self.engine.factor_is_current():
+            self.engine.factorize()
+
+    def _propose_one(self, problem, lo, hi, rng, num_restarts, raw_samples, maximize, options):
+        """One single-point search of :meth:`propose_continuous` against the engine's present posterior: the best candidate's
+        standardized continuous coordinates and its acquisition value."""
+        from scipy.optimize import minimize
+
+        f, cont, cols, full = problem
         raw = lo + (hi - lo) * rng.random((raw_samples, len(cont)))
         mu, var = self.engine.predict(full(raw), with_noise=False)
         raw_value = f(mu, var, maximize)[0]
@@ -687,7 +765,6 @@ class HipGP(Regressor):
             value, grad = self.acquisition_with_grad(z.reshape(num_restarts, len(cont)), maximize=maximize, _problem=problem)
             return -float(np.sum(value)), -grad.ravel()
 
-        options = {"maxiter": 200, **optim_kwargs.pop("options", {}), **optim_kwargs}
         res = minimize(objective, starts.ravel(), jac=True, method="L-BFGS-B",
                        bounds=list(zip(np.tile(lo, num_restarts), np.tile(hi, num_restarts))), options=options)
         cand = np.clip(np.vstack([res.x.reshape(num_restarts, len(cont)), starts]), lo, hi)
@@ -695,10 +772,105 @@ class HipGP(Regressor):
         value = f(mu, var, maximize)[0]
         best = int(np.argmax(value))
         self.proposal_result = res
-        self.proposal_acquisition = float(value[best])
         self.proposal_raw_acquisition = raw_value
-        self.proposal = self.parray(**{d: np.array([cand[best, k]]) for k, d in enumerate(cont)}, stdzd=True)
-        return self.proposal
+        return cand[best], float(value[best])
+
+    def _shaped_rows(self):
+        """:meth:`get_shaped_data` for a table of ANY number of rows: ``(K, D)`` and ``(K,)`` -- the base method squeezes a
+        one-row table of a single-output model to a 0-d y (and masks X with it into three dimensions)."""
+        self.X, self.y = self.get_structured_data("mean")
+        if self.out_col in self.dims:
+            return self.get_shaped_data("mean")  # (stacked with hstack / vstack: already 1-D and 2-D)
+        y = np.atleast_1d(np.asarray(self.y.z.values(), dtype=np.float64).squeeze())
+        xz = self.X.z
+        X = np.column_stack([np.atleast_1d(np.asarray(xz[dim + "_z"].values(), dtype=np.float64).squeeze()) for dim in self.dims])
+        X = X.reshape(-1, len(self.dims))
+        keep = ~np.isnan(y)
+        return np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep])
+
+    # -- new observations under the fitted hyper-parameters ---------------------------------------------------------------------
+    def condition_on(self, new_data, refit=False):
+        """Absorb further measurements into the fitted GP WITHOUT re-factorising: the rows of ``new_data`` -- a wide-form DataFrame,
+        or a DataSet, with the columns of ``gp.data`` -- are appended to the resident Cholesky factor (``engine.append``: a bordered
+        update, O(N^2 K) instead of O(N^3)) under the hyper-parameters :attr:`MAP`, which stay as they are.
+
+        The rows are standardized with the EXISTING standardizer and coded with the fitted model's own levels and coordinates
+        (a categorical level, or a filter value, the model has not seen is a ``ValueError``; new values of a numeric continuous
+        dimension join its levels).  ``self.data`` becomes the merged DataSet with the same standardizer and specs; ``model.X``
+        and ``model.y`` gain the rows in the engine's order (behind the old ones).  Cached predictions, the grid and the
+        structured-data cache are dropped.  The lengthscale prior keeps the pairwise-distance limits of the data the model was
+        built on.  ``refit=True`` then runs ``find_MAP(start=self.MAP)`` on the merged data.  Returns ``self``.
+
+        Kronecker and distributed GPs raise ``NotImplementedError`` (build with ``kronecker=False``)."""
+        import pandas as pd
+
+        if self.distributed:
+            raise NotImplementedError("condition_on: the factor of a distributed GP is spread over the ranks; the bordered update "
+                                      "works on one device's complete factor")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError("condition_on: the Kronecker path holds P systems over the SAME inputs; new observations "
+                                      "would break that alignment (pass kronecker=False)")
+        if self.model is None or self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before it can be conditioned on new data")
+        wide = pd.DataFrame(new_data.data if isinstance(new_data, DataSet) else new_data)
+        columns = list(self.data.data.columns)
+        missing = [c for c in columns if c not in wide.columns]
+        if missing:
+            raise ValueError(f"new_data lacks the column(s) {missing} of the GP's data")
+        wide = wide[columns].reset_index(drop=True)
+        if len(wide) == 0:
+            return self
+
+        # the fitted model's levels: categorical and filter values must be known, numeric continuous values join their levels
+        levels, coords = dict(self.continuous_levels), dict(self.continuous_coords)
+        for dim, known in self.filter_dims.items():
+            if dim != self.out_col and not wide[dim].isin(known).all():
+                raise ValueError(f"new_data[{dim!r}] holds values other than {known}, which the model was filtered to")
+        for dim in self.categorical_dims:
+            if dim == self.out_col:
+                continue
+            unseen = sorted(set(wide[dim].unique().tolist()) - set(self.categorical_levels[dim]))
+            if unseen:
+                raise ValueError(f"new_data[{dim!r}] holds level(s) {unseen} the fitted model has not seen "
+                                 f"(its levels: {self.categorical_levels[dim]})")
+        for dim in self.continuous_dims:
+            fresh = [v for v in wide[dim].unique().tolist() if v not in coords[dim]]
+            if not fresh:
+                continue
+            if not all(k is v or k == v for k, v in coords[dim].items()) or wide[dim].dtype.kind not in "fiu":
+                raise ValueError(f"new_data[{dim!r}] holds level(s) {fresh} without coordinates in the fitted model")
+            levels[dim] = list(levels[dim]) + fresh
+            coords[dim] = {**coords[dim], **{v: v for v in fresh}}
+
+        # the new rows as the engine takes them: shaped by the model's own plumbing on a DataSet that shares the standardizer
+        old = (self.data, self.continuous_levels, self.continuous_coords, self._structured_cache, self.X, self.y)
+        try:
+            self.data = DataSet(wide, **self.data.specs)
+            self.continuous_levels, self.continuous_coords, self._structured_cache = levels, coords, None
+            X_new, y_new = self._shaped_rows()
+        finally:
+            self.data, self.continuous_levels, self.continuous_coords, self._structured_cache, self.X, self.y = old
+        if len(y_new) == 0:
+            return self
+        n_old = len(self.model.y)
+        try:
+            self.engine.append(X_new, y_new)
+        except np.linalg.LinAlgError:
+            # the grown covariance is not positive definite at the MAP: back to the fitted state, and say so
+            self.engine.truncate(n_old)
+            self.engine.factorize()
+            raise
+        self.model.X = np.vstack([self.model.X, X_new])
+        self.model.y = np.concatenate([self.model.y, y_new])
+        self.data = DataSet(pd.concat([pd.DataFrame(self.data.data), wide], ignore_index=True), **self.data.specs)
+        self.continuous_levels, self.continuous_coords = levels, coords
+        self._structured_cache = None
+        for slot in ("grid_vectors", "grid_parray", "grid_points", "ticks", "predictions", "predictions_X"):
+            setattr(self, slot, None)
+        self.X, self.y = self.get_structured_data("mean")
+        if refit:
+            self.find_MAP(start=self.MAP)
+        return self
 
     # -- joint posterior: covariance and draws ---------------------------------------------------------------------------------
     def _joint_engine(self, additive_level, what):

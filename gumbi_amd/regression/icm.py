@@ -80,6 +80,14 @@ class IcmEngine:
         self._state = None
         self._slots = {}
 
+    def append(self, X, y):
+        raise NotImplementedError("append: the Kronecker path holds P systems over the SAME inputs; observations of one output at a new "
+                                  "input would break that alignment (pass kronecker=False for a model that is conditioned on new data)")
+
+    def truncate(self, n):
+        raise NotImplementedError("truncate: the Kronecker path holds P systems over the SAME inputs, not one stacked factor to cut "
+                                  "(pass kronecker=False)")
+
     def set_kernel(self, spec: KernelSpec):
         if not aligned_outputs(self.X, spec):
             raise ValueError("the Kronecker path needs the same inputs for every output")

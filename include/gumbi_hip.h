@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GMB_ABI_VERSION 15
+#define GMB_ABI_VERSION 16
 #define GMB_MAX_DIMS 16   /* continuous dims per kernel */
 #define GMB_MAX_LIN 8     /* linear dims per kernel (subset of the continuous dims) */
 #define GMB_MAX_COREG 4   /* categorical (coregion) dims besides the output column */
@@ -227,6 +227,31 @@ int gmb_theta_size(const gmb_kernel_spec* spec);
  * Additive models warp every term's own lengthscales with the same periods.  The multi-GPU driver (gmb_dist_*) refuses
  * periodic engines. */
 int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t n);
+
+/* (ABI 16) Change N under the engine; kernel, periods and theta stay, no gmb_set_theta is needed afterwards.
+ * gmb_append: K further observations for the SAME kernel and theta: Xnew (K, D) row-major with leading dimension ldx >= D, ynew (K).
+ * gmb_truncate: keep the first n_keep observations (1 <= n_keep <= N).
+ * Without a valid resident factor they only change the data: the result is what gmb_set_data on the concatenated / cut arrays
+ * followed by the stored theta would leave; gmb_factor_valid stays 0.  With a complete, unconsumed single-engine factor they update
+ * it: row i of a Cholesky factor depends on rows <= i of Sigma only, so with I0 = floor(min(N_old, N_new) / 128) the block columns
+ * [0, I0) are kept and the block rows >= I0 of the bordered matrix are rebuilt, solved against the kept columns, their corner updated
+ * (contraction length 128 I0: on the split-k product of gmb_blk_gemm_splitk below when the corner is a handful of tiles or the
+ * rule finds slices to cut, on the trailing update's triangular GEMM when an append is so large that the corner has many tiles) and factored; log-det, v and |v|^2 follow.  O(N^2 K) instead of O(N^3).  When
+ * the padded row or column count changes, the factor is re-laid to the new leading dimension in a second buffer (the kept triangle
+ * copied device to device): a device that cannot hold both returns GMB_ENOMEM with the bytes needed in gmb_last_error before
+ * anything is touched.  (Only that buffer is measured up front.  The small allocations behind it -- X, y, v, prepared points: O(N D)
+ * -- can still fail after the data has begun to change; the engine then holds no factor and no theta, gmb_num_obs says which N its
+ * data has, and gmb_set_data + gmb_set_theta start over.)  Afterwards gmb_factor_valid is 1 and gmb_predict*, gmb_nlml, gmb_copy_* behave as behind gmb_factorize at the
+ * new N; everything derived from the old factor (both alphas, U, L^-1, the joint state) is invalid, so the next prediction takes
+ * the solve form.  Deterministic call after call; NOT promised to equal a fresh factorisation bit for bit.  GMB_ENOTPD +
+ * gmb_notpd_index (a row of the new matrix): the data has the new N, the factor is invalid; gmb_truncate + gmb_factorize recovers.
+ * GMB_EINVAL: null pointers, ldx < D, n_keep out of range, no data or theta yet, a consumed factor, distributed or capacity-mode
+ * engines, engines whose last factorisation was gmb_dist_*.  K == 0 and n_keep == N are GMB_OK and change nothing. */
+int gmb_append(gmb_engine* e, const double* Xnew, int64_t K, int64_t ldx, const double* ynew, int32_t memspace);
+int gmb_truncate(gmb_engine* e, int64_t n_keep);
+/* N of the data the engine holds now (0 before gmb_set_data), or a negative gmb_status for a null handle: what a binding reads back
+ * after gmb_append / gmb_truncate, whatever they returned. */
+int64_t gmb_num_obs(const gmb_engine* e);
 
 /* Hyper-parameters on the natural scale -- the role of `point=self.MAP` (pymc/GP.py:846). */
 int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n);
@@ -473,6 +498,17 @@ typedef struct gmb_gemm_desc {
 } gmb_gemm_desc;
 int gmb_blk_gemm_ex(gmb_engine* e, double* C, const double* A, const double* B, const gmb_gemm_desc* d,
                     int32_t* launched);
+/* (ABI 16) The same product for FEW output tiles and a LONG contraction, split along k (csrc/gemm_splitk.hpp): m, n multiples of 128,
+ * k of 16, tri != 0 skips the tiles strictly above the diagonal.  Two launches in stream order: the grid (slices x computed tiles)
+ * writes each slice's 128 x 128 partial to an engine workspace laid out [tile][slice][128 * 128]; the second adds a tile's partials in
+ * ascending slice order and applies alpha and beta.  No atomics, nothing waits: the same bits call after call.  `slices` = -1: by the
+ * rule -- a function of (tile count, k) alone: min(256 / tiles, k / 256), at least 1, slices equal multiples of 16 with a shorter last
+ * one; >= 1 pins the number.  *slices_used (may be NULL) = what ran, 0 when nothing was launched.  GMB_EINVAL, nothing launched: bad
+ * sizes, more than 65535 computed tiles (it is the kernel for FEW tiles), or a pinned `slices` that leaves a slice empty or not a
+ * multiple of 16. */
+int gmb_blk_gemm_splitk(gmb_engine* e, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
+                        int64_t m, int64_t n, int64_t k, double alpha, double beta, int32_t tri,
+                        int32_t slices /* -1 = by the rule, >= 1 = pin */, int32_t* slices_used);
 /* -- ONE GP over the GPUs of a node (no reference counterpart -- the reference is
  * single-process; the work replaced is what pm.find_MAP / Marginal.predict do per evaluation,
  * pymc/GP.py:811, 845-847) -------------------------------------------------------------------------------
