@@ -41,7 +41,6 @@
 #include "predict_form.hpp"
 #include "joint_predict.hpp"
 #include "predict_grad.hpp"
-#include "predict_var_grad.hpp"
 
 using namespace gmb;
 
@@ -212,11 +211,9 @@ struct gmb_engine {
   double* dalpha_bs = nullptr;  // Np: alpha, then Np: the running right-hand side
   int64_t cap_alpha_bs = 0;
   bool bs_valid = false;
-  // gmb_predict_with_grad (predict_var_grad.hpp): the variance gradient of an M-tile and the doubled partials
+  // gmb_predict_with_grad: the variance gradient of an M-tile (its partials are a second set in pg_part)
   double* vg_grad = nullptr;
   int64_t cap_vg_grad = 0;
-  double* vg_part = nullptr;
-  int64_t cap_vg_part = 0;
 
   // gradient workspace
   double* dW = nullptr;  // Np x Np column-major: L^-1 then Sigma^-1
@@ -2442,7 +2439,7 @@ void gmb_destroy(gmb_engine* e) {
                   e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
                   e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
                   e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage,
-                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->vg_part, e->dsk};
+                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->dsk};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int a = 0; a < 3; ++a)
@@ -3481,30 +3478,37 @@ int launch_draw(gmb_engine* e, const DrawArgs& a) {
   return GMB_OK;
 }
 
-// ---- gradient of the posterior mean (predict_grad.hpp) ----------------------------------------------------------------------------
+// ---- gradients of the posterior mean and variance (predict_grad.hpp) -----------------------------------------------------------------
 
-template <int KIND, bool GEN>
-void launch_predict_grad_nc(gmb_engine* e, const PredGradArgs& a, dim3 grid) {
-  const dim3 block(256);
+template <int KIND, int NC>
+void launch_predict_grad_nc(gmb_engine* e, const PredGradArgs& a, dim3 grid, bool gen, int nset) {
+  auto go = [&](void (*kernel)(PredGradArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
+  if (nset == 2) go(gen ? predict_grad_partial_kernel<KIND, NC, true, 2> : predict_grad_partial_kernel<KIND, NC, false, 2>);
+  else go(gen ? predict_grad_partial_kernel<KIND, NC, true, 1> : predict_grad_partial_kernel<KIND, NC, false, 1>);
+}
+
+template <int KIND>
+void launch_predict_grad_kind(gmb_engine* e, const PredGradArgs& a, dim3 grid, bool gen, int nset) {
   switch (e->nc_pad) {
-    case 1: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 1, GEN>), grid, block, 0, e->stream, a); break;
-    case 2: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 2, GEN>), grid, block, 0, e->stream, a); break;
-    case 4: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 4, GEN>), grid, block, 0, e->stream, a); break;
-    case 8: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 8, GEN>), grid, block, 0, e->stream, a); break;
-    default: hipLaunchKernelGGL((predict_grad_partial_kernel<KIND, 16, GEN>), grid, block, 0, e->stream, a); break;
+    case 1: launch_predict_grad_nc<KIND, 1>(e, a, grid, gen, nset); break;
+    case 2: launch_predict_grad_nc<KIND, 2>(e, a, grid, gen, nset); break;
+    case 4: launch_predict_grad_nc<KIND, 4>(e, a, grid, gen, nset); break;
+    case 8: launch_predict_grad_nc<KIND, 8>(e, a, grid, gen, nset); break;
+    default: launch_predict_grad_nc<KIND, 16>(e, a, grid, gen, nset); break;
   }
 }
 
-// one term's partials for the prepared test points in pg_xs / pg_xl / pg_cat (dispatched as launch_cov dispatches the tiles)
-int launch_predict_grad(gmb_engine* e, const PredGradArgs& a, int nchunk) {
+// one term's partials, `nset` accumulator sets, for the prepared test points in pg_xs / pg_xl / pg_cat (dispatched as launch_cov
+// dispatches the tiles)
+int launch_predict_grad(gmb_engine* e, const PredGradArgs& a, int nchunk, int nset) {
   const dim3 grid((unsigned)(a.test.npad / PG_PTS), (unsigned)nchunk);
   const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
   switch (a.p.kind) {
-    case GMB_EXPQUAD: gen ? launch_predict_grad_nc<0, true>(e, a, grid) : launch_predict_grad_nc<0, false>(e, a, grid); break;
-    case GMB_MATERN52: gen ? launch_predict_grad_nc<1, true>(e, a, grid) : launch_predict_grad_nc<1, false>(e, a, grid); break;
-    case GMB_MATERN32: gen ? launch_predict_grad_nc<2, true>(e, a, grid) : launch_predict_grad_nc<2, false>(e, a, grid); break;
-    case GMB_MATERN12: gen ? launch_predict_grad_nc<3, true>(e, a, grid) : launch_predict_grad_nc<3, false>(e, a, grid); break;
-    case GMB_EXPONENTIAL: gen ? launch_predict_grad_nc<4, true>(e, a, grid) : launch_predict_grad_nc<4, false>(e, a, grid); break;
+    case GMB_EXPQUAD: launch_predict_grad_kind<0>(e, a, grid, gen, nset); break;
+    case GMB_MATERN52: launch_predict_grad_kind<1>(e, a, grid, gen, nset); break;
+    case GMB_MATERN32: launch_predict_grad_kind<2>(e, a, grid, gen, nset); break;
+    case GMB_MATERN12: launch_predict_grad_kind<3>(e, a, grid, gen, nset); break;
+    case GMB_EXPONENTIAL: launch_predict_grad_kind<4>(e, a, grid, gen, nset); break;
     default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
   }
   HIP_TRY(e, hipGetLastError());
@@ -3532,118 +3536,6 @@ int backsub_alpha(gmb_engine* e) {
   return GMB_OK;
 }
 
-// workspaces of gmb_predict_grad for M-tiles of Mt rows (a multiple of 128)
-int predict_grad_workspace(gmb_engine* e, int64_t Mt) {
-  int rc;
-  if (e->pg_cap < Mt) {
-    e->pg_cap = 0;
-    if ((rc = alloc(e, &e->pg_Xs, Mt * (int64_t)e->D))) return rc;
-    if ((rc = alloc(e, &e->pg_xs, (int64_t)17 * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_xl, (int64_t)MAX_LIN * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_cat, (int64_t)MAX_TABS * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_grad, Mt * (int64_t)e->D))) return rc;
-    e->pg_cap = Mt;
-  }
-  // every M-tile of mpad <= Mt rows runs nchunk <= PG_TARGET_WGS / (mpad / 64) + 1 chunks (predict_grad_chunk), so its partials
-  // -- nchunk x (nc_pad + n_lin) x mpad doubles -- fit in this whatever its size
-  const int64_t need = ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
-  return ensure(e, &e->pg_part, &e->cap_pg_part, need);
-}
-
-// d mu / d x* of one M-tile (mc points, first row Xs) into pg_grad (mc x D, row-major)
-int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, const double* alpha, hipMemcpyKind in_kind) {
-  int rc;
-  HIP_TRY(e, hipMemcpy2DAsync(e->pg_Xs, e->D * sizeof(double), Xs, ldxs * sizeof(double), e->D * sizeof(double), mc, in_kind, e->stream));
-  HIP_TRY(e, hipMemsetAsync(e->pg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
-  int64_t chunk;
-  int nchunk;
-  predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
-  const PointSet test{e->pg_xs, e->pg_xl, e->pg_cat, mc, mpad};
-  for (size_t t = 0; t < e->terms.size(); ++t) {
-    const gmb_engine::Term& tr = e->terms[t];
-    // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
-    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
-    if ((rc = prep_points(e, e->pg_Xs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
-    PredGradArgs a{};
-    a.p = tr.cp;
-    a.test = test;
-    a.train = train_set(e);
-    a.alpha = alpha;
-    a.part = e->pg_part;
-    a.chunk = chunk;
-    ev_begin(e, e->stream, EV_PREDICT_GRAD, 0.0, (int)(mpad / PG_PTS), nchunk);
-    rc = launch_predict_grad(e, a, nchunk);
-    if (!rc) {
-      PredGradFinishArgs f{};
-      f.part = e->pg_part;
-      f.nchunk = nchunk;
-      f.nc = tr.pa.nc;
-      f.nc_pad = e->nc_pad;
-      f.n_lin = tr.cp.n_lin;
-      f.periodic = tr.pa.periodic;
-      f.D = e->D;
-      f.mpad = mpad;
-      f.mc = mc;
-      f.txs = e->pg_xs;
-      for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k];
-      if (tr.pa.periodic) {
-        for (int d = 0; 2 * d < tr.pa.nc; ++d) f.scale[d] = 2.0 * M_PI * tr.pa.two_over_T[d];  // 2 * (2 pi / T_d)
-      } else {
-        for (int k = 0; k < tr.pa.nc; ++k) f.scale[k] = 2.0 * tr.pa.inv_ls[k];
-      }
-      for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
-      f.tau = tr.cp.tau;
-      f.grad = e->pg_grad;
-      hipLaunchKernelGGL(predict_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, f);
-    }
-    ev_end(e);
-    if (rc) return rc;
-    HIP_TRY(e, hipGetLastError());
-  }
-  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
-  return GMB_OK;
-}
-
-// ---- gradients of mean and variance in one call (predict_var_grad.hpp) -------------------------------------------------------------
-
-template <int KIND, bool GEN>
-void launch_predict_var_grad_nc(gmb_engine* e, const PredVarGradArgs& a, dim3 grid) {
-  const dim3 block(256);
-  switch (e->nc_pad) {
-    case 1: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 1, GEN>), grid, block, 0, e->stream, a); break;
-    case 2: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 2, GEN>), grid, block, 0, e->stream, a); break;
-    case 4: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 4, GEN>), grid, block, 0, e->stream, a); break;
-    case 8: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 8, GEN>), grid, block, 0, e->stream, a); break;
-    default: hipLaunchKernelGGL((predict_var_grad_partial_kernel<KIND, 16, GEN>), grid, block, 0, e->stream, a); break;
-  }
-}
-
-int launch_predict_var_grad(gmb_engine* e, const PredVarGradArgs& a, int nchunk) {
-  const dim3 grid((unsigned)(a.test.npad / PG_PTS), (unsigned)nchunk);
-  const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
-  switch (a.p.kind) {
-    case GMB_EXPQUAD: gen ? launch_predict_var_grad_nc<0, true>(e, a, grid) : launch_predict_var_grad_nc<0, false>(e, a, grid); break;
-    case GMB_MATERN52: gen ? launch_predict_var_grad_nc<1, true>(e, a, grid) : launch_predict_var_grad_nc<1, false>(e, a, grid); break;
-    case GMB_MATERN32: gen ? launch_predict_var_grad_nc<2, true>(e, a, grid) : launch_predict_var_grad_nc<2, false>(e, a, grid); break;
-    case GMB_MATERN12: gen ? launch_predict_var_grad_nc<3, true>(e, a, grid) : launch_predict_var_grad_nc<3, false>(e, a, grid); break;
-    case GMB_EXPONENTIAL: gen ? launch_predict_var_grad_nc<4, true>(e, a, grid) : launch_predict_var_grad_nc<4, false>(e, a, grid); break;
-    default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
-  }
-  HIP_TRY(e, hipGetLastError());
-  return GMB_OK;
-}
-
-// workspaces of gmb_predict_with_grad for M-tiles of Mt rows, beside a prediction's and gmb_predict_grad's
-int predict_var_grad_workspace(gmb_engine* e, int64_t Mt) {
-  int rc;
-  if ((rc = predict_workspace(e, Mt))) return rc;
-  if ((rc = predict_grad_workspace(e, Mt))) return rc;
-  if ((rc = ensure(e, &e->vg_grad, &e->cap_vg_grad, Mt * (int64_t)e->D))) return rc;
-  // two accumulator sets: twice predict_grad_workspace's bound
-  const int64_t need = 2 * ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
-  return ensure(e, &e->vg_part, &e->cap_vg_part, need);
-}
-
 // W <- V L^-1 in dV (mpad rows, test index fastest) against the resident factor: block columns from the last
 int predict_solve_w(gmb_engine* e, int64_t mpad) {
   const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
@@ -3660,12 +3552,42 @@ int predict_solve_w(gmb_engine* e, int64_t mpad) {
   return GMB_OK;
 }
 
-// d mu / d x* and d sigma^2 / d x* of one M-tile into pg_grad and vg_grad (mc x D, row-major): the tile's raw points are in dXs
-// (predict_cross_cov), W = K(X*, X) Sigma^-1 in dV
-int predict_var_grad_tile(gmb_engine* e, int64_t mc, int64_t mpad, const double* alpha) {
+// the fit's alpha if one is resident (the gradient evaluation's, refined against L), else by back substitution, once per
+// factorisation
+int resident_alpha(gmb_engine* e, const double** alpha) {
   int rc;
+  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) return rc;
+  *alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
+  return GMB_OK;
+}
+
+// workspaces of the gradient calls for M-tiles of Mt rows (a multiple of 128), beside a prediction's: nset = 1 for
+// gmb_predict_grad, 2 for gmb_predict_with_grad
+int predict_grad_workspace(gmb_engine* e, int64_t Mt, int nset) {
+  int rc;
+  if (e->pg_cap < Mt) {
+    e->pg_cap = 0;
+    if ((rc = alloc(e, &e->pg_Xs, Mt * (int64_t)e->D))) return rc;
+    if ((rc = alloc(e, &e->pg_xs, (int64_t)17 * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_xl, (int64_t)MAX_LIN * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_cat, (int64_t)MAX_TABS * Mt))) return rc;
+    if ((rc = alloc(e, &e->pg_grad, Mt * (int64_t)e->D))) return rc;
+    e->pg_cap = Mt;
+  }
+  if (nset == 2 && (rc = ensure(e, &e->vg_grad, &e->cap_vg_grad, Mt * (int64_t)e->D))) return rc;
+  // every M-tile of mpad <= Mt rows runs nchunk <= PG_TARGET_WGS / (mpad / 64) + 1 chunks (predict_grad_chunk), so its partials
+  // -- nchunk x nset x (nc_pad + n_lin) x mpad doubles -- fit in this whatever its size
+  const int64_t need = nset * ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
+  return ensure(e, &e->pg_part, &e->cap_pg_part, need);
+}
+
+// d mu / d x* of one M-tile (mc raw points on the device, D per row, first row Xs) into pg_grad (mc x D, row-major); with
+// W = K(X*, X) Sigma^-1 of the tile (mpad rows, test index fastest) also d sigma^2 / d x* into vg_grad.  W == nullptr: the mean only.
+int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, const double* alpha, const double* W) {
+  int rc;
+  const int nset = W ? 2 : 1;
   HIP_TRY(e, hipMemsetAsync(e->pg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
-  HIP_TRY(e, hipMemsetAsync(e->vg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  if (W) HIP_TRY(e, hipMemsetAsync(e->vg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
   int64_t chunk;
   int nchunk;
   predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
@@ -3674,27 +3596,27 @@ int predict_var_grad_tile(gmb_engine* e, int64_t mc, int64_t mpad, const double*
     const gmb_engine::Term& tr = e->terms[t];
     // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
     if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
-    if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
-    PredVarGradArgs a{};
+    if ((rc = prep_points(e, Xs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
+    PredGradArgs a{};
     a.p = tr.cp;
     a.test = test;
     a.train = train_set(e);
     a.alpha = alpha;
-    a.W = e->dV;
-    a.part = e->vg_part;
+    a.W = W;
+    a.part = e->pg_part;
     a.chunk = chunk;
-    ev_begin(e, e->stream, EV_PREDICT_VGRAD, 0.0, (int)(mpad / PG_PTS), nchunk);
-    rc = launch_predict_var_grad(e, a, nchunk);
+    ev_begin(e, e->stream, W ? EV_PREDICT_VGRAD : EV_PREDICT_GRAD, 0.0, (int)(mpad / PG_PTS), nchunk);
+    rc = launch_predict_grad(e, a, nchunk, nset);
     if (!rc) {
-      PredVarGradFinishArgs v{};
-      PredGradFinishArgs& f = v.f;
-      f.part = e->vg_part;
+      PredGradFinishArgs f{};
+      f.part = e->pg_part;
       f.nchunk = nchunk;
       f.nc = tr.pa.nc;
       f.nc_pad = e->nc_pad;
       f.n_lin = tr.cp.n_lin;
       f.periodic = tr.pa.periodic;
       f.D = e->D;
+      f.nset = nset;
       f.mpad = mpad;
       f.mc = mc;
       f.txs = e->pg_xs;
@@ -3707,17 +3629,52 @@ int predict_var_grad_tile(gmb_engine* e, int64_t mc, int64_t mpad, const double*
       for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
       f.tau = tr.cp.tau;
       f.grad = e->pg_grad;
-      v.dvar = e->vg_grad;
-      v.p = tr.cp;
-      v.txl = e->pg_xl;
-      v.tcat = e->pg_cat;
-      hipLaunchKernelGGL(predict_var_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, v);
+      if (W) {
+        f.dvar = e->vg_grad;
+        f.n_tab = tr.cp.n_tab;
+        for (int i = 0; i < MAX_TABS; ++i) f.tab_levels[i] = tr.cp.tab_levels[i], f.tab_off[i] = tr.cp.tab_off[i];
+        f.tabs = tr.cp.tabs;
+        f.txl = e->pg_xl;
+        f.tcat = e->pg_cat;
+      }
+      hipLaunchKernelGGL(predict_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, f);
     }
     ev_end(e);
     if (rc) return rc;
     HIP_TRY(e, hipGetLastError());
   }
   if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+  return GMB_OK;
+}
+
+// ---- what the five prediction entry points share -------------------------------------------------------------------------------
+
+void reset_predict_timings(gmb_engine* e) {
+  gmb_timings& tm = e->tm;
+  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
+  tm.predict_gemm_launches = 0;
+}
+
+// how the caller's arrays are copied in and out
+struct CopyKinds {
+  hipMemcpyKind in, out;
+};
+CopyKinds copy_kinds(int32_t memspace) {
+  if (memspace == GMB_DEVICE) return {hipMemcpyDeviceToDevice, hipMemcpyDeviceToDevice};
+  return {hipMemcpyHostToDevice, hipMemcpyDeviceToHost};
+}
+
+// The ending of a prediction call, on every exit after its first launch (rc: what the call's work returned; tp: its phase
+// timer, if it keeps one).  Whatever happened, the stream is drained and the launches' events are collected -- none stays
+// behind for the next call's sums; predict_ms is set only by a call that succeeded; the call's own error goes before the
+// synchronise's.
+int predict_end(gmb_engine* e, PhaseTimer* tp, int rc) {
+  if (tp) tp->stop();
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  if (tp && !rc && sync == hipSuccess) e->tm.predict_ms = tp->ms();
+  ev_collect(e);
+  if (rc) return rc;
+  HIP_TRY(e, sync);
   return GMB_OK;
 }
 
@@ -3751,34 +3708,30 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
   if (e->factor_consumed)
     return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
   HIP_TRY(e, hipSetDevice(e->device));
-  gmb_timings& tm = e->tm;
-  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
-  tm.predict_gemm_launches = 0;
+  reset_predict_timings(e);
 
   const int64_t Mt = predict_tile_rows(e, M);
   if ((rc = predict_workspace(e, Mt))) return rc;
   // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
   const bool use_gemm_form = predict_takes_gemm_form(e);
   if (use_gemm_form && (rc = predict_gemm_form_workspace(e, Mt))) return rc;
-  tm.predict_gemm_form = use_gemm_form ? 1 : 0;
+  e->tm.predict_gemm_form = use_gemm_form ? 1 : 0;
 
-  const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const CopyKinds ck = copy_kinds(memspace);
   PhaseTimer tp(e);
-  for (int64_t m0 = 0; m0 < M; m0 += Mt) {
-    const int64_t mc = std::min<int64_t>(Mt, M - m0);
-    const int64_t mpad = round_up(mc, TILE);
-    if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, in_kind))) return rc;
-    if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
-    if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
-    HIP_TRY(e, hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), out_kind, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), out_kind, e->stream));
-  }
-  tp.stop();
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  tm.predict_ms = tp.ms();
-  ev_collect(e);
-  return GMB_OK;
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
+      if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
+      if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), ck.out, e->stream));
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
 }
 
 int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace) {
@@ -3789,29 +3742,22 @@ int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, d
   HIP_TRY(e, hipSetDevice(e->device));
   // 16384 points per tile: 256 blocks of 64, i.e. four chunks of the training set -- partials of 4 x the tile's gradient
   const int64_t Mt = std::min<int64_t>(round_up(M, TILE), 16384);
-  if ((rc = predict_grad_workspace(e, Mt))) return rc;
-  // alpha: the gradient evaluation's (refined against L) when one is resident, else by back substitution, once per factorisation
-  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) {
-    ev_collect(e);
-    return rc;
-  }
-  const double* alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
-  const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  for (int64_t m0 = 0; m0 < M; m0 += Mt) {
-    const int64_t mc = std::min<int64_t>(Mt, M - m0);
-    if ((rc = predict_grad_tile(e, Xs + m0 * ldxs, mc, round_up(mc, TILE), ldxs, alpha, in_kind))) break;
-    if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg_grad, e->D * sizeof(double), e->D * sizeof(double), mc, out_kind,
-                         e->stream) != hipSuccess) {
-      rc = fail(e, GMB_EHIP, "gmb_predict_grad: copying the gradient out failed");
-      break;
+  if ((rc = predict_grad_workspace(e, Mt, 1))) return rc;
+  const double* alpha = nullptr;
+  if ((rc = resident_alpha(e, &alpha))) return predict_end(e, nullptr, rc);
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      HIP_TRY(e, hipMemcpy2DAsync(e->pg_Xs, row, Xs + m0 * ldxs, ldxs * sizeof(double), row, mc, ck.in, e->stream));
+      if ((rc = predict_grad_tile(e, e->pg_Xs, mc, round_up(mc, TILE), alpha, nullptr))) return rc;
+      if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, ck.out, e->stream) != hipSuccess)
+        return fail(e, GMB_EHIP, "gmb_predict_grad: copying the gradient out failed");
     }
-  }
-  const hipError_t sync = hipStreamSynchronize(e->stream);
-  ev_collect(e);
-  if (rc) return rc;
-  HIP_TRY(e, sync);
-  return GMB_OK;
+    return GMB_OK;
+  };
+  return predict_end(e, nullptr, tiles());
 }
 
 int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
@@ -3822,43 +3768,35 @@ int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
     return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var/dmean/dvar/ldg");
   if (M == 0) return GMB_OK;
   HIP_TRY(e, hipSetDevice(e->device));
-  gmb_timings& tm = e->tm;
-  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
-  tm.predict_gemm_launches = 0;
-  tm.predict_gemm_form = 0;  // V is always solved for: W = V L^-1 follows in place, and neither dW nor U is touched
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;  // V is always solved for: W = V L^-1 follows in place, and neither dW nor U is touched
   const int64_t Mt = predict_tile_rows(e, M);
-  if ((rc = predict_var_grad_workspace(e, Mt))) return rc;
-  // alpha as in gmb_predict_grad
-  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) {
-    ev_collect(e);
-    return rc;
-  }
-  const double* alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
-  const hipMemcpyKind in_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out_kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if ((rc = predict_workspace(e, Mt))) return rc;
+  if ((rc = predict_grad_workspace(e, Mt, 2))) return rc;
+  const double* alpha = nullptr;
+  if ((rc = resident_alpha(e, &alpha))) return predict_end(e, nullptr, rc);
+  const CopyKinds ck = copy_kinds(memspace);
   const size_t row = e->D * sizeof(double);
   PhaseTimer tp(e);
-  for (int64_t m0 = 0; m0 < M && !rc; m0 += Mt) {
-    const int64_t mc = std::min<int64_t>(Mt, M - m0);
-    const int64_t mpad = round_up(mc, TILE);
-    if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, in_kind))) break;
-    if ((rc = predict_solve_v(e, mpad, false))) break;
-    if ((rc = predict_reduce(e, mc, mpad, false))) break;
-    if ((rc = predict_solve_w(e, mpad))) break;
-    if ((rc = predict_var_grad_tile(e, mc, mpad, alpha))) break;
-    if (hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), out_kind, e->stream) != hipSuccess ||
-        hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), out_kind, e->stream) != hipSuccess ||
-        hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, out_kind, e->stream) != hipSuccess ||
-        hipMemcpy2DAsync(dvar + m0 * ldg, ldg * sizeof(double), e->vg_grad, row, row, mc, out_kind, e->stream) != hipSuccess)
-      rc = fail(e, GMB_EHIP, "gmb_predict_with_grad: copying the results out failed");
-  }
-  tp.stop();
-  const hipError_t sync = hipStreamSynchronize(e->stream);
-  if (!rc && sync == hipSuccess) tm.predict_ms = tp.ms();
-  ev_collect(e);
-  if (rc) return rc;
-  HIP_TRY(e, sync);
-  return GMB_OK;
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
+      if ((rc = predict_solve_v(e, mpad, false))) return rc;
+      if ((rc = predict_reduce(e, mc, mpad, false))) return rc;
+      if ((rc = predict_solve_w(e, mpad))) return rc;
+      // (the tile's raw points are in dXs: predict_cross_cov; W = K(X*, X) Sigma^-1 in dV)
+      if ((rc = predict_grad_tile(e, e->dXs, mc, mpad, alpha, e->dV))) return rc;
+      if (hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, ck.out, e->stream) != hipSuccess ||
+          hipMemcpy2DAsync(dvar + m0 * ldg, ldg * sizeof(double), e->vg_grad, row, row, mc, ck.out, e->stream) != hipSuccess)
+        return fail(e, GMB_EHIP, "gmb_predict_with_grad: copying the results out failed");
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
 }
 
 int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
@@ -3872,31 +3810,28 @@ int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, 
   const bool host = memspace != GMB_DEVICE;
   const bool gemm_form = predict_takes_gemm_form(e);
   if ((rc = joint_workspace(e, "gmb_predict_joint", M, gemm_form, host ? (double)M * (double)M : 0.0))) return rc;
-  gmb_timings& tm = e->tm;
-  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
-  tm.predict_gemm_launches = 0;
-  tm.predict_gemm_form = gemm_form ? 1 : 0;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+  const CopyKinds ck = copy_kinds(memspace);
   PhaseTimer tp(e);
-  if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice)))
-    return rc;
-  SymArgs sa{};
-  sa.C = e->jt.dC;
-  sa.ldc = e->jt.Mr;
-  sa.out = host ? e->jt.dstage : cov;
-  sa.ldo = host ? M : ldc;
-  sa.M = M;
-  const unsigned nb = (unsigned)((M + 31) / 32);
-  hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
-  HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
-  if (host)
-    HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
-                                hipMemcpyDeviceToHost, e->stream));
-  tp.stop();
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  tm.predict_ms = tp.ms();
-  ev_collect(e);
-  return GMB_OK;
+  auto work = [&]() -> int {
+    if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
+    SymArgs sa{};
+    sa.C = e->jt.dC;
+    sa.ldc = e->jt.Mr;
+    sa.out = host ? e->jt.dstage : cov;
+    sa.ldo = host ? M : ldc;
+    sa.M = M;
+    const unsigned nb = (unsigned)((M + 31) / 32);
+    hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), ck.out, e->stream));
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
+                                  hipMemcpyDeviceToHost, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
 }
 
 int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
@@ -3910,41 +3845,34 @@ int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int
   const bool host = memspace != GMB_DEVICE;
   const bool gemm_form = predict_takes_gemm_form(e);
   if ((rc = joint_workspace(e, "gmb_draw_joint", M, gemm_form, host ? 2.0 * (double)S * (double)M : 0.0))) return rc;
-  gmb_timings& tm = e->tm;
-  tm.predict_ms = tm.predict_gemm_ms = tm.predict_gemm_flops = 0.0;
-  tm.predict_gemm_launches = 0;
-  tm.predict_gemm_form = gemm_form ? 1 : 0;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+  const CopyKinds ck = copy_kinds(memspace);
   PhaseTimer tp(e);
-  if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice)))
-    return rc;
-  if ((rc = joint_factor(e))) {
-    ev_collect(e);
-    return rc;
-  }
-  DrawArgs da{};
-  da.L = e->jt.dC;
-  da.ldl = e->jt.Mr;
-  da.mean = e->dmean;
-  da.M = M;
-  da.S = (int32_t)S;
-  if (host) {
-    double* dZ = e->jt.dstage;
-    double* dY = e->jt.dstage + S * M;
-    HIP_TRY(e, hipMemcpy2DAsync(dZ, M * sizeof(double), Z, ldz * sizeof(double), M * sizeof(double), S, hipMemcpyHostToDevice, e->stream));
-    da.Z = dZ, da.ldz = M, da.Y = dY, da.ldy = M;
-  } else {
-    da.Z = Z, da.ldz = ldz, da.Y = Y, da.ldy = ldy;
-  }
-  if ((rc = launch_draw(e, da))) return rc;
-  if (host)
-    HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
-  if (mean)
-    HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
-  tp.stop();
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  tm.predict_ms = tp.ms();
-  ev_collect(e);
-  return GMB_OK;
+  auto work = [&]() -> int {
+    if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
+    if ((rc = joint_factor(e))) return rc;
+    DrawArgs da{};
+    da.L = e->jt.dC;
+    da.ldl = e->jt.Mr;
+    da.mean = e->dmean;
+    da.M = M;
+    da.S = (int32_t)S;
+    if (host) {
+      double* dZ = e->jt.dstage;
+      double* dY = e->jt.dstage + S * M;
+      HIP_TRY(e, hipMemcpy2DAsync(dZ, M * sizeof(double), Z, ldz * sizeof(double), M * sizeof(double), S, hipMemcpyHostToDevice, e->stream));
+      da.Z = dZ, da.ldz = M, da.Y = dY, da.ldy = M;
+    } else {
+      da.Z = Z, da.ldz = ldz, da.Y = Y, da.ldy = ldy;
+    }
+    if ((rc = launch_draw(e, da))) return rc;
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
+    if (mean) HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), ck.out, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
 }
 
 int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, int64_t nc, double* out) {

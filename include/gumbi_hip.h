@@ -330,7 +330,7 @@ int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int
 int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace);
 
 /* (ABI 15) Posterior mean and variance at M points WITH their gradients with respect to the test point, d mu / d x* and
- * d sigma^2 / d x* (csrc/predict_var_grad.hpp): what a gradient-based search of an acquisition function needs per evaluation (the
+ * d sigma^2 / d x* (csrc/predict_grad.hpp): what a gradient-based search of an acquisition function needs per evaluation (the
  * reference's `propose`, gumbi/regression/botorch/GP.py).  mean, var: length M, the values of gmb_predict (solve form); dmean,
  * dvar: M x D row-major with leading dimension ldg >= D, all four in the memspace of Xs.  EVERY column of dmean and dvar is
  * written, categorical columns and the output index with 0, nothing beyond column D.  With W = K(X*, X) Sigma^-1 = V L^-1

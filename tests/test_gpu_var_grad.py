@@ -161,6 +161,27 @@ def test_m_tiles_with_a_ragged_tail(gpu):
     run_case("M-tiles")
 
 
+@pytest.mark.parametrize("name, fit", [("Matern52-N300-d3-M77", False),   # a padded prepared column, points on training points
+                                       ("Matern52-N300-d3-M77", True),    # ... with the fit's alpha as the source
+                                       ("ExpQuad-N260-d16-M50", False),   # every prepared column, a ragged last piece
+                                       ("composite_N140", False),         # linear + two tables
+                                       ("additive-N300", False),          # two terms
+                                       ("Matern52+Periodic", False), ("Periodic", False)])  # both periodic rules
+def test_mean_gradient_is_predict_grads_bit_for_bit(gpu, name, fit):
+    """One kernel forms d mu / d x* for both calls (``predict_grad_partial_kernel``, NSET = 1 and 2, set 0 the same operations),
+    and both tile M <= 16384 identically: the ``dmean`` of ``predict_with_grad`` is ``predict_grad``'s, to the bit."""
+    theta, Xs = case(name)[1], case(name)[4]
+    with engine_for(name) as eng:
+        if fit:
+            eng.evaluate(theta, grad=True)
+        else:
+            eng.factorize()
+        dmean = eng.predict_with_grad(Xs)[2]
+        G = eng.predict_grad(Xs)
+    print(f"{name}: max |dmean - G| = {float(np.max(np.abs(dmean - G))):.3e}, max |G| = {float(np.max(np.abs(G))):.3e}")
+    assert dmean.tobytes() == G.tobytes()
+
+
 # ---- 2. the two sources of alpha; the gemm-form state -----------------------------------------------------------------------------
 @pytest.mark.parametrize("N", [600, 4224])
 def test_back_substitution_and_the_fit_path_agree(gpu, N):
