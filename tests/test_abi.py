@@ -65,6 +65,39 @@ def test_struct_layouts_match_header():
         engine.KernelSpec(D=20, idx_cont=list(range(17))).to_c()
 
 
+def test_padded_buffer_helpers_round_trip_and_notice_a_touched_cell():
+    """tests/abi_forms.py, the buffers behind tests/test_gpu_abi_forms.py: an array survives ``embed``, the padding carries the
+    fill's bit pattern -- NaN included -- and one changed padding cell, in a row, behind the last row or in a vector's tail, shows."""
+    import abi_forms as AF
+
+    a = np.random.default_rng(0).standard_normal((7, 3))
+    for fill in (AF.FILL, np.nan):
+        bits = AF.bits_of(fill)
+        buf = AF.embed(a, 5, fill)
+        assert buf.flags.c_contiguous and buf.shape[1] == 5 and (buf.shape[0] - 7) * 5 >= AF.SPARE
+        assert np.array_equal(buf[:7, :3], a) and AF.untouched(buf, 3, bits, rows=7)
+        packed = AF.embed(a, 3, fill, spare=0)
+        assert packed.shape == (7, 3) and np.array_equal(packed, a) and AF.untouched(packed, 3, bits, rows=7)
+        buf[:7, :3] = -a  # the window is the caller's to write
+        assert AF.untouched(buf, 3, bits, rows=7)
+        for cell in ((2, 3), (6, 4), (7, 0), (buf.shape[0] - 1, 4)):
+            hit = buf.copy()
+            hit[cell] = 0.0
+            assert not AF.untouched(hit, 3, bits, rows=7), cell
+        hit = buf.copy()
+        hit[7, 1] = 1.0
+        assert AF.untouched(hit, 3, bits)  # (without ``rows`` only the columns are looked at)
+        vec = AF.padded(9, AF.SPARE, fill, values=np.arange(9.0))
+        assert vec.shape == (9 + AF.SPARE,) and np.array_equal(vec[:9], np.arange(9.0)) and AF.untouched(vec, 9, bits)
+        vec[9] = 0.0
+        assert not AF.untouched(vec, 9, bits)
+    assert np.isfinite(AF.FILL) and AF.bits_of(AF.FILL) == AF.FILL_BITS
+    other_nan = np.array([0x7FF8000000000001], dtype=np.uint64).view(np.float64)[0]  # NaN == NaN is false; another NaN's bits differ
+    assert not AF.untouched(AF.padded(2, 1, other_nan), 2, AF.bits_of(np.nan))
+    with pytest.raises(ValueError):
+        AF.embed(a, 2, AF.FILL)
+
+
 def test_no_cpu_fallback_without_device(lib):
     from gumbi_amd import engine
 

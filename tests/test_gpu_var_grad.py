@@ -156,9 +156,25 @@ def test_periodic_models_match_the_reference(gpu, name):
     run_case(name)
 
 
+@functools.lru_cache(maxsize=None)
+def oracle_predict(name):
+    """``O.predict`` (direct distances, with noise) at the points of a stationary case: the float64 reference of mean and variance."""
+    spec, theta, X, y, Xs, _, _ = case(name)
+    return O.predict(spec, theta, X, y, Xs, with_noise=True, dist_mode="direct")
+
+
 def test_m_tiles_with_a_ragged_tail(gpu):
-    """The call tiles M as ``gmb_predict`` does: two tiles, the second of 77 rows."""
-    run_case("M-tiles")
+    """The call tiles M as ``gmb_predict`` does: two tiles, the second of 77 rows.  ``run_case`` compares mean and variance with
+    ``Engine.predict``, which walks the same tile loop; they are therefore held to the oracle as well, at the bars of
+    tests/test_gpu_parity.py against ``O.predict(direct)``: mean 1e-10 relative, variance 1e-11 absolute (on these inputs the
+    float64 oracle is itself 1.8e-13 / 2.2e-15 from the extended-precision reference, cond(Sigma) ~ 3.7e3)."""
+    mean, var, _, _ = run_case("M-tiles")
+    mu_o, var_o = oracle_predict("M-tiles")
+    e_m, e_v = rel(mean, mu_o), float(np.max(np.abs(var - var_o)))
+    e_m2, e_v2 = rel(mean[M_TILE:], mu_o[M_TILE:]), float(np.max(np.abs(var[M_TILE:] - var_o[M_TILE:])))
+    print(f"M-tiles vs oracle: mean {e_m:.2e} (second tile {e_m2:.2e}), var {e_v:.2e} (second tile {e_v2:.2e})")
+    assert mean.shape == mu_o.shape and var.shape == var_o.shape
+    assert e_m < 1e-10 and e_v < 1e-11
 
 
 @pytest.mark.parametrize("name, fit", [("Matern52-N300-d3-M77", False),   # a padded prepared column, points on training points
