@@ -51,9 +51,9 @@ int cap_ensure(gmb_engine* e, int G, int rank, int panel_cols) {
   dist_owned(rank, G, 0, nrt, &first, &own);
   const int64_t ld_own = (int64_t)std::max(own, 1) * TILE;
   int rc;
-  if ((rc = ensure(e, &e->dAown, &e->cap_Aown, ld_own * e->Np))) return rc;
+  if ((rc = e->dAown.reserve(e->pool, ld_own * e->Np))) return rc;
   e->ld_own = ld_own;
-  if ((rc = ensure(e, &e->dPanel, &e->cap_panel, e->Nr * (int64_t)panel_cols * TILE))) return rc;
+  if ((rc = e->dPanel.reserve(e->pool, e->Nr * (int64_t)panel_cols * TILE))) return rc;
   return GMB_OK;
 }
 
@@ -92,8 +92,8 @@ int cap_staging(gmb_engine* e, int G, int w, int64_t extra_send = 0) {
   const int nrt = (int)(e->Nr / TILE);
   const int64_t need = std::max<int64_t>((int64_t)dist_max_owned(G, 0, nrt) * TILE * (int64_t)w * TILE, GACC_DOUBLES);
   int rc;
-  if ((rc = ensure(e, &e->dsend, &e->cap_send, need + extra_send))) return rc;
-  return ensure(e, &e->drecv, &e->cap_recv, std::max<int64_t>(need * G, (int64_t)GACC_DOUBLES * G));
+  if ((rc = e->dsend.reserve(e->pool, need + extra_send))) return rc;
+  return e->drecv.reserve(e->pool, std::max<int64_t>(need * G, (int64_t)GACC_DOUBLES * G));
 }
 
 // ---- factorisation ------------------------------------------------------------------------------------------------------
@@ -118,7 +118,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     int64_t need_chain = 0;
     for (const gmb_dist_step& s : plan)
       if (s.op == DIST_SQUARE || s.op == DIST_PANEL) need_chain = std::max(need_chain, s.elems);
-    if (!rc && need_chain > 0 && !(rc = ensure(e, &e->dsend2, &e->cap_send2, need_chain))) rc = ensure(e, &e->drecv2, &e->cap_recv2, need_chain * G);
+    if (!rc && need_chain > 0 && !(rc = e->dsend2.reserve(e->pool, need_chain))) rc = e->drecv2.reserve(e->pool, need_chain * G);
   }
   e->coll_count = e->coll_hash = 0;
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_factorize (set-up)"))) return rc;
@@ -192,12 +192,12 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         a.y = e->dy;
         if ((rc = launch_cov(e, a))) break;
         for (size_t t = 1; t < e->terms.size() && !rc; ++t) {
-          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[t].pa))) break;
+          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) break;
           a.p = e->terms[t].cp;
           a.accumulate = 1;
           rc = launch_cov(e, a);
         }
-        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa);
+        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa);
         break;
       }
       case DIST_SQUARE: {  // the diagonal square's block rows from their owners, then every rank factors it
@@ -381,7 +381,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   const int maxown = dist_max_owned(G, 0, nt);
   const int64_t ldv = (int64_t)maxown * TILE;
   const int cw = cap_chunk(nt);
-  if (!rc) rc = ensure(e, &e->dW, &e->cap_W, ldv * e->Np);
+  if (!rc) rc = e->dW.reserve(e->pool, ldv * e->Np);
   if (!rc) rc = grad_workspace(e);
   if (!rc) rc = cap_ensure(e, G, rank, 3 * cw);  // two panels of L (one arriving, one in use) + the chunk of U
   const int nchunks = (nt + cw - 1) / cw;
@@ -615,20 +615,16 @@ int cap_predict(gmb_engine* e, const gmb_comm* comm, const double* Xs, int64_t M
   const int64_t lo = M > 0 ? bound(rank) : 0, cnt = M > 0 ? bound(rank + 1) - lo : 0;
   const int cw = cap_chunk((int)(e->Np / TILE));
   // results of every pass are kept in a staging area of their own (the panel gathers of the passes reuse dsend / drecv)
-  double* res = nullptr;
-  int64_t cap_res = 0;
+  ScopedBuf<double> res(e->pool);
   if (!rc) rc = cap_ensure(e, G, rank, 2 * cw);  // two panels of L: one arriving, one in use
   if (!rc) rc = cap_staging(e, G, cw);
-  if (!rc) rc = ensure(e, &res, &cap_res, std::max<int64_t>(2 * width * (1 + G) + width * std::max(e->D, 1), 1));
+  if (!rc) rc = res.reserve(e->pool, std::max<int64_t>(2 * width * (1 + G) + width * std::max(e->D, 1), 1));
   // gmb_predict's own workspaces for the largest shard's M-tile, BEFORE the ranks agree to start: an allocation that fails
   // inside a pass would take its rank out of gmb_predict ahead of the solve hook, i.e. ahead of the pass's all-gathers
   if (!rc && width > 0) rc = predict_workspace(e, predict_tile_rows(e, width));
   e->coll_count = e->coll_hash = 0;
   rc = dist_agree(e, comm, rc, "gmb_dist_predict (set-up)");
-  if (rc || M == 0) {
-    release(e, res);
-    return rc;
-  }
+  if (rc || M == 0) return rc;
   // every rank runs the same number of passes over L: the largest shard in slices of the prediction's own M-tile
   int64_t mt_max = (int64_t)(8.0 * 1024 * 1024 * 1024 / 8.0 / (double)e->Np);
   mt_max = std::max<int64_t>(TILE, std::min<int64_t>(mt_max / TILE * TILE, 32768));
@@ -677,7 +673,6 @@ int cap_predict(gmb_engine* e, const gmb_comm* comm, const double* Xs, int64_t M
     }
     if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) rc = fail(e, GMB_EHIP, "hipStreamSynchronize failed");
   }
-  release(e, res);
   return rc;
 }
 

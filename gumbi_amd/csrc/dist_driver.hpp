@@ -350,9 +350,9 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
       if (s.op == DIST_TAIL) need_tail = std::max(need_tail, s.elems);
       else need = std::max(need, std::max(s.elems, s.op == DIST_SOLVE ? (int64_t)s.maxcount * TILE * (int64_t)(s.c1 - s.c0) * TILE : 0));
     }
-    if (!(rc = ensure(e, &e->dsend, &e->cap_send, need))) rc = ensure(e, &e->drecv, &e->cap_recv, need * G);
+    if (!(rc = e->dsend.reserve(e->pool, need))) rc = e->drecv.reserve(e->pool, need * G);
     // (the TAIL travels on the communication stream while the next chain uses dsend / drecv: a staging pair of its own)
-    if (!rc && need_tail > 0 && !(rc = ensure(e, &e->dsend2, &e->cap_send2, need_tail))) rc = ensure(e, &e->drecv2, &e->cap_recv2, need_tail * G);
+    if (!rc && need_tail > 0 && !(rc = e->dsend2.reserve(e->pool, need_tail))) rc = e->drecv2.reserve(e->pool, need_tail * G);
   }
   e->coll_count = e->coll_hash = 0;  // the issue log covers this call: its closing agreement compares the ranks' sequences
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_factorize (set-up)"))) return rc;
@@ -408,12 +408,12 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
         a.y = e->dy;
         if ((rc = launch_cov(e, a))) break;
         for (size_t t = 1; t < e->terms.size() && !rc; ++t) {  // additive models: accumulating passes
-          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[t].pa))) break;
+          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) break;
           a.p = e->terms[t].cp;
           a.accumulate = 1;
           rc = launch_cov(e, a);
         }
-        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa);
+        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa);
         break;
       }
       case DIST_SQUARE: {
@@ -589,10 +589,10 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   const int64_t chunk_elems = (int64_t)maxown * TILE * (int64_t)cw * TILE;
   const int64_t send_need = std::max<int64_t>(chunk_elems + ldv, GACC_DOUBLES);  // [chunk | this rank's alpha rows]
   // V = this rank's block rows of U (later: of Sigma^-1), (maxown * 128) x Np column-major
-  if (!rc) rc = ensure(e, &e->dW, &e->cap_W, ldv * e->Np);
+  if (!rc) rc = e->dW.reserve(e->pool, ldv * e->Np);
   if (!rc) rc = grad_workspace(e);
-  if (!rc) rc = ensure(e, &e->dsend, &e->cap_send, send_need);
-  if (!rc) rc = ensure(e, &e->drecv, &e->cap_recv, send_need * G);
+  if (!rc) rc = e->dsend.reserve(e->pool, send_need);
+  if (!rc) rc = e->drecv.reserve(e->pool, send_need * G);
   e->coll_count = e->coll_hash = 0;  // the issue log covers this call: its closing agreement compares the ranks' sequences
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_nlml (set-up)"))) return rc;
   *nlml = 0.5 * (double)e->N * std::log(2.0 * M_PI) + e->logdet + 0.5 * e->vnorm2;
@@ -723,8 +723,8 @@ int dist_predict(gmb_engine* e, const gmb_comm* comm, const double* Xs, int64_t 
   for (int q = 0; q < G && M > 0; ++q) width = std::max(width, bound(q + 1) - bound(q));
   const int64_t lo = M > 0 ? bound(rank) : 0, cnt = M > 0 ? bound(rank + 1) - lo : 0;
   const int64_t stage = std::max<int64_t>(std::max<int64_t>(2 * width, width * std::max(e->D, 1)), 1);
-  if (!rc) rc = ensure(e, &e->dsend, &e->cap_send, stage);
-  if (!rc) rc = ensure(e, &e->drecv, &e->cap_recv, stage * G);
+  if (!rc) rc = e->dsend.reserve(e->pool, stage);
+  if (!rc) rc = e->drecv.reserve(e->pool, stage * G);
   e->coll_count = e->coll_hash = 0;  // the issue log covers this call: its closing agreement compares the ranks' sequences
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_predict (set-up)"))) return rc;
   if (M == 0) return GMB_OK;  // the same M on every rank by contract

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/gumbi_hip.h"
+#include "device_buffers.hpp"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_splitk.hpp"
@@ -96,16 +97,15 @@ constexpr int SCAL_INFO_AT = 64, SCAL_GACC_AT = 72, SCAL_DOUBLES = SCAL_GACC_AT 
 
 // The matrix a Cholesky / triangular-solve host routine works on, said by its caller: the training factor (train_factor), the
 // joint posterior's C (joint_factor_ref), a panel window of the capacity driver (cap_window).  A VIEW: the buffers and their
-// capacities stay with their owner; only the tile kernel's control block is reached through its owner's pointer and capacity,
-// because the launches grow it (ensure).
+// capacities stay with their owner; only the tile kernel's control block is reached as its owner's buffer, because the
+// launches grow it (reserve).
 struct FactorRef {
   double* A;          // column-major, leading dimension ld: Sigma's lower triangle in, L out
   int64_t ld;
   int64_t N, Np, Nr;  // order; padded to 128; rows of the bordered layout ((N + 1) up)
   double* dinv16;     // 8 x (16 x 16) sub-block inverses per diagonal block
   double* scal;       // head of a scalar block: [0] log-det, the info word (int32) at SCAL_INFO_AT
-  uint32_t** ct;      // control block of the persistent tile kernel
-  int64_t* cap_ct;
+  DevBuf<uint32_t>* ct;  // control block of the persistent tile kernel
   int32_t* info() const { return reinterpret_cast<int32_t*>(scal + SCAL_INFO_AT); }
 };
 
@@ -126,11 +126,9 @@ struct gmb_engine {
   // data
   int64_t N = 0, Np = 0, Nr = 0, ld = 0;
   int32_t D = 0;
-  double* dX = nullptr;
-  double* dy = nullptr;
-  double* dA = nullptr;
-  double* dDinv16 = nullptr; // 8 x (16 x 16) sub-block inverses per diagonal block (triangular solves)
-  int64_t cap_A = 0, cap_dinv16 = 0;
+  DevPool pool;  // every device block of this engine (device_buffers.hpp); gmb_destroy frees them through it
+  DevBuf<double> dX, dy, dA;
+  DevBuf<double> dDinv16;  // 8 x (16 x 16) sub-block inverses per diagonal block (triangular solves)
 
   // kernel + parameters
   gmb_kernel_spec spec{};
@@ -139,12 +137,18 @@ struct gmb_engine {
   int nc_pad = 1;
   int periodic = 0;        // gmb_set_periodic: 0 off, 1 <kind>+Periodic, 2 pm.gp.cov.Periodic; the prepared columns are then 2 n_cont
   double periods[8] = {};  // T_d per continuous dimension (standardized units)
-  double* xs = nullptr;
-  double* xl = nullptr;
-  int32_t* cat = nullptr;
-  int64_t cap_pts = 0;
-  double* dtabs = nullptr;
-  double* dnoise = nullptr;
+  struct PreparedPoints : RowGroup {  // the training points as the covariance kernels read them (SoA, stride = rows)
+    DevBuf<double> xs, xl;
+    DevBuf<int32_t> cat;
+    int reserve(DevPool& pool, int64_t n) {
+      return reserve_rows(n, [&] {
+        int rc;
+        if ((rc = xs.renew(pool, (int64_t)17 * n)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * n))) return rc;
+        return cat.renew(pool, (int64_t)MAX_TABS * n);
+      });
+    }
+  } pts;
+  DevBuf<double> dtabs, dnoise;
   CovParams cp{};
   PrepArgs prep_proto{};
   // Additive models: term 0 (the global kernel) is (prep_proto, cp); term 1 + j is the kernel of
@@ -160,9 +164,9 @@ struct gmb_engine {
   std::vector<double> hnoise;
 
   // factorisation results
-  double* dscal = nullptr;  // the scalar block (SCAL_DOUBLES): [0] logdet, [1] |v|^2, [2..] partials of that sum
+  DevBuf<double> dscal;     // the scalar block (SCAL_DOUBLES, uncounted): [0] logdet, [1] |v|^2, [2..] partials of that sum
   int32_t* dinfo = nullptr; // = dscal + SCAL_INFO_AT (and dgpart = dscal + SCAL_GACC_AT)
-  double* dv = nullptr;
+  DevBuf<double> dv;
   bool factored = false;
   // which path produced the resident factorisation (meaningful while `factored`): the single-engine and the replicated
   // multi-GPU paths leave the COMPLETE factor in dA; the capacity driver leaves this rank's rows in dAown and nothing in dA
@@ -170,62 +174,69 @@ struct gmb_engine {
   int factor_kind = FK_NONE;
   bool factor_consumed = false;  // U = L^-T sits in the factor buffer's diagonal tiles (multi-GPU gradient; or a failed one)
   bool have_alpha = false;       // dalpha holds Sigma^-1 y of the current factorisation
-  double* dDiagSave = nullptr;   // the factor's diagonal blocks while the gradient keeps U in their place
-  int64_t cap_diag = 0;
-  double* dsk = nullptr;         // partials of the split-k product (gemm_splitk.hpp): [tile][slice][128 * 128]
-  int64_t cap_sk = 0;
+  DevBuf<double> dDiagSave;      // the factor's diagonal blocks while the gradient keeps U in their place
+  DevBuf<double> dsk;            // partials of the split-k product (gemm_splitk.hpp): [tile][slice][128 * 128]
   int64_t notpd = -1;
   double logdet = 0.0, vnorm2 = 0.0;
 
-  // predict workspace
-  int64_t Mt_cap = 0;
-  double* dV = nullptr;
+  // predict workspace: what an M-tile of Mt rows needs (predict_workspace)
+  struct PredictWorkspace : RowGroup {
+    DevBuf<double> dV, dXs, txs, txl;
+    DevBuf<int32_t> tcat;
+    DevBuf<double> dkss, dmean, dvar;
+    int reserve(DevPool& pool, int64_t Mt, int64_t Np, int D) {
+      return reserve_rows(Mt, [&] {
+        int rc;
+        if ((rc = dV.renew(pool, Mt * Np)) || (rc = dXs.renew(pool, Mt * (int64_t)D)) || (rc = txs.renew(pool, (int64_t)17 * Mt)) ||
+            (rc = txl.renew(pool, (int64_t)MAX_LIN * Mt)) || (rc = tcat.renew(pool, (int64_t)MAX_TABS * Mt)) ||
+            (rc = dkss.renew(pool, Mt)) || (rc = dmean.renew(pool, Mt)))
+          return rc;
+        return dvar.renew(pool, Mt);
+      });
+    }
+  } pw;
   // GEMM-form prediction (predict_form.hpp): behind a gradient on the tile path U = L^-T of the resident factor sits in the
   // factor buffer's upper triangle + dUdiag (`u_valid`); the first prediction transposes it into dW's lower triangle
   // (`linv_valid`; Sigma^-1 is dead by then) and every prediction until the next factorisation is one GEMM into dV2
   bool u_valid = false, linv_valid = false;
   int predict_form = -1;   // -1 = GEMM form whenever U is there; 0 = always the triangular solve; 1 = as -1 (explicit)
-  double* dV2 = nullptr;   // Np x Mt: the solved cross-covariance with the TRAINING index fastest
-  int64_t Mt2_cap = 0;
+  struct GemmFormWorkspace : RowGroup {
+    DevBuf<double> dV2;    // Np x Mt: the solved cross-covariance with the TRAINING index fastest
+    int reserve(DevPool& pool, int64_t Mt, int64_t Np) {
+      return reserve_rows(Mt, [&] { return dV2.renew(pool, Mt * Np); });
+    }
+  } pw2;
   JointState jt;           // the second matrix of gmb_predict_joint / gmb_draw_joint (joint_predict.hpp)
-  double* dXs = nullptr;
-  double* txs = nullptr;
-  double* txl = nullptr;
-  int32_t* tcat = nullptr;
-  double* dkss = nullptr;
-  double* dpart = nullptr;
-  double* dmean = nullptr;
-  double* dvar = nullptr;
-  int64_t cap_part = 0;
+  DevBuf<double> dpart;    // the prediction's chunked partial sums (2 x chunks x pw.rows)
   // gmb_predict_grad (predict_grad.hpp): workspaces of its own -- a prediction's (Mt x Np and friends) stay as they are --
   // and alpha by back substitution for the states in which no gradient evaluation left one (`have_alpha` false); `bs_valid`
   // falls wherever the factorisation does
-  double* pg_Xs = nullptr;
-  double* pg_xs = nullptr;
-  double* pg_xl = nullptr;
-  int32_t* pg_cat = nullptr;
-  double* pg_grad = nullptr;
-  int64_t pg_cap = 0;
-  double* pg_part = nullptr;
-  int64_t cap_pg_part = 0;
-  double* dalpha_bs = nullptr;  // Np: alpha, then Np: the running right-hand side
-  int64_t cap_alpha_bs = 0;
+  struct PredictGradWorkspace : RowGroup {
+    DevBuf<double> Xs, xs, xl;
+    DevBuf<int32_t> cat;
+    DevBuf<double> grad;
+    int reserve(DevPool& pool, int64_t Mt, int D) {
+      return reserve_rows(Mt, [&] {
+        int rc;
+        if ((rc = Xs.renew(pool, Mt * (int64_t)D)) || (rc = xs.renew(pool, (int64_t)17 * Mt)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * Mt)) ||
+            (rc = cat.renew(pool, (int64_t)MAX_TABS * Mt)))
+          return rc;
+        return grad.renew(pool, Mt * (int64_t)D);
+      });
+    }
+  } pg;
+  DevBuf<double> pg_part;
+  DevBuf<double> dalpha_bs;  // Np: alpha, then Np: the running right-hand side
   bool bs_valid = false;
   // gmb_predict_with_grad: the variance gradient of an M-tile (its partials are a second set in pg_part)
-  double* vg_grad = nullptr;
-  int64_t cap_vg_grad = 0;
+  DevBuf<double> vg_grad;
 
   // gradient workspace
-  double* dW = nullptr;  // Np x Np column-major: L^-1 then Sigma^-1
-  int64_t cap_W = 0;
-  double* dalpha = nullptr;
-  int64_t cap_pts_alpha = 0;
-  double* dgpart = nullptr;   // accumulators of the trace reductions (GACC_DOUBLES) + 64 doubles of scratch
-  int64_t cap_gpart = 0;
-  double* dgred = nullptr;    // per-workgroup partial vectors of grad_tile_kernel (two-stage, fixed-order sums)
-  int64_t cap_gred = 0;
-  double* dgbig = nullptr;    // per-wave copies of coregion tables with more than 8 levels
-  int64_t cap_gbig = 0;
+  DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
+  DevBuf<double> dalpha;
+  double* dgpart = nullptr;   // = dscal + SCAL_GACC_AT: accumulators of the trace reductions (GACC_DOUBLES) + 64 doubles of scratch
+  DevBuf<double> dgred;       // per-workgroup partial vectors of grad_tile_kernel (two-stage, fixed-order sums)
+  DevBuf<double> dgbig;       // per-wave copies of coregion tables with more than 8 levels
 
   // cached launch plan of the batched levels of the triangular inverse (static per data set)
   struct InvLevelPlan {
@@ -238,8 +249,8 @@ struct gmb_engine {
     double flops[2] = {0.0, 0.0};
   };
   std::vector<InvLevelPlan> inv_plan;  // indexed by depth; count == 0 -> level not batched
-  GemmArgs* dplan_gemm = nullptr;
-  TransposeJob* dplan_tr = nullptr;
+  DevBuf<GemmArgs> dplan_gemm;  // (uncounted, as dplan_tr)
+  DevBuf<TransposeJob> dplan_tr;
   int64_t plan_N = -1, plan_ld = -1, plan_Np = -1;
   const double* plan_W = nullptr;
   const double* plan_A = nullptr;
@@ -268,10 +279,8 @@ struct gmb_engine {
   // -1 = by size; 0 = plain recursion; 2 = masked look-ahead; 3 = persistent tile kernel (chol_tiles.hpp)
   int chol_scheme = -1;
   // persistent tile Cholesky: control words + per-tile flags (zeroed before every launch), optional task trace
-  uint32_t* dct = nullptr;
-  int64_t cap_ct = 0;
-  unsigned long long* dct_trace = nullptr;
-  int64_t cap_ct_trace = 0;
+  DevBuf<uint32_t> dct;
+  DevBuf<unsigned long long> dct_trace;
   bool ct_trace = false;
   CholResult chol;           // what the tile kernel did in the last TRAINING factorisation
   int ct_lose = 0;           // fault injection (gmb_debug_chol_lose_tickets): one shot
@@ -307,17 +316,14 @@ struct gmb_engine {
   // when the caller asks for the gradient together with the factorisation (gmb_evaluate)
   int grad_scheme = -1;        // -1 = by size; 0 = launch tree (winv_levels); 1 = tile tasks behind the factorisation; 2 = fused
   int et_lag = -1;             // the INV tasks of column c - lag follow the CHOL tasks of column c in the task list (-1: by size)
-  uint32_t* det_tasks = nullptr;  // task list on the device, and what it was built for
-  int64_t cap_et_tasks = 0;
+  DevBuf<uint32_t> det_tasks;  // task list on the device, and what it was built for
   int et_key[5] = {-1, -1, -1, -1, -1};
   int et_pairs = -1;           // Sigma^-1 tasks of two tiles (128 x 256; eval_tiles.hpp: et_zz2_task): -1 = by size, 0 = off, 1 = on
   int et_pairs_min_blocks = 72;  // (measured, profiles/r05_eval_pairs_ab.txt: +19 % at 24 block columns, +8 % at 41, 0 at 50 - 64,
                                  //  -0.7 % at 79, -1.0 ... -1.2 % at 128 - 157: a pair halves the number of tasks the tail is balanced with)
   int et_ntasks = 0;
-  double* dUdiag = nullptr;    // diagonal tiles of U = L^-T
-  int64_t cap_udiag = 0;
-  double* dApart = nullptr;    // partial products U(r,c) v_c
-  int64_t cap_apart = 0;
+  DevBuf<double> dUdiag;       // diagonal tiles of U = L^-T
+  DevBuf<double> dApart;       // partial products U(r,c) v_c
   bool et_fused = false;       // the factorisation in flight carries INV / ZZ tasks: Sigma^-1 (dW) and the alpha parts come with it
   int et_min_blocks = 1;       // smallest matrix (in 128-blocks) whose MAP evaluation runs as the fused launch by default
   // the bottom of the plain recursion (matrices beyond tiles_max_blocks): panels of <= panel_tiles_w block columns, with every
@@ -340,32 +346,23 @@ struct gmb_engine {
   bool aux_borrowed = false;  // aux[0..2] belong to the engine this one was created beside (gmb_create_sibling)
   int part_cus = 0;         // compute units the masked stream leaves free
   // multi-GPU driver (dist_driver.hpp): packed send / receive staging of the all-gathers
-  double* dsend = nullptr;
-  double* drecv = nullptr;
-  int64_t cap_send = 0, cap_recv = 0;
-  double* dsend2 = nullptr;  // ... and of the panel columns' TAILs, which travel on the communication stream beside the next chain
-  double* drecv2 = nullptr;
-  int64_t cap_send2 = 0, cap_recv2 = 0;
+  DevBuf<double> dsend, drecv;
+  DevBuf<double> dsend2, drecv2;  // ... and of the panel columns' TAILs, which travel on the communication stream beside the next chain
   int panel_blocks = 8;
   bool panel_auto = true;  // panel width grows with the matrix (GMB_PANEL_BLOCKS pins it)
-  // every device buffer obtained through ensure / alloc, with its size (gmb_resident_bytes)
-  std::unordered_map<void*, size_t> allocs;
-  int64_t bytes_resident = 0, bytes_peak = 0;
   // Multi-GPU driver, CAPACITY mode (gmb_dist_set_mode(e, 1); dist_capacity.hpp): no rank holds the whole factor.  dAown =
   // this rank's block rows, packed ((owned blocks * 128) rows x Np columns); dPanel = one column panel of L with ALL its rows
   // (what a panel all-gather delivers), addressed through a virtual full-buffer base so that every kernel written for the
   // replicated layout works on it unchanged -- two of them (the factorisation's look-ahead; the gradient: one panel of L and
   // one column chunk of U = L^-T with all its rows).
   int dist_mode = 0;
-  double* dAown = nullptr;
-  int64_t cap_Aown = 0;
+  DevBuf<double> dAown;
   int64_t ld_own = 0;
   int own_world = -1, own_rank = -1;  // what dAown holds the rows of
-  double* dPanel = nullptr;
-  int64_t cap_panel = 0;
+  DevBuf<double> dPanel;
   // gmb_predict's triangular solve V <- V L^-T, when somebody else has to do it (the capacity driver streams L through)
   std::function<int(double*, int64_t, int)> solve_hook;
-  double* dstat = nullptr;  // status words (+ payload) the ranks exchange: this rank's, then everybody's (dist_agree)
+  DevBuf<double> dstat;     // (uncounted) status words (+ payload) the ranks exchange: this rank's, then everybody's (dist_agree)
   // Every collective this engine has issued on a transport, in host issue order: count and a running hash of (element count,
   // stream).  RCCL matches the collectives of a communicator by ISSUE ORDER on every rank -- and gmb_dist_nlml issues them on
   // two streams -- so the ranks compare these two words whenever they agree on a status: a rank that issued a different
@@ -395,46 +392,13 @@ int fail(gmb_engine* e, int code, const char* fmt, ...) {
                   __FILE__, __LINE__);                                                \
   } while (0)
 
-// device allocations of an engine go through ensure / alloc / release, which keep the engine's resident byte count
-// (gmb_resident_bytes: what the multi-GPU driver's capacity mode is judged by)
-void release(gmb_engine* e, void* p) {
-  if (!p) return;
-  if (e) {
-    auto it = e->allocs.find(p);
-    if (it != e->allocs.end()) {
-      e->bytes_resident -= (int64_t)it->second;
-      e->allocs.erase(it);
-    }
-  }
-  (void)hipFree(p);
-}
-
-template <typename T>
-int ensure(gmb_engine* e, T** p, int64_t* cap, int64_t need) {
-  if (*cap >= need && *p) return GMB_OK;
-  release(e, (void*)*p);
-  *p = nullptr;
-  *cap = 0;
-  if (need < 1) need = 1;
-  hipError_t s = hipMalloc((void**)p, (size_t)need * sizeof(T));
-  if (s != hipSuccess)
-    return fail(e, GMB_ENOMEM, "hipMalloc of %lld bytes failed: %s", (long long)(need * sizeof(T)),
-                hipGetErrorString(s));
-  *cap = need;
-  if (e) {
-    e->allocs[(void*)*p] = (size_t)need * sizeof(T);
-    e->bytes_resident += (int64_t)((size_t)need * sizeof(T));
-    e->bytes_peak = std::max(e->bytes_peak, e->bytes_resident);
-  }
-  return GMB_OK;
-}
-
-template <typename T>
-int alloc(gmb_engine* e, T** p, int64_t need) {
-  int64_t cap = 0;
-  release(e, (void*)*p);
-  *p = nullptr;
-  return ensure(e, p, &cap, need);
+// Device memory of an engine: every block belongs to the engine's DevPool (device_buffers.hpp) and is held by a DevBuf field of
+// gmb_engine / JointState, by a row group of such fields, or by a ScopedBuf on the stack.  A buffer is declared once and sized
+// where it is used, with reserve (keep what is large enough), renew (always a fresh block) or a group's reserve(rows); nothing
+// else has to know about it: the pool keeps the byte count (gmb_resident_bytes: what the multi-GPU driver's capacity mode is
+// judged by) and gmb_destroy frees whatever is live.  What the pool could not get is reported here.
+int alloc_refused(void* owner, size_t bytes, const char* why) {
+  return fail(static_cast<gmb_engine*>(owner), GMB_ENOMEM, "hipMalloc of %lld bytes failed: %s", (long long)bytes, why);
 }
 
 int pick_nc(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : 16; }
@@ -953,9 +917,9 @@ int apply_theta(gmb_engine* e) {
   if (s.additive) k += s.n_coreg * (n_ls + 1 + (s.n_lin > 0 ? s.n_lin + 1 : 0));
   if (k != (int)e->theta.size()) return fail(e, GMB_EINVAL, "internal: theta packing mismatch");
   if (!e->dtabs) {
-    int rc = alloc(e, &e->dtabs, (int64_t)MAX_TABS * GMB_MAX_LEVELS * GMB_MAX_LEVELS);
+    int rc = e->dtabs.renew(e->pool, (int64_t)MAX_TABS * GMB_MAX_LEVELS * GMB_MAX_LEVELS);
     if (rc) return rc;
-    rc = alloc(e, &e->dnoise, (int64_t)GMB_MAX_LEVELS);
+    rc = e->dnoise.renew(e->pool, (int64_t)GMB_MAX_LEVELS);
     if (rc) return rc;
   }
   if (!e->htabs.empty())
@@ -1048,16 +1012,31 @@ int prep_points(gmb_engine* e, const double* dXraw, int64_t n, int64_t ldx, int6
 int flush_deferred_prep(gmb_engine* e) {
   if (!e->prep_deferred) return GMB_OK;
   e->prep_deferred = false;
-  return prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat);
+  return prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat);
 }
 
-PointSet train_set(const gmb_engine* e) { return PointSet{e->xs, e->xl, e->cat, e->N, e->Nr}; }
+// N (hence Np, Nr, ld) changes -- gmb_set_data, resize_n: every workspace whose size or layout follows from them is stale, and
+// so is the cached launch plan of the triangular inverse.  The union of what the two sites used to mark, one line each:
+//   * prep_deferred was cleared by resize_n only.  It is raised by gmb_set_theta inside a gmb_evaluate and lowered again before
+//     that gmb_evaluate returns (build_sigma consumes it, flush_deferred_prep otherwise), so it is false on entry to either
+//     site and clearing it is a no-op at both.
+//   * the prepared points (pts) were marked by gmb_set_data only and stay there: resize_n keeps them when they are large enough.
+void stale_sized_by_n(gmb_engine* e) {
+  e->pw.stale();
+  e->pw2.stale();
+  e->dpart.stale();
+  e->pg.stale();
+  e->plan_N = -1;
+  e->prep_deferred = false;
+}
+
+PointSet train_set(const gmb_engine* e) { return PointSet{e->pts.xs, e->pts.xl, e->pts.cat, e->N, e->Nr}; }
 
 // the full factor buffer (Nr x Np, leading dimension Nr), allocated on first use
-int ensure_factor_buffer(gmb_engine* e) { return ensure(e, &e->dA, &e->cap_A, e->ld * e->Np); }
+int ensure_factor_buffer(gmb_engine* e) { return e->dA.reserve(e->pool, e->ld * e->Np); }
 
 // the training factor as the Cholesky / triangular-solve routines take it
-FactorRef train_factor(gmb_engine* e) { return FactorRef{e->dA, e->ld, e->N, e->Np, e->Nr, e->dDinv16, e->dscal, &e->dct, &e->cap_ct}; }
+FactorRef train_factor(gmb_engine* e) { return FactorRef{e->dA, e->ld, e->N, e->Np, e->Nr, e->dDinv16, e->dscal, &e->dct}; }
 
 // Covariance build: lower-triangular tiles of Sigma = K + noise + jitter, the y row, identity padding, written
 // column-major into `out` (Nr x Np, leading dimension ldo) -- the factor buffer in gmb_factorize.
@@ -1079,18 +1058,18 @@ int build_sigma(gmb_engine* e, double* out, int64_t ldo) {
   if (e->prep_deferred) {  // small gmb_evaluate: this launch prepares the points it stages (and clears prep_points_kernel's words)
     e->prep_deferred = false;
     a.inline_prep = 1;
-    a.prep = prep_args(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, nullptr);
+    a.prep = prep_args(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, nullptr);
   }
   if ((rc = launch_cov(e, a))) return rc;
   // additive models: the other terms add their covariance to the real entries, one pass each
   for (size_t t = 1; t < e->terms.size(); ++t) {
-    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[t].pa))) return rc;
+    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) return rc;
     a.p = e->terms[t].cp;
     a.accumulate = 1;
     if ((rc = launch_cov(e, a))) return rc;
   }
   if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa)))
+      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
     return rc;
   return GMB_OK;
 }
@@ -1205,7 +1184,7 @@ int tiles_lose_tickets(gmb_engine* e, hipStream_t s, uint32_t* ctl, int lose) {
 // a traced launch stamps its tasks into the engine's trace buffer (gmb_chol_task_trace), cleared here
 int tiles_trace_buffer(gmb_engine* e, hipStream_t s, CholTilesArgs& a) {
   int rc;
-  if ((rc = ensure(e, &e->dct_trace, &e->cap_ct_trace, 4 * (int64_t)a.ntasks))) return rc;
+  if ((rc = e->dct_trace.reserve(e->pool, 4 * (int64_t)a.ntasks))) return rc;
   HIP_TRY(e, hipMemsetAsync(e->dct_trace, 0, (size_t)a.ntasks * 4 * sizeof(unsigned long long), s));
   a.dbg = e->dct_trace;
   return GMB_OK;
@@ -1217,7 +1196,7 @@ int chol_tiles(gmb_engine* e, hipStream_t s, const FactorRef& f, bool trace, int
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
-  if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
+  if ((rc = f.ct->reserve(e->pool, words))) return rc;
   HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), s));
   res->injected = lose > 0;
   if (lose > 0 && (rc = tiles_lose_tickets(e, s, *f.ct, lose))) return rc;
@@ -1256,7 +1235,7 @@ int chol_tiles_panel(gmb_engine* e, hipStream_t s, const FactorRef& f, int c0, i
   const int ntasks = ct_task_count(nct, nrt);
   const int64_t words = 4 + (int64_t)nrt * nct + 3 * (int64_t)nct;
   int rc;
-  if ((rc = ensure(e, f.ct, f.cap_ct, std::max<int64_t>(words, 4 + (int64_t)(e->panel_tiles_w + 3) * (f.Nr / TILE))))) return rc;  // (one size for every panel of the matrix)
+  if ((rc = f.ct->reserve(e->pool, std::max<int64_t>(words, 4 + (int64_t)(e->panel_tiles_w + 3) * (f.Nr / TILE))))) return rc;  // (one size for every panel of the matrix)
   HIP_TRY(e, hipMemsetAsync(*f.ct, 0, sizeof(uint32_t), s));                                  // the ticket counter
   HIP_TRY(e, hipMemsetAsync(*f.ct + 2, 0, (size_t)(words - 2) * sizeof(uint32_t), s));       // flags and chain words
   const CholTilesArgs a = tiles_args(f, c0, nct, nrt, ntasks);
@@ -1277,7 +1256,7 @@ int trsm_tiles(gmb_engine* e, hipStream_t s, const FactorRef& f, double* V, int6
   if (ntasks <= 0) return GMB_OK;
   const int64_t words = 4 + (int64_t)ntm * nct;
   int rc;
-  if ((rc = ensure(e, f.ct, f.cap_ct, words))) return rc;
+  if ((rc = f.ct->reserve(e->pool, words))) return rc;
   HIP_TRY(e, hipMemsetAsync(*f.ct, 0, (size_t)words * sizeof(uint32_t), s));
   CholTilesArgs a = tiles_args(f, 0, nct, nct, (int)ntasks, false);
   a.V = V;
@@ -1327,7 +1306,7 @@ int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
   if (e->et_key[0] != nct || e->et_key[1] != nrt || e->et_key[2] != (int)with_chol || e->et_key[3] != lag || e->et_key[4] != pairs) {
     std::vector<uint32_t> list;
     et_build_tasks(nct, nrt, with_chol, lag, list, pairs != 0);
-    if ((rc = ensure(e, &e->det_tasks, &e->cap_et_tasks, (int64_t)list.size()))) return rc;
+    if ((rc = e->det_tasks.reserve(e->pool, (int64_t)list.size()))) return rc;
     HIP_TRY(e, hipMemcpy(e->det_tasks, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     e->et_key[0] = nct;
     e->et_key[1] = nrt;
@@ -1339,11 +1318,11 @@ int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
   const int ntasks = e->et_ntasks;
   const int64_t chol_words = (int64_t)nrt * nct + 3 * (int64_t)nct;
   const int64_t words = eval_tiles_words(nct, nrt);
-  if ((rc = ensure(e, &e->dct, &e->cap_ct, words + 2))) return rc;
-  if ((rc = ensure(e, &e->dW, &e->cap_W, e->Np * e->Np))) return rc;
+  if ((rc = e->dct.reserve(e->pool, words + 2))) return rc;
+  if ((rc = e->dW.reserve(e->pool, e->Np * e->Np))) return rc;
   e->u_valid = e->linv_valid = false;  // (U is rewritten, Sigma^-1 takes dW: set again once the launch is known to have succeeded)
-  if ((rc = ensure(e, &e->dUdiag, &e->cap_udiag, (int64_t)nct * TILE * TILE))) return rc;
-  if ((rc = ensure(e, &e->dApart, &e->cap_apart, (int64_t)nct * nct * TILE + nct))) return rc;  // (+ the partials of |v|^2)
+  if ((rc = e->dUdiag.reserve(e->pool, (int64_t)nct * TILE * TILE))) return rc;
+  if ((rc = e->dApart.reserve(e->pool, (int64_t)nct * nct * TILE + nct))) return rc;  // (+ the partials of |v|^2)
   if ((rc = grad_workspace(e))) return rc;
   if (!(with_chol && e->prezeroed)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), s));
   // a factor that is final already: every tile flag reads "final" (any non-zero word)
@@ -1479,7 +1458,7 @@ int chol_factor(gmb_engine* e, const FactorRef& f, const CholOpts& o, CholResult
   const bool tile_panels = !e->naive_leaf && !e->panel_tiles_veto && e->panel_tiles_w >= 2 && e->chol_scheme != 0;
   if (tile_panels) {
     int rc;
-    if ((rc = ensure(e, f.ct, f.cap_ct, 4 + (int64_t)(e->panel_tiles_w + 3) * nrt))) return rc;
+    if ((rc = f.ct->reserve(e->pool, 4 + (int64_t)(e->panel_tiles_w + 3) * nrt))) return rc;
     HIP_TRY(e, hipMemsetAsync(*f.ct, 0, 4 * sizeof(uint32_t), e->stream));  // (the abort word: once per factorisation)
   }
   return chol_cols(e, e->stream, f, 0, nblocks, nrt, EV_CHOL_UPDATE, tile_panels ? res : nullptr);
@@ -1720,14 +1699,12 @@ int build_inv_plan(gmb_engine* e, const std::vector<std::vector<InvNode>>& level
       }
     }
   }
-  if (e->dplan_gemm) (void)hipFree(e->dplan_gemm);
-  if (e->dplan_tr) (void)hipFree(e->dplan_tr);
-  e->dplan_gemm = nullptr;
-  e->dplan_tr = nullptr;
+  e->dplan_gemm.drop(e->pool);
+  e->dplan_tr.drop(e->pool);
   e->plan_N = -1;
   if (!hg.empty()) {
-    HIP_TRY(e, hipMalloc((void**)&e->dplan_gemm, hg.size() * sizeof(GemmArgs)));
-    HIP_TRY(e, hipMalloc((void**)&e->dplan_tr, ht.size() * sizeof(TransposeJob)));
+    int rc;
+    if ((rc = e->dplan_gemm.renew(e->pool, (int64_t)hg.size(), false)) || (rc = e->dplan_tr.renew(e->pool, (int64_t)ht.size(), false))) return rc;
     HIP_TRY(e, hipMemcpy(e->dplan_gemm, hg.data(), hg.size() * sizeof(GemmArgs), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(e->dplan_tr, ht.data(), ht.size() * sizeof(TransposeJob), hipMemcpyHostToDevice));
   }
@@ -1799,10 +1776,7 @@ int launch_grad_nc(gmb_engine* e, const GradArgs& a_in, int nblocks) {
 //     from 64.  `h` receives the raw accumulators: plain sums over tiles, so shards of several GPUs add up.
 int grad_workspace(gmb_engine* e) {
   int rc;
-  if (e->cap_pts_alpha < 3 * e->Np) {  // alpha | the refinement's residual t | its correction (refine_alpha)
-    if ((rc = alloc(e, &e->dalpha, 3 * e->Np))) return rc;
-    e->cap_pts_alpha = 3 * e->Np;
-  }
+  if ((rc = e->dalpha.reserve(e->pool, 3 * e->Np))) return rc;  // alpha | the refinement's residual t | its correction (refine_alpha)
   return GMB_OK;  // (the accumulators live in the engine's scalar block)
 }
 
@@ -1850,7 +1824,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
   GradFinishArgs fin{};
   for (size_t t = 0; t < e->terms.size(); ++t) {
     const gmb_engine::Term& tr = e->terms[t];
-    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
+    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
     GradArgs a{};
     a.p = tr.cp;
     a.pts = train_set(e);
@@ -1901,10 +1875,10 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
     a.gsplit = ndirect <= 512 ? 4 : 1;
     const int nvec = a.split ? ndirect * a.gsplit + grid : ndirect * a.gsplit;  // partial vectors the pass leaves
     if (grid > 0) {
-      if ((rc = ensure(e, &e->dgred, &e->cap_gred, (int64_t)nvec * a.part_stride))) return rc;
+      if ((rc = e->dgred.reserve(e->pool, (int64_t)nvec * a.part_stride))) return rc;
       a.part = e->dgred;
       if (big > 0) {
-        if ((rc = ensure(e, &e->dgbig, &e->cap_gbig, (int64_t)ndirect * a.gsplit * 4 * big))) return rc;
+        if ((rc = e->dgbig.reserve(e->pool, (int64_t)ndirect * a.gsplit * 4 * big))) return rc;
         HIP_TRY(e, hipMemsetAsync(e->dgbig, 0, (size_t)ndirect * a.gsplit * 4 * big * sizeof(double), e->stream));
         a.big = e->dgbig;
       }
@@ -1977,7 +1951,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
     }
   }
   if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa)))
+      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
     return rc;
   h.assign(GACC_DOUBLES, 0.0);
   if (e->light) {
@@ -2049,7 +2023,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   int rc;
   gmb_timings& tm = e->tm;
   tm.grad_ms = tm.grad_gemm_ms = tm.grad_gemm_flops = 0.0;
-  if ((rc = ensure(e, &e->dW, &e->cap_W, e->Np * e->Np))) return rc;
+  if ((rc = e->dW.reserve(e->pool, e->Np * e->Np))) return rc;
   if ((rc = grad_workspace(e))) return rc;
   const int nt = (int)(e->Np / TILE);
   if (e->et_fused || grad_by_tiles(e)) {
@@ -2091,7 +2065,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
     e->u_valid = true;
     return GMB_OK;
   }
-  if ((rc = ensure(e, &e->dDiagSave, &e->cap_diag, (int64_t)nt * TILE * TILE))) return rc;
+  if ((rc = e->dDiagSave.reserve(e->pool, (int64_t)nt * TILE * TILE))) return rc;
   e->u_valid = e->linv_valid = false;
   PhaseTimer tg(e);
   // the diagonal blocks of L are put back at the end: U takes their place in between
@@ -2247,7 +2221,7 @@ int require_ready(gmb_engine* e, bool need_factor) {
 // multi-GPU passes) against a factorisation of the capacity driver, which leaves none there -- and the reverse: the capacity
 // passes against anything else than a capacity factorisation (their dAown would be an older theta's).
 int require_full_factor(gmb_engine* e, const char* what) {
-  if (e->factor_kind == gmb_engine::FK_CAPACITY || !e->dA || e->cap_A <= 0)
+  if (e->factor_kind == gmb_engine::FK_CAPACITY || !e->dA || e->dA.cap <= 0)
     return fail(e, GMB_EINVAL, "%s needs the complete factor on this device, but the resident factorisation is a capacity-mode one "
                                "(gmb_dist_set_mode(e, 1): no rank holds the factor) -- use the gmb_dist_* calls, or gmb_factorize first", what);
   return GMB_OK;
@@ -2392,8 +2366,10 @@ int gmb_create_impl(gmb_engine** out, int32_t device, void* stream, const gmb_en
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) e->wg_slots = 2LL * prop.multiProcessorCount;
-  if (hipMalloc((void**)&e->dscal, (size_t)SCAL_DOUBLES * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&e->dstat, (size_t)(DIST_HEADER + DIST_MAX_PAYLOAD) * (1 + DIST_MAX_WORLD) * sizeof(double)) != hipSuccess) {
+  e->pool.owner = e;
+  e->pool.refused = alloc_refused;
+  // (uncounted: fixed overhead of every engine, not what gmb_resident_bytes reports)
+  if (e->dscal.renew(e->pool, SCAL_DOUBLES, false) || e->dstat.renew(e->pool, (DIST_HEADER + DIST_MAX_PAYLOAD) * (1 + DIST_MAX_WORLD), false)) {
     gmb_destroy(e);
     return GMB_ENOMEM;
   }
@@ -2434,14 +2410,7 @@ void gmb_destroy(gmb_engine* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (int a = 0; a < 3; ++a)
     if (e->aux[a]) (void)hipStreamSynchronize(e->aux[a]);
-  void* ptrs[] = {e->dct, e->dct_trace, e->dstat, e->dDiagSave, e->dsend, e->drecv, e->dplan_gemm, e->dplan_tr, e->dDinv16, e->dX, e->dy, e->dA, e->xs, e->xl, e->cat, e->dtabs,
-                  e->dnoise, e->dscal, e->dv, e->dV, e->dXs, e->txs, e->txl,
-                  e->tcat, e->dkss, e->dpart, e->dmean, e->dvar, e->dW, e->dalpha, e->dgred, e->dgbig, e->det_tasks, e->dUdiag, e->dApart,
-                  e->dAown, e->dPanel, e->dV2, e->dsend2, e->drecv2,
-                  e->jt.dC, e->jt.dDinv16, e->jt.dscal, e->jt.dct, e->jt.dzero, e->jt.dstage,
-                  e->pg_Xs, e->pg_xs, e->pg_xl, e->pg_cat, e->pg_grad, e->pg_part, e->dalpha_bs, e->vg_grad, e->dsk};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  e->pool.release_all();
   for (int a = 0; a < 3; ++a)
     if (e->aux[a] && !e->aux_borrowed && !(a == 2 && e->aux_shared)) (void)hipStreamDestroy(e->aux[a]);
   for (auto ev : e->fe)
@@ -2484,16 +2453,14 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   // not ready until every allocation below has succeeded; workspaces sized for the previous N / D are dropped
   e->factored = false;
   e->bs_valid = false;
-  e->pg_cap = 0;
   e->factor_kind = gmb_engine::FK_NONE;  // (no factorisation of THIS data has been attempted: gmb_debug_assume_factored must refuse)
   e->have_theta = false;
   e->N = 0;
-  e->cap_pts = 0;
-  e->Mt_cap = 0;
-  e->Mt2_cap = 0;
+  stale_sized_by_n(e);
+  // (here only: new data gets prepared points of exactly its own size.  resize_n keeps a block that is large enough -- after
+  // a truncation it is larger than Nr asks for, and renewing it there would move gmb_resident_bytes.)
+  e->pts.stale();
   e->u_valid = e->linv_valid = false;
-  e->cap_part = 0;
-  e->plan_N = -1;
   e->D = D;
   e->Np = round_up(N, TILE);
   e->Nr = round_up(N + 1, TILE);
@@ -2502,17 +2469,13 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   if (const char* lp = getenv("GMB_LD_PAD")) e->ld = e->Nr + atoi(lp);  // probe: leading dimension off the 1 KiB grid (tools/gpu_ld_pad.py)
 #endif
   int rc;
-  if ((rc = alloc(e, &e->dX, N * (int64_t)D))) return rc;
-  if ((rc = alloc(e, &e->dy, e->Np))) return rc;
+  if ((rc = e->dX.renew(e->pool, N * (int64_t)D))) return rc;
+  if ((rc = e->dy.renew(e->pool, e->Np))) return rc;
   // (the factor buffer itself -- Nr x Np doubles -- is allocated by the first factorisation that needs it: in the multi-GPU
   // driver's capacity mode no rank ever holds it)
-  if (e->cap_A < e->ld * e->Np && e->dA) {
-    release(e, e->dA);
-    e->dA = nullptr;
-    e->cap_A = 0;
-  }
-  if ((rc = ensure(e, &e->dDinv16, &e->cap_dinv16, (e->Np / TILE) * (int64_t)8 * 256))) return rc;
-  if ((rc = alloc(e, &e->dv, e->Np))) return rc;
+  if (e->dA.cap < e->ld * e->Np) e->dA.drop(e->pool);
+  if ((rc = e->dDinv16.reserve(e->pool, (e->Np / TILE) * (int64_t)8 * 256))) return rc;
+  if ((rc = e->dv.renew(e->pool, e->Np))) return rc;
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(e, hipMemcpy2DAsync(e->dX, D * sizeof(double), X, ldx * sizeof(double), D * sizeof(double), N,
                               kind, e->stream));
@@ -2549,7 +2512,7 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->factor_kind = gmb_engine::FK_NONE;
   e->nc_pad = pick_nc(spec->n_cont);
   e->periodic = 0;
-  e->cap_pts = 0;
+  e->pts.stale();
   return GMB_OK;
 }
 
@@ -2596,26 +2559,21 @@ int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) {
   e->factor_kind = gmb_engine::FK_NONE;
   int rc = apply_theta(e);
   if (rc) return rc;
-  if (e->cap_pts < e->Nr) {
-    if ((rc = alloc(e, &e->xs, (int64_t)17 * e->Nr))) return rc;
-    if ((rc = alloc(e, &e->xl, (int64_t)MAX_LIN * e->Nr))) return rc;
-    if ((rc = alloc(e, &e->cat, (int64_t)MAX_TABS * e->Nr))) return rc;
-    e->cap_pts = e->Nr;
-  }
+  if ((rc = e->pts.reserve(e->pool, e->Nr))) return rc;
   e->prezeroed = false;
   if (e->eval_call && eval_will_fuse(e) && e->ct_lose == 0) {
     // gmb_evaluate: this launch also clears the scalar block and the tile launch's control words (factorize_enqueue, eval_tiles)
     const int64_t words = eval_tiles_words((int)(e->Np / TILE), (int)(e->Nr / TILE));
-    if ((rc = ensure(e, &e->dct, &e->cap_ct, words + 2))) return rc;
-    e->prep_zero[0] = reinterpret_cast<unsigned long long*>(e->dscal);
+    if ((rc = e->dct.reserve(e->pool, words + 2))) return rc;
+    e->prep_zero[0] = reinterpret_cast<unsigned long long*>(e->dscal.p);
     e->prep_zero_words[0] = SCAL_DOUBLES;
-    e->prep_zero[1] = reinterpret_cast<unsigned long long*>(e->dct);
+    e->prep_zero[1] = reinterpret_cast<unsigned long long*>(e->dct.p);
     e->prep_zero_words[1] = (words + 1) / 2;
     e->prezeroed = true;
   }
   // small evaluations: the covariance build of this same gmb_evaluate prepares the points itself (one launch less)
   e->prep_deferred = e->prezeroed && e->terms.size() == 1 && e->Nr <= e->inline_prep_max_rows && !e->naive_leaf;
-  if (!e->prep_deferred && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat))) return rc;
+  if (!e->prep_deferred && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat))) return rc;
   e->have_theta = true;
   return GMB_OK;
 }
@@ -2869,7 +2827,7 @@ int launch_gemm_splitk(gmb_engine* e, hipStream_t s, SplitKArgs a, int pin, int3
     S = splitk_rule(tiles, a.k, &len);
   }
   int rc;
-  if ((rc = ensure(e, &e->dsk, &e->cap_sk, (int64_t)tiles * S * TILE * TILE))) return rc;
+  if ((rc = e->dsk.reserve(e->pool, (int64_t)tiles * S * TILE * TILE))) return rc;
   a.slices = S;
   a.slice_len = len;
   a.ws = e->dsk;
@@ -2884,7 +2842,7 @@ int launch_gemm_splitk(gmb_engine* e, hipStream_t s, SplitKArgs a, int pin, int3
 
 // a complete, unconsumed single-engine factor of the current (data, kernel, theta) sits in dA
 bool has_live_factor(const gmb_engine* e) {
-  return e->factored && e->factor_kind == gmb_engine::FK_SINGLE && !e->factor_consumed && e->dA && e->cap_A > 0;
+  return e->factored && e->factor_kind == gmb_engine::FK_SINGLE && !e->factor_consumed && e->dA && e->dA.cap > 0;
 }
 
 // what gmb_append and gmb_truncate refuse alike
@@ -2941,12 +2899,12 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
     a.y = e->dy;
     if ((rc = launch_cov(e, a))) return rc;
     for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: accumulating passes
-      if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[t].pa))) return rc;
+      if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) return rc;
       a.p = e->terms[t].cp;
       a.accumulate = 1;
       if ((rc = launch_cov(e, a))) return rc;
     }
-    if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+    if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa))) return rc;
   }
   HIP_TRY(e, hipEventRecord(e->fe[1], s));
   HIP_TRY(e, hipEventRecord(e->fe[2], s));
@@ -3015,15 +2973,14 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
   HIP_TRY(e, hipSetDevice(e->device));
   const bool live = has_live_factor(e);
   // sizes, kept block columns and copy plan: append_layout.hpp (host arithmetic that tools/append_layout_check.cpp runs under sanitizers)
-  const AppendLayout lay = append_layout(e->N, e->ld, N_new, e->dA ? e->cap_A : 0);
+  const AppendLayout lay = append_layout(e->N, e->ld, N_new, e->dA ? e->dA.cap : 0);
   const int64_t N_old = lay.N_old, Np_old = lay.Np_old, ld_old = lay.ld_old;
   const int64_t Np_new = lay.Np_new, Nr_new = lay.Nr_new, ld_new = lay.ld_new;
   const int I0 = (int)lay.I0;
   const int D = e->D;
   int rc;
   // the re-laid factor first: a device that cannot hold both copies refuses before anything is touched
-  double* newA = nullptr;
-  int64_t cap_newA = 0;
+  ScopedBuf<double> newA(e->pool);
   if (live && lay.relayout) {
     const double need = 8.0 * (double)ld_new * (double)Np_new;
     size_t free_b = 0, total_b = 0;
@@ -3031,7 +2988,7 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
     if (need > (double)free_b)
       return fail(e, GMB_ENOMEM, "%s: re-laying the factor for N = %lld (leading dimension %lld -> %lld) needs %.0f bytes beside the resident "
                                  "copy, %.0f are free -- nothing was changed", what, (long long)N_new, (long long)ld_old, (long long)ld_new, need, (double)free_b);
-    if ((rc = ensure(e, &newA, &cap_newA, ld_new * Np_new))) return rc;
+    if ((rc = newA.reserve(e->pool, ld_new * Np_new))) return rc;
   }
   e->factored = false;
   e->have_alpha = false;
@@ -3039,7 +2996,6 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
   e->u_valid = e->linv_valid = false;
   if (!live) e->factor_kind = gmb_engine::FK_NONE;
   auto bail = [&](int code) {  // a failure half-way: no factor; the data may be of either size, so nothing is ready
-    if (newA) release(e, newA);
     e->factored = false;
     e->factor_kind = gmb_engine::FK_NONE;
     e->have_theta = false;
@@ -3047,42 +3003,26 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
   };
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (Xnew) {  // append: new X and y buffers, the old rows in front
-    double* nX = nullptr;
-    double* ny = nullptr;
-    int64_t c1 = 0, c2 = 0;
-    if ((rc = ensure(e, &nX, &c1, N_new * (int64_t)D)) || (rc = ensure(e, &ny, &c2, Np_new))) {
-      if (nX) release(e, nX);
-      return bail(rc);
-    }
+    ScopedBuf<double> nX(e->pool), ny(e->pool);
+    if ((rc = nX.reserve(e->pool, N_new * (int64_t)D)) || (rc = ny.reserve(e->pool, Np_new))) return bail(rc);
     hipError_t hs = hipMemcpyAsync(nX, e->dX, (size_t)(N_old * D) * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
     if (hs == hipSuccess) hs = hipMemcpy2DAsync(nX + N_old * D, D * sizeof(double), Xnew, ldx * sizeof(double), D * sizeof(double), K, kind, e->stream);
     if (hs == hipSuccess) hs = hipMemsetAsync(ny, 0, (size_t)Np_new * sizeof(double), e->stream);
     if (hs == hipSuccess) hs = hipMemcpyAsync(ny, e->dy, (size_t)N_old * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
     if (hs == hipSuccess) hs = hipMemcpyAsync(ny + N_old, ynew, (size_t)K * sizeof(double), kind, e->stream);
     if (hs == hipSuccess) hs = hipStreamSynchronize(e->stream);  // the caller may reuse its buffers
-    if (hs != hipSuccess) {
-      release(e, nX);
-      release(e, ny);
-      return bail(fail(e, GMB_EHIP, "%s: copying the new observations failed: %s", what, hipGetErrorString(hs)));
-    }
-    release(e, e->dX);
-    release(e, e->dy);
-    e->dX = nX;
-    e->dy = ny;
+    if (hs != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: copying the new observations failed: %s", what, hipGetErrorString(hs)));
+    e->dX.adopt(e->pool, nX);
+    e->dy.adopt(e->pool, ny);
     if (Np_new > Np_old) {
-      if ((rc = alloc(e, &e->dv, Np_new))) return bail(rc);
+      if ((rc = e->dv.renew(e->pool, Np_new))) return bail(rc);
       const int64_t need = (Np_new / TILE) * (int64_t)8 * 256;
-      if (e->cap_dinv16 < need) {  // the kept blocks' sub-block inverses move along
-        double* nd = nullptr;
-        int64_t cd = 0;
-        if ((rc = ensure(e, &nd, &cd, need))) return bail(rc);
-        if (live && I0 > 0 && hipMemcpy(nd, e->dDinv16, (size_t)I0 * 8 * 256 * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) {
-          release(e, nd);
+      if (e->dDinv16.cap < need) {  // the kept blocks' sub-block inverses move along
+        ScopedBuf<double> nd(e->pool);
+        if ((rc = nd.reserve(e->pool, need))) return bail(rc);
+        if (live && I0 > 0 && hipMemcpy(nd, e->dDinv16, (size_t)I0 * 8 * 256 * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess)
           return bail(fail(e, GMB_EHIP, "%s: copying the kept blocks' sub-block inverses failed", what));
-        }
-        release(e, e->dDinv16);
-        e->dDinv16 = nd;
-        e->cap_dinv16 = cd;
+        e->dDinv16.adopt(e->pool, nd);
       }
     }
   } else {  // truncate: the buffers stay, y's padding is zero again
@@ -3094,28 +3034,13 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
   e->Np = Np_new;
   e->Nr = Nr_new;
   e->ld = ld_new;
-  e->Mt_cap = 0;
-  e->Mt2_cap = 0;
-  e->cap_part = 0;
-  e->pg_cap = 0;
-  e->plan_N = -1;
-  e->prep_deferred = false;
+  stale_sized_by_n(e);
   // the prepared coordinates of ALL rows: their SoA stride is Nr
-  if (e->cap_pts < e->Nr) {
-    e->cap_pts = 0;
-    if ((rc = alloc(e, &e->xs, (int64_t)17 * e->Nr)) || (rc = alloc(e, &e->xl, (int64_t)MAX_LIN * e->Nr)) ||
-        (rc = alloc(e, &e->cat, (int64_t)MAX_TABS * e->Nr)))
-      return bail(rc);
-    e->cap_pts = e->Nr;
-  }
-  if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat))) return bail(rc);
+  if ((rc = e->pts.reserve(e->pool, e->Nr))) return bail(rc);
+  if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat))) return bail(rc);
   if (!live) {
     if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: preparing the points failed", what));
-    if (e->cap_A < e->ld * e->Np && e->dA) {  // (gmb_set_data: a factor buffer too small for the new size goes)
-      release(e, e->dA);
-      e->dA = nullptr;
-      e->cap_A = 0;
-    }
+    if (e->dA.cap < e->ld * e->Np) e->dA.drop(e->pool);  // (gmb_set_data: a factor buffer too small for the new size goes)
     return GMB_OK;
   }
   if (newA) {  // the kept lower triangle, block column by block column: rows [128 c, 128 I0) of columns [128 c, 128 c + 128)
@@ -3126,10 +3051,7 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
       if (hs != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: re-laying the factor failed: %s", what, hipGetErrorString(hs)));
     }
     if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail(e, GMB_EHIP, "%s: re-laying the factor failed", what));
-    release(e, e->dA);
-    e->dA = newA;
-    e->cap_A = cap_newA;
-    newA = nullptr;
+    e->dA.adopt(e->pool, newA);
   }
   return refactor_tail(e, lay);
 }
@@ -3146,20 +3068,9 @@ int64_t predict_tile_rows(const gmb_engine* e, int64_t M) {
 // issuing the pass's all-gathers, with its peers blocked inside them.
 int predict_workspace(gmb_engine* e, int64_t Mt) {
   int rc;
-  if (e->Mt_cap < Mt) {
-    e->Mt_cap = 0;  // (a failure half-way leaves no capacity claimed)
-    if ((rc = alloc(e, &e->dV, Mt * e->Np))) return rc;
-    if ((rc = alloc(e, &e->dXs, Mt * (int64_t)e->D))) return rc;
-    if ((rc = alloc(e, &e->txs, (int64_t)17 * Mt))) return rc;
-    if ((rc = alloc(e, &e->txl, (int64_t)MAX_LIN * Mt))) return rc;
-    if ((rc = alloc(e, &e->tcat, (int64_t)MAX_TABS * Mt))) return rc;
-    if ((rc = alloc(e, &e->dkss, Mt))) return rc;
-    if ((rc = alloc(e, &e->dmean, Mt))) return rc;
-    if ((rc = alloc(e, &e->dvar, Mt))) return rc;
-    e->Mt_cap = Mt;
-  }
+  if ((rc = e->pw.reserve(e->pool, Mt, e->Np, e->D))) return rc;
   const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
-  return ensure(e, &e->dpart, &e->cap_part, (int64_t)2 * nchunk * e->Mt_cap);
+  return e->dpart.reserve(e->pool, (int64_t)2 * nchunk * e->pw.rows);
 }
 
 // ---- the pieces of one M-tile of a prediction, shared by gmb_predict (tile by tile) and the joint posterior (all M rows at
@@ -3169,35 +3080,27 @@ int predict_workspace(gmb_engine* e, int64_t Mt) {
 // path's gradient leaves behind; everything else is the triangular solve.
 bool predict_takes_gemm_form(const gmb_engine* e) {
   return !e->solve_hook && e->predict_form != 0 && e->u_valid && e->have_alpha && e->factor_kind == gmb_engine::FK_SINGLE &&
-         e->dW && e->dUdiag && e->cap_W >= e->Np * e->Np;
+         e->dW && e->dUdiag && e->dW.cap >= e->Np * e->Np;
 }
 
 // ... and the second Mt x Np buffer that form needs
-int predict_gemm_form_workspace(gmb_engine* e, int64_t Mt) {
-  int rc;
-  if (e->Mt2_cap < Mt) {
-    e->Mt2_cap = 0;
-    if ((rc = alloc(e, &e->dV2, Mt * e->Np))) return rc;
-    e->Mt2_cap = Mt;
-  }
-  return GMB_OK;
-}
+int predict_gemm_form_workspace(gmb_engine* e, int64_t Mt) { return e->pw2.reserve(e->pool, Mt, e->Np); }
 
 // mc test points (Xs: their first row) -> prepared points in txs / txl / tcat, the cross-covariance K(X*, X) in dV (mpad x Np,
 // test index fastest) and the prior variances (+ noise) in dkss
 int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, int32_t with_noise,
                       hipMemcpyKind in_kind) {
   int rc;
-  HIP_TRY(e, hipMemcpy2DAsync(e->dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double),
+  HIP_TRY(e, hipMemcpy2DAsync(e->pw.dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double),
                               e->D * sizeof(double), mc, in_kind, e->stream));
-  if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat))) return rc;
-  const PointSet test{e->txs, e->txl, e->tcat, mc, mpad};
+  if ((rc = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat))) return rc;
+  const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, mc, mpad};
   {  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
     CovTileArgs a{};
     a.p = e->cp;
     a.rows = test;
     a.cols = train_set(e);
-    a.out = e->dV;
+    a.out = e->pw.dV;
     a.ldo = mpad;
     a.ti = (int)(mpad / TILE);
     a.tj = (int)(e->Np / TILE);
@@ -3211,17 +3114,17 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
   k.p = e->cp;
   k.pts = test;
   k.with_noise = with_noise;
-  k.kss = e->dkss;
+  k.kss = e->pw.dkss;
   hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
   for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: one accumulating pass per further term
     const gmb_engine::Term& tr = e->terms[t];
-    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
-    if ((rc = prep_points(e, e->dXs, mc, e->D, mpad, e->txs, e->txl, e->tcat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &tr.pa))) return rc;
     CovTileArgs a{};
     a.p = tr.cp;
     a.rows = test;
     a.cols = train_set(e);
-    a.out = e->dV;
+    a.out = e->pw.dV;
     a.ldo = mpad;
     a.ti = (int)(mpad / TILE);
     a.tj = (int)(e->Np / TILE);
@@ -3234,7 +3137,7 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
   }
   if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa)))
+      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
     return rc;
   return GMB_OK;
 }
@@ -3256,7 +3159,7 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
   const bool tiles = !e->naive_leaf && ntm <= 96 && (e->chol_scheme == 3 || (e->chol_scheme < 0 && by_size));
   bool tile_solve = false;  // the solve ran on the tile kernel, whose abort word is read back below
   if (e->solve_hook) {
-    if ((rc = e->solve_hook(e->dV, mpad, (int)(mpad / TILE)))) return rc;
+    if ((rc = e->solve_hook(e->pw.dV, mpad, (int)(mpad / TILE)))) return rc;
   } else if (use_gemm_form) {
     // U = L^-T of this factor is resident (the fit's last evaluation left it): V^T = L^-1 K(X, X*) as ONE product with a
     // triangular operand (predict_form.hpp) instead of a solve
@@ -3273,9 +3176,9 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
       e->linv_valid = true;
     }
     GemmArgs g{};
-    g.C = e->dV2;
+    g.C = e->pw2.dV2;
     g.ldc = e->Np;
-    g.A = e->dV;
+    g.A = e->pw.dV;
     g.lda = mpad;
     g.B = e->dW;
     g.ldb = e->Np;
@@ -3286,8 +3189,8 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
     g.beta = 0.0;
     g.khi_n = 1;
     if ((rc = launch_gemm(e, e->stream, g, EV_PREDICT_GEMM))) return rc;
-  } else if ((rc = tiles ? trsm_tiles(e, e->stream, train_factor(e), e->dV, mpad, ntm, EV_PREDICT_GEMM, &tile_solve)
-                         : trsm_cols(e, e->stream, train_factor(e), e->dV, mpad, ntm, 0, nblocks, EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
+  } else if ((rc = tiles ? trsm_tiles(e, e->stream, train_factor(e), e->pw.dV, mpad, ntm, EV_PREDICT_GEMM, &tile_solve)
+                         : trsm_cols(e, e->stream, train_factor(e), e->pw.dV, mpad, ntm, 0, nblocks, EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
     return rc;
   if (tile_solve) {  // a launch that gave up waiting must not be mistaken for a prediction
     uint32_t ab = 0;
@@ -3303,19 +3206,19 @@ int predict_reduce(gmb_engine* e, int64_t mc, int64_t mpad, bool gemm_form) {
   const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
   if (gemm_form) {
     // variance from Vt, mean = K(X*, X) alpha from the cross-covariance, which the GEMM left in dV (predict_form.hpp)
-    hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->dV2, e->Np, e->N, e->dkss, e->dvar);
+    hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->pw2.dV2, e->Np, e->N, e->pw.dkss, e->pw.dvar);
     hipLaunchKernelGGL(predict_mean_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
-                       dim3(256), 0, e->stream, e->dV, mpad, e->dalpha, e->N, e->dpart, mpad);
+                       dim3(256), 0, e->stream, e->pw.dV, mpad, e->dalpha, e->N, e->dpart, mpad);
     hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->dpart, nchunk,
-                       mpad, mc, e->dmean);
+                       mpad, mc, e->pw.dmean);
     HIP_TRY(e, hipGetLastError());
   } else {
     double* pmu = e->dpart;
     double* ps = e->dpart + (int64_t)nchunk * mpad;
     hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk),
-                       dim3(256), 0, e->stream, e->dV, mpad, e->dv, e->N, pmu, ps, mpad);
+                       dim3(256), 0, e->stream, e->pw.dV, mpad, e->dv, e->N, pmu, ps, mpad);
     hipLaunchKernelGGL(predict_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream,
-                       pmu, ps, nchunk, mpad, e->dkss, mc, e->dmean, e->dvar);
+                       pmu, ps, nchunk, mpad, e->pw.dkss, mc, e->pw.dmean, e->pw.dvar);
     HIP_TRY(e, hipGetLastError());
   }
   return GMB_OK;
@@ -3324,7 +3227,7 @@ int predict_reduce(gmb_engine* e, int64_t mc, int64_t mpad, bool gemm_form) {
 // ---- the joint posterior (joint_predict.hpp): full covariance and correlated draws ----------------------------------------------
 
 // C as the Cholesky's routines take it (buffers and capacities stay JointState's)
-FactorRef joint_factor_ref(JointState& jt) { return FactorRef{jt.dC, jt.Mr, jt.M, jt.Mp, jt.Mr, jt.dDinv16, jt.dscal, &jt.dct, &jt.cap_ct}; }
+FactorRef joint_factor_ref(JointState& jt) { return FactorRef{jt.dC, jt.Mr, jt.M, jt.Mp, jt.Mr, jt.dDinv16, jt.dscal, &jt.dct}; }
 
 // what both calls ask of the engine: a complete single-engine factor on this device
 int joint_ready(gmb_engine* e, const char* what) {
@@ -3349,11 +3252,11 @@ int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, 
   const double total = per_row * Mr + 16.0 * nchunk * Mr + (gemm_form ? v_bytes : 0.0) + c_bytes + stage_bytes;
   // what is still to be allocated, less what those allocations release first
   double fresh = 0.0;
-  if ((double)e->Mt_cap < Mr) fresh += per_row * (Mr - (double)e->Mt_cap);
-  if ((double)e->cap_part < 2.0 * nchunk * Mr) fresh += 8.0 * (2.0 * nchunk * Mr - (double)e->cap_part);
-  if (gemm_form && (double)e->Mt2_cap < Mr) fresh += 8.0 * Np * (Mr - (double)e->Mt2_cap);
-  if ((double)jt.cap_C < Mr * Mp) fresh += 8.0 * (Mr * Mp - (double)jt.cap_C);
-  if ((double)jt.cap_stage < stage) fresh += 8.0 * (stage - (double)jt.cap_stage);
+  if ((double)e->pw.rows < Mr) fresh += per_row * (Mr - (double)e->pw.rows);
+  if ((double)e->dpart.cap < 2.0 * nchunk * Mr) fresh += 8.0 * (2.0 * nchunk * Mr - (double)e->dpart.cap);
+  if (gemm_form && (double)e->pw2.rows < Mr) fresh += 8.0 * Np * (Mr - (double)e->pw2.rows);
+  if ((double)jt.dC.cap < Mr * Mp) fresh += 8.0 * (Mr * Mp - (double)jt.dC.cap);
+  if ((double)jt.dstage.cap < stage) fresh += 8.0 * (stage - (double)jt.dstage.cap);
   size_t free_b = 0, total_b = 0;
   HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
   if (fresh > (double)free_b || Mr > 1073741824.0)
@@ -3364,17 +3267,14 @@ int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, 
   int rc;
   if ((rc = predict_workspace(e, mr))) return rc;
   if (gemm_form && (rc = predict_gemm_form_workspace(e, mr))) return rc;
-  if ((rc = ensure(e, &jt.dC, &jt.cap_C, mr * mp))) return rc;
-  if ((rc = ensure(e, &jt.dDinv16, &jt.cap_dinv16, (mp / TILE) * (int64_t)8 * 256))) return rc;
-  if (!jt.dscal) {
-    int64_t cap = 0;
-    if ((rc = ensure(e, &jt.dscal, &cap, (int64_t)SCAL_GACC_AT))) return rc;
+  if ((rc = jt.dC.reserve(e->pool, mr * mp))) return rc;
+  if ((rc = jt.dDinv16.reserve(e->pool, (mp / TILE) * (int64_t)8 * 256))) return rc;
+  if ((rc = jt.dscal.reserve(e->pool, (int64_t)SCAL_GACC_AT))) return rc;
+  if (jt.dzero.cap < mr) {
+    if ((rc = jt.dzero.reserve(e->pool, mr))) return rc;
+    HIP_TRY(e, hipMemsetAsync(jt.dzero, 0, (size_t)jt.dzero.cap * sizeof(double), e->stream));
   }
-  if (jt.cap_zero < mr) {
-    if ((rc = ensure(e, &jt.dzero, &jt.cap_zero, mr))) return rc;
-    HIP_TRY(e, hipMemsetAsync(jt.dzero, 0, (size_t)jt.cap_zero * sizeof(double), e->stream));
-  }
-  if (stage > 0.0 && (rc = ensure(e, &jt.dstage, &jt.cap_stage, (int64_t)stage))) return rc;
+  if (stage > 0.0 && (rc = jt.dstage.reserve(e->pool, (int64_t)stage))) return rc;
   jt.M = M, jt.Mp = mp, jt.Mr = mr;
   return GMB_OK;
 }
@@ -3393,17 +3293,17 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   if ((rc = predict_reduce(e, M, Mr, gemm_form))) return rc;
   // the product form leaves V with the training index fastest: turned into the update's k-major layout (the cross-covariance
   // in dV has served the mean)
-  if (gemm_form && (rc = launch_transpose(e, e->stream, e->dV2, e->Np, e->dV, Mr, (int)e->Np, (int)Mr))) return rc;
+  if (gemm_form && (rc = launch_transpose(e, e->stream, e->pw2.dV2, e->Np, e->pw.dV, Mr, (int)e->Np, (int)Mr))) return rc;
   // Columns N .. Np-1 of V belong to no training point.  gmb_predict never reads them (its reductions stop at N); the update
   // below contracts over all Np, so they are cleared, whichever form produced them.
   if (e->Np > e->N)
-    HIP_TRY(e, hipMemsetAsync(e->dV + e->N * Mr, 0, (size_t)((e->Np - e->N) * Mr) * sizeof(double), e->stream));
+    HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * Mr, 0, (size_t)((e->Np - e->N) * Mr) * sizeof(double), e->stream));
 
   // K(X*, X*): the training build's launch (build_sigma) on the test points -- direct distances on the diagonal tiles, so the
   // diagonal is gmb_predict's k** to the bit
   const bool additive = e->terms.size() > 1;
-  if (additive && (rc = prep_points(e, e->dXs, M, e->D, Mr, e->txs, e->txl, e->tcat, &e->terms[0].pa))) return rc;
-  const PointSet test{e->txs, e->txl, e->tcat, M, Mr};
+  if (additive && (rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[0].pa))) return rc;
+  const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, M, Mr};
   CovTileArgs a{};
   a.p = e->cp;
   a.p.sigma2 = with_noise ? e->cp.sigma2 : 0.0;
@@ -3420,7 +3320,7 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   a.y = jt.dzero;
   if ((rc = launch_cov(e, a))) return rc;
   for (size_t t = 1; t < e->terms.size(); ++t) {
-    if ((rc = prep_points(e, e->dXs, M, e->D, Mr, e->txs, e->txl, e->tcat, &e->terms[t].pa))) return rc;
+    if ((rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[t].pa))) return rc;
     a.p = e->terms[t].cp;
     a.accumulate = 1;
     if ((rc = launch_cov(e, a))) return rc;
@@ -3430,9 +3330,9 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   GemmArgs g{};
   g.C = jt.dC;
   g.ldc = Mr;
-  g.A = e->dV;
+  g.A = e->pw.dV;
   g.lda = Mr;
-  g.B = e->dV;
+  g.B = e->pw.dV;
   g.ldb = Mr;
   g.mt = (int)(Mp / TILE);
   g.nt = (int)(Mr / TILE);
@@ -3519,7 +3419,7 @@ int launch_predict_grad(gmb_engine* e, const PredGradArgs& a, int nchunk, int ns
 // in place: the state every caller has checked -- complete single-engine factor, not consumed)
 int backsub_alpha(gmb_engine* e) {
   int rc;
-  if ((rc = ensure(e, &e->dalpha_bs, &e->cap_alpha_bs, 2 * e->Np))) return rc;
+  if ((rc = e->dalpha_bs.reserve(e->pool, 2 * e->Np))) return rc;
   double* alpha = e->dalpha_bs;
   double* w = e->dalpha_bs + e->Np;
   const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
@@ -3542,10 +3442,10 @@ int predict_solve_w(gmb_engine* e, int64_t mpad) {
   const int nb = (int)(e->Np / TILE);
   ev_begin(e, e->stream, EV_PREDICT_VGRAD_SOLVE, (double)mpad * (double)e->N * (double)e->N, (int)(mpad / TILE), nb);
   for (int b = nb - 1; b >= 0; --b) {
-    hipLaunchKernelGGL(vsolve_diag_kernel, dim3((unsigned)(mpad / VS_ROWS)), dim3(VS_ROWS), 0, e->stream, L, (int64_t)b, e->N, e->dV, mpad);
+    hipLaunchKernelGGL(vsolve_diag_kernel, dim3((unsigned)(mpad / VS_ROWS)), dim3(VS_ROWS), 0, e->stream, L, (int64_t)b, e->N, e->pw.dV, mpad);
     if (b > 0)
       hipLaunchKernelGGL(vsolve_update_kernel, dim3((unsigned)(mpad / VS_PTS), (unsigned)b), dim3(256), 0, e->stream, L, (int64_t)b, e->N,
-                         e->dV, mpad);
+                         e->pw.dV, mpad);
   }
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
@@ -3565,20 +3465,12 @@ int resident_alpha(gmb_engine* e, const double** alpha) {
 // gmb_predict_grad, 2 for gmb_predict_with_grad
 int predict_grad_workspace(gmb_engine* e, int64_t Mt, int nset) {
   int rc;
-  if (e->pg_cap < Mt) {
-    e->pg_cap = 0;
-    if ((rc = alloc(e, &e->pg_Xs, Mt * (int64_t)e->D))) return rc;
-    if ((rc = alloc(e, &e->pg_xs, (int64_t)17 * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_xl, (int64_t)MAX_LIN * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_cat, (int64_t)MAX_TABS * Mt))) return rc;
-    if ((rc = alloc(e, &e->pg_grad, Mt * (int64_t)e->D))) return rc;
-    e->pg_cap = Mt;
-  }
-  if (nset == 2 && (rc = ensure(e, &e->vg_grad, &e->cap_vg_grad, Mt * (int64_t)e->D))) return rc;
+  if ((rc = e->pg.reserve(e->pool, Mt, e->D))) return rc;
+  if (nset == 2 && (rc = e->vg_grad.reserve(e->pool, Mt * (int64_t)e->D))) return rc;
   // every M-tile of mpad <= Mt rows runs nchunk <= PG_TARGET_WGS / (mpad / 64) + 1 chunks (predict_grad_chunk), so its partials
   // -- nchunk x nset x (nc_pad + n_lin) x mpad doubles -- fit in this whatever its size
   const int64_t need = nset * ((int64_t)PG_TARGET_WGS * PG_PTS + Mt) * (e->nc_pad + MAX_LIN);
-  return ensure(e, &e->pg_part, &e->cap_pg_part, need);
+  return e->pg_part.reserve(e->pool, need);
 }
 
 // d mu / d x* of one M-tile (mc raw points on the device, D per row, first row Xs) into pg_grad (mc x D, row-major); with
@@ -3586,17 +3478,17 @@ int predict_grad_workspace(gmb_engine* e, int64_t Mt, int nset) {
 int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, const double* alpha, const double* W) {
   int rc;
   const int nset = W ? 2 : 1;
-  HIP_TRY(e, hipMemsetAsync(e->pg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->pg.grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
   if (W) HIP_TRY(e, hipMemsetAsync(e->vg_grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
   int64_t chunk;
   int nchunk;
   predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
-  const PointSet test{e->pg_xs, e->pg_xl, e->pg_cat, mc, mpad};
+  const PointSet test{e->pg.xs, e->pg.xl, e->pg.cat, mc, mpad};
   for (size_t t = 0; t < e->terms.size(); ++t) {
     const gmb_engine::Term& tr = e->terms[t];
     // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
-    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &tr.pa))) return rc;
-    if ((rc = prep_points(e, Xs, mc, e->D, mpad, e->pg_xs, e->pg_xl, e->pg_cat, &tr.pa))) return rc;
+    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
+    if ((rc = prep_points(e, Xs, mc, e->D, mpad, e->pg.xs, e->pg.xl, e->pg.cat, &tr.pa))) return rc;
     PredGradArgs a{};
     a.p = tr.cp;
     a.test = test;
@@ -3619,7 +3511,7 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
       f.nset = nset;
       f.mpad = mpad;
       f.mc = mc;
-      f.txs = e->pg_xs;
+      f.txs = e->pg.xs;
       for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k];
       if (tr.pa.periodic) {
         for (int d = 0; 2 * d < tr.pa.nc; ++d) f.scale[d] = 2.0 * M_PI * tr.pa.two_over_T[d];  // 2 * (2 pi / T_d)
@@ -3628,14 +3520,14 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
       }
       for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
       f.tau = tr.cp.tau;
-      f.grad = e->pg_grad;
+      f.grad = e->pg.grad;
       if (W) {
         f.dvar = e->vg_grad;
         f.n_tab = tr.cp.n_tab;
         for (int i = 0; i < MAX_TABS; ++i) f.tab_levels[i] = tr.cp.tab_levels[i], f.tab_off[i] = tr.cp.tab_off[i];
         f.tabs = tr.cp.tabs;
-        f.txl = e->pg_xl;
-        f.tcat = e->pg_cat;
+        f.txl = e->pg.xl;
+        f.tcat = e->pg.cat;
       }
       hipLaunchKernelGGL(predict_grad_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, f);
     }
@@ -3643,7 +3535,7 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     if (rc) return rc;
     HIP_TRY(e, hipGetLastError());
   }
-  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->xs, e->xl, e->cat, &e->terms[0].pa))) return rc;
+  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa))) return rc;
   return GMB_OK;
 }
 
@@ -3726,8 +3618,8 @@ int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_
       if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
       if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
       if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
-      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), ck.out, e->stream));
-      HIP_TRY(e, hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream));
     }
     return GMB_OK;
   };
@@ -3750,9 +3642,9 @@ int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, d
   auto tiles = [&]() -> int {
     for (int64_t m0 = 0; m0 < M; m0 += Mt) {
       const int64_t mc = std::min<int64_t>(Mt, M - m0);
-      HIP_TRY(e, hipMemcpy2DAsync(e->pg_Xs, row, Xs + m0 * ldxs, ldxs * sizeof(double), row, mc, ck.in, e->stream));
-      if ((rc = predict_grad_tile(e, e->pg_Xs, mc, round_up(mc, TILE), alpha, nullptr))) return rc;
-      if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, ck.out, e->stream) != hipSuccess)
+      HIP_TRY(e, hipMemcpy2DAsync(e->pg.Xs, row, Xs + m0 * ldxs, ldxs * sizeof(double), row, mc, ck.in, e->stream));
+      if ((rc = predict_grad_tile(e, e->pg.Xs, mc, round_up(mc, TILE), alpha, nullptr))) return rc;
+      if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, mc, ck.out, e->stream) != hipSuccess)
         return fail(e, GMB_EHIP, "gmb_predict_grad: copying the gradient out failed");
     }
     return GMB_OK;
@@ -3787,10 +3679,10 @@ int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
       if ((rc = predict_reduce(e, mc, mpad, false))) return rc;
       if ((rc = predict_solve_w(e, mpad))) return rc;
       // (the tile's raw points are in dXs: predict_cross_cov; W = K(X*, X) Sigma^-1 in dV)
-      if ((rc = predict_grad_tile(e, e->dXs, mc, mpad, alpha, e->dV))) return rc;
-      if (hipMemcpyAsync(mean + m0, e->dmean, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
-          hipMemcpyAsync(var + m0, e->dvar, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
-          hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg_grad, row, row, mc, ck.out, e->stream) != hipSuccess ||
+      if ((rc = predict_grad_tile(e, e->pw.dXs, mc, mpad, alpha, e->pw.dV))) return rc;
+      if (hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, mc, ck.out, e->stream) != hipSuccess ||
           hipMemcpy2DAsync(dvar + m0 * ldg, ldg * sizeof(double), e->vg_grad, row, row, mc, ck.out, e->stream) != hipSuccess)
         return fail(e, GMB_EHIP, "gmb_predict_with_grad: copying the results out failed");
     }
@@ -3825,7 +3717,7 @@ int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, 
     const unsigned nb = (unsigned)((M + 31) / 32);
     hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
     HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), ck.out, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
     if (host)
       HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
                                   hipMemcpyDeviceToHost, e->stream));
@@ -3855,7 +3747,7 @@ int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int
     DrawArgs da{};
     da.L = e->jt.dC;
     da.ldl = e->jt.Mr;
-    da.mean = e->dmean;
+    da.mean = e->pw.dmean;
     da.M = M;
     da.S = (int32_t)S;
     if (host) {
@@ -3869,7 +3761,7 @@ int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int
     if ((rc = launch_draw(e, da))) return rc;
     if (host)
       HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
-    if (mean) HIP_TRY(e, hipMemcpyAsync(mean, e->dmean, M * sizeof(double), ck.out, e->stream));
+    if (mean) HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
     return GMB_OK;
   };
   return predict_end(e, &tp, work());
@@ -3879,7 +3771,7 @@ int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, in
   gmb_engine* e = const_cast<gmb_engine*>(ce);
   if (!e || !out) return GMB_EINVAL;
   if (e->factored && require_full_factor(e, "gmb_copy_factor")) return GMB_EINVAL;
-  if (!e->dA || e->cap_A <= 0 || r0 < 0 || c0 < 0 || nr < 0 || nc < 0 || r0 + nr > e->Nr || c0 + nc > e->Np)
+  if (!e->dA || e->dA.cap <= 0 || r0 < 0 || c0 < 0 || nr < 0 || nc < 0 || r0 + nr > e->Nr || c0 + nc > e->Np)
     return fail(e, GMB_EINVAL, "factor window out of range");
   if (nr == 0 || nc == 0) return GMB_OK;
   std::vector<double> tmp((size_t)nr * nc);  // column-major window
@@ -4101,7 +3993,7 @@ int64_t gmb_chol_task_trace(gmb_engine* e, int32_t enable, uint64_t* out, int64_
   if (!e) return GMB_EINVAL;
   if (enable >= 0) e->ct_trace = enable != 0;
   // only the stamps of the LAST factorisation count: 0 when it did not run on the tile kernel or ran untraced
-  const int64_t n = (e->chol.tiles && e->chol.traced && e->dct_trace && e->cap_ct_trace >= 4 * (int64_t)e->chol.ntasks) ? e->chol.ntasks : 0;
+  const int64_t n = (e->chol.tiles && e->chol.traced && e->dct_trace && e->dct_trace.cap >= 4 * (int64_t)e->chol.ntasks) ? e->chol.ntasks : 0;
   if (out && n > 0) {
     HIP_TRY(e, hipSetDevice(e->device));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -4154,7 +4046,7 @@ int gmb_reserve(gmb_engine* e, int32_t gradient, int64_t M) {
   HIP_TRY(e, hipSetDevice(e->device));
   if ((rc = ensure_factor_buffer(e))) return rc;
   if (gradient) {
-    if ((rc = ensure(e, &e->dW, &e->cap_W, e->Np * e->Np))) return rc;
+    if ((rc = e->dW.reserve(e->pool, e->Np * e->Np))) return rc;
     if ((rc = grad_workspace(e))) return rc;
   }
   if (M > 0 && (rc = predict_workspace(e, predict_tile_rows(e, M)))) return rc;
@@ -4389,11 +4281,9 @@ int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
   if (mode == 1) {
     // the point of the mode is that no rank keeps an Nr x Np buffer: one left behind by an earlier single-engine or replicated
     // factorisation goes now (its factorisation was just invalidated, or is of no use to the capacity passes)
-    if (e->dA && e->cap_A > 0) {
+    if (e->dA && e->dA.cap > 0) {
       if (hipSetDevice(e->device) == hipSuccess) (void)hipStreamSynchronize(e->stream);
-      release(e, e->dA);
-      e->dA = nullptr;
-      e->cap_A = 0;
+      e->dA.drop(e->pool);
       e->factored = false;
       e->bs_valid = false;
       e->factor_kind = gmb_engine::FK_NONE;
@@ -4405,7 +4295,7 @@ int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
 // device bytes this engine holds through its own allocations right now (peak != 0: the largest value so far)
 int64_t gmb_resident_bytes(const gmb_engine* e, int32_t peak) {
   if (!e) return GMB_EINVAL;
-  return peak ? e->bytes_peak : e->bytes_resident;
+  return peak ? e->pool.bytes_peak : e->pool.bytes_resident;
 }
 
 int gmb_dist_factorize(gmb_engine* e, const gmb_comm* comm, int32_t panel_blocks) {

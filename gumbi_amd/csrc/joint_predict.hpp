@@ -18,27 +18,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_buffers.hpp"
 #include "gemm_f64.hpp"
 
 namespace gmb {
 
-// Everything the factorisation of C owns.  The host routines of the Cholesky (chol_factor, chol_tiles, chol_cols, ...) are told
+// Everything the factorisation of C owns (the blocks belong to the engine's pool: device_buffers.hpp).  The host routines of the Cholesky (chol_factor, chol_tiles, chol_cols, ...) are told
 // the matrix they work on -- its 16 x 16 diagonal inverses, scalar block, info word and tile-kernel control block with it
 // (engine.hip: FactorRef, joint_factor_ref) -- so nothing of the training factorisation -- its factor, log-determinant, failure
 // index, control words -- is written by a draw.
 struct JointState {
   int64_t M = 0, Mp = 0, Mr = 0;  // test points; padded to 128; rows of the bordered layout the Cholesky kernels expect ((M + 1) up)
-  double* dC = nullptr;           // Mr x Mp column-major, leading dimension Mr: lower-triangle tiles of C, then of L*
-  int64_t cap_C = 0;
-  double* dDinv16 = nullptr;      // 8 x (16 x 16) sub-block inverses per diagonal block
-  int64_t cap_dinv16 = 0;
-  double* dscal = nullptr;        // head of the engine's scalar-block layout: [0] log-det of C, [64] the info word (int32)
-  uint32_t* dct = nullptr;        // control block of the persistent tile kernel
-  int64_t cap_ct = 0;
-  double* dzero = nullptr;        // Mp zeros: the bordered layout's extra row (the training build puts y there)
-  int64_t cap_zero = 0;
-  double* dstage = nullptr;       // device staging of host-side cov / Z / Y
-  int64_t cap_stage = 0;
+  DevBuf<double> dC;              // Mr x Mp column-major, leading dimension Mr: lower-triangle tiles of C, then of L*
+  DevBuf<double> dDinv16;         // 8 x (16 x 16) sub-block inverses per diagonal block
+  DevBuf<double> dscal;           // head of the engine's scalar-block layout: [0] log-det of C, [64] the info word (int32)
+  DevBuf<uint32_t> dct;           // control block of the persistent tile kernel
+  DevBuf<double> dzero;           // Mp zeros: the bordered layout's extra row (the training build puts y there)
+  DevBuf<double> dstage;          // device staging of host-side cov / Z / Y
 };
 
 // ---- the draw ---------------------------------------------------------------------------------------------------------------
