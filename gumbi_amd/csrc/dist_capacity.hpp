@@ -176,28 +176,11 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     double* panel = e->dPanel + (int64_t)((s.op == DIST_UPDATE ? panel_of(s.c0) : std::max(panel_idx, 0)) & 1) * panel_elems;
     if (!bad.rc) switch (s.op) {
       case DIST_KBUILD: {  // this rank's block rows of the lower triangle (y row and padding included), packed
-        CovTileArgs a{};
-        a.p = e->cp;
-        a.rows = train_set(e);
-        a.cols = train_set(e);
-        a.out = e->dAown;
-        a.ldo = e->ld_own;
-        a.ti = nrt;
-        a.tj = nct;
-        a.mode = COV_TRAIN;
-        a.lower_only = 1;
+        CovTileArgs a = train_cov_args(e, e->dAown, e->ld_own, nrt, nct);
         a.row_first = rank;
         a.row_stride = G;
         a.rows_packed = 1;
-        a.y = e->dy;
-        if ((rc = launch_cov(e, a))) break;
-        for (size_t t = 1; t < e->terms.size() && !rc; ++t) {
-          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) break;
-          a.p = e->terms[t].cp;
-          a.accumulate = 1;
-          rc = launch_cov(e, a);
-        }
-        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa);
+        rc = launch_train_cov(e, a);
         break;
       }
       case DIST_SQUARE: {  // the diagonal square's block rows from their owners, then every rank factors it

@@ -393,27 +393,10 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     }
     if (!bad.rc) switch (s.op) {
       case DIST_KBUILD: {  // this rank's block rows of the lower triangle, y row and padding included
-        CovTileArgs a{};
-        a.p = e->cp;
-        a.rows = train_set(e);
-        a.cols = train_set(e);
-        a.out = e->dA;
-        a.ldo = e->ld;
-        a.ti = nrt;
-        a.tj = nct;
-        a.mode = COV_TRAIN;
-        a.lower_only = 1;
+        CovTileArgs a = train_cov_args(e, e->dA, e->ld, nrt, nct);
         a.row_first = rank;
         a.row_stride = G;
-        a.y = e->dy;
-        if ((rc = launch_cov(e, a))) break;
-        for (size_t t = 1; t < e->terms.size() && !rc; ++t) {  // additive models: accumulating passes
-          if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) break;
-          a.p = e->terms[t].cp;
-          a.accumulate = 1;
-          rc = launch_cov(e, a);
-        }
-        if (!rc && e->terms.size() > 1) rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa);
+        rc = launch_train_cov(e, a);
         break;
       }
       case DIST_SQUARE: {

@@ -31,6 +31,7 @@
 
 #include "../../include/gumbi_hip.h"
 #include "device_buffers.hpp"
+#include "term_walk.hpp"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_splitk.hpp"
@@ -149,10 +150,9 @@ struct gmb_engine {
     }
   } pts;
   DevBuf<double> dtabs, dnoise;
-  CovParams cp{};
-  PrepArgs prep_proto{};
-  // Additive models: term 0 (the global kernel) is (prep_proto, cp); term 1 + j is the kernel of
-  // coregion dim j.  Covariances are built and differentiated term by term (accumulating passes).
+  // The model's covariance terms (apply_theta; empty until gmb_set_theta): terms[0] is the global kernel -- the ONLY copy of its
+  // parameters, and the preparation the resident points hold between calls -- and an additive model adds term 1 + j, the kernel
+  // of coregion dim j.  Covariances are built and differentiated term by term (accumulating passes: walk_terms).
   struct Term {
     PrepArgs pa;
     CovParams cp;
@@ -829,14 +829,13 @@ int validate_spec(gmb_engine* e, const gmb_kernel_spec& s, int D) {
   return GMB_OK;
 }
 
-// Fill PrepArgs / CovParams from spec + theta and upload the coregion tables.
+// Fill the terms' PrepArgs / CovParams from spec + theta and upload the coregion tables.
 int apply_theta(gmb_engine* e) {
   const gmb_kernel_spec& s = e->spec;
   const double* th = e->theta.data();
   int k = 0;
   const int n_ls = s.ard ? s.n_cont : 1;
-  PrepArgs& pa = e->prep_proto;
-  pa = PrepArgs{};
+  PrepArgs pa{};
   const int per = e->periodic;
   pa.nc = per ? 2 * s.n_cont : s.n_cont;
   pa.nc_pad = e->nc_pad;
@@ -865,8 +864,7 @@ int apply_theta(gmb_engine* e) {
   k += n_ls;
   const double eta = th[k], sigma = th[k + 1];
   k += 2;
-  CovParams& cp = e->cp;
-  cp = CovParams{};
+  CovParams cp{};
   cp.kind = s.kind;
   cp.eta2 = eta * eta;
   cp.sigma2 = sigma * sigma;
@@ -977,14 +975,12 @@ int apply_theta(gmb_engine* e) {
     select_tables(t, j);
     e->terms.push_back(t);
   }
-  pa = e->terms[0].pa;  // the engine-wide defaults are the global term
-  cp = e->terms[0].cp;
   return GMB_OK;
 }
 
 PrepArgs prep_args(gmb_engine* e, const double* dXraw, int64_t n, int64_t ldx, int64_t npad, double* xs, double* xl, int32_t* cat,
                    const PrepArgs* proto) {
-  PrepArgs a = proto ? *proto : e->prep_proto;
+  PrepArgs a = proto ? *proto : e->terms[0].pa;  // (every caller sits behind gmb_set_theta's apply_theta: terms is not empty)
   for (int z = 0; z < 2; ++z) {  // (one shot: gmb_set_theta inside gmb_evaluate)
     a.zero[z] = e->prep_zero[z];
     a.zero_words[z] = e->prep_zero_words[z];
@@ -1038,40 +1034,52 @@ int ensure_factor_buffer(gmb_engine* e) { return e->dA.reserve(e->pool, e->ld * 
 // the training factor as the Cholesky / triangular-solve routines take it
 FactorRef train_factor(gmb_engine* e) { return FactorRef{e->dA, e->ld, e->N, e->Np, e->Nr, e->dDinv16, e->dscal, &e->dct}; }
 
+// The walk over the model's covariance terms (term_walk.hpp): body(t) runs with the resident training points prepared for term t.
+// This is the ONE place they are re-prepared for a term, and term 0's preparation is back when the walk returns, however it ends.
+// Test points are a body's own business (workspace, not engine state).
+template <typename Body>
+int walk_terms(gmb_engine* e, Body&& body) {
+  return for_each_term(
+      (int)e->terms.size(),
+      [e](int t) { return prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa); }, body);
+}
+
+// What every train x train build of Sigma passes the covariance launch: `out` (leading dimension ldo) takes ti x tj tiles of the
+// lower triangle, y row and identity padding included.  The caller adds what is its own (the grid, the block rows it owns).
+CovTileArgs train_cov_args(gmb_engine* e, double* out, int64_t ldo, int ti, int tj) {
+  CovTileArgs a{};
+  a.p = e->terms[0].cp;
+  a.rows = a.cols = train_set(e);
+  a.out = out;
+  a.ldo = ldo;
+  a.ti = ti;
+  a.tj = tj;
+  a.mode = COV_TRAIN;
+  a.lower_only = 1;
+  a.y = e->dy;
+  return a;
+}
+
+// ... and the build itself: term 0 writes, an additive model's further terms add their covariance to the real entries
+int launch_train_cov(gmb_engine* e, CovTileArgs& a) {
+  return walk_terms(e, [&](int t) {
+    a.p = e->terms[t].cp;
+    a.accumulate = t > 0;
+    return launch_cov(e, a);
+  });
+}
+
 // Covariance build: lower-triangular tiles of Sigma = K + noise + jitter, the y row, identity padding, written
 // column-major into `out` (Nr x Np, leading dimension ldo) -- the factor buffer in gmb_factorize.
 int build_sigma(gmb_engine* e, double* out, int64_t ldo) {
-  int rc;
-  CovTileArgs a{};
-  a.p = e->cp;
-  a.rows = train_set(e);
-  a.cols = train_set(e);
-  a.out = out;
-  a.ldo = ldo;
-  a.i0 = a.j0 = 0;
-  a.ti = (int)(e->Nr / TILE);
-  a.tj = (int)(e->Np / TILE);
-  a.mode = COV_TRAIN;
-  a.lower_only = 1;
+  CovTileArgs a = train_cov_args(e, out, ldo, (int)(e->Nr / TILE), (int)(e->Np / TILE));
   a.tri_grid = 1;
-  a.y = e->dy;
   if (e->prep_deferred) {  // small gmb_evaluate: this launch prepares the points it stages (and clears prep_points_kernel's words)
     e->prep_deferred = false;
     a.inline_prep = 1;
     a.prep = prep_args(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, nullptr);
   }
-  if ((rc = launch_cov(e, a))) return rc;
-  // additive models: the other terms add their covariance to the real entries, one pass each
-  for (size_t t = 1; t < e->terms.size(); ++t) {
-    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) return rc;
-    a.p = e->terms[t].cp;
-    a.accumulate = 1;
-    if ((rc = launch_cov(e, a))) return rc;
-  }
-  if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
-    return rc;
-  return GMB_OK;
+  return launch_train_cov(e, a);
 }
 
 // ---- Cholesky recursion -------------------------------------------------------------------
@@ -1808,7 +1816,6 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
                 std::vector<double>& h) {
   const gmb_kernel_spec& s = e->spec;
   const int nt = (int)(e->Np / TILE);
-  int rc;
   if (!e->gacc_zeroed) HIP_TRY(e, hipMemsetAsync(e->dgpart, 0, (GACC_DOUBLES + 64) * sizeof(double), e->stream));
   e->gacc_zeroed = false;
   const int n_ls = s.ard ? s.n_cont : 1;
@@ -1822,9 +1829,9 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
   const int ncp = e->nc_pad;
   bool merged = false;  // the pass ends in grad_finish_kernel (set inside the one term's iteration)
   GradFinishArgs fin{};
-  for (size_t t = 0; t < e->terms.size(); ++t) {
+  const int walked = walk_terms(e, [&](int t) -> int {
     const gmb_engine::Term& tr = e->terms[t];
-    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
+    int rc;
     GradArgs a{};
     a.p = tr.cp;
     a.pts = train_set(e);
@@ -1949,10 +1956,9 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
         HIP_TRY(e, hipGetLastError());
       }
     }
-  }
-  if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
-    return rc;
+    return GMB_OK;
+  });
+  if (walked) return walked;
   h.assign(GACC_DOUBLES, 0.0);
   if (e->light) {
     // gmb_evaluate on the fused launch: scalars, failure index, abort word and the used head of every accumulator region go to
@@ -2884,27 +2890,10 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
   const FactorRef f = train_factor(e);
   HIP_TRY(e, hipEventRecord(e->fe[0], s));
   {  // block rows >= I0 of Sigma: partial block row, new rows, y row, identity padding
-    CovTileArgs a{};
-    a.p = e->cp;
-    a.rows = train_set(e);
-    a.cols = train_set(e);
-    a.out = e->dA;
-    a.ldo = e->ld;
-    a.ti = nrt;
-    a.tj = nct;
-    a.mode = COV_TRAIN;
-    a.lower_only = 1;
+    CovTileArgs a = train_cov_args(e, e->dA, e->ld, nrt, nct);
     a.row_first = I0;
     a.row_stride = 1;
-    a.y = e->dy;
-    if ((rc = launch_cov(e, a))) return rc;
-    for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: accumulating passes
-      if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa))) return rc;
-      a.p = e->terms[t].cp;
-      a.accumulate = 1;
-      if ((rc = launch_cov(e, a))) return rc;
-    }
-    if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa))) return rc;
+    if ((rc = launch_train_cov(e, a))) return rc;
   }
   HIP_TRY(e, hipEventRecord(e->fe[1], s));
   HIP_TRY(e, hipEventRecord(e->fe[2], s));
@@ -3093,34 +3082,12 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
   int rc;
   HIP_TRY(e, hipMemcpy2DAsync(e->pw.dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double),
                               e->D * sizeof(double), mc, in_kind, e->stream));
-  if ((rc = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat))) return rc;
   const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, mc, mpad};
-  {  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
-    CovTileArgs a{};
-    a.p = e->cp;
-    a.rows = test;
-    a.cols = train_set(e);
-    a.out = e->pw.dV;
-    a.ldo = mpad;
-    a.ti = (int)(mpad / TILE);
-    a.tj = (int)(e->Np / TILE);
-    a.mode = COV_CROSS;
-    ev_begin(e, e->stream, EV_PREDICT_COV, 0.0, a.ti, a.tj);  // (while profiling: the launch on its own in GMB_TRACE_FILE)
-    rc = launch_cov(e, a);
-    ev_end(e);
-    if (rc) return rc;
-  }
-  KssArgs k{};
-  k.p = e->cp;
-  k.pts = test;
-  k.with_noise = with_noise;
-  k.kss = e->pw.dkss;
-  hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
-  for (size_t t = 1; t < e->terms.size(); ++t) {  // additive models: one accumulating pass per further term
+  // term 0 writes, an additive model's further terms add (the noise is the first pass's)
+  return walk_terms(e, [&](int t) -> int {
     const gmb_engine::Term& tr = e->terms[t];
-    if ((rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
     if ((rc = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &tr.pa))) return rc;
-    CovTileArgs a{};
+    CovTileArgs a{};  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
     a.p = tr.cp;
     a.rows = test;
     a.cols = train_set(e);
@@ -3129,17 +3096,20 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     a.ti = (int)(mpad / TILE);
     a.tj = (int)(e->Np / TILE);
     a.mode = COV_CROSS;
-    a.accumulate = 1;
-    if ((rc = launch_cov(e, a))) return rc;
+    a.accumulate = t > 0;
+    if (t == 0) ev_begin(e, e->stream, EV_PREDICT_COV, 0.0, a.ti, a.tj);  // (while profiling: the launch on its own in GMB_TRACE_FILE)
+    rc = launch_cov(e, a);
+    if (t == 0) ev_end(e);
+    if (rc) return rc;
+    KssArgs k{};
     k.p = tr.cp;
-    k.with_noise = 0;
-    k.accumulate = 1;
+    k.pts = test;
+    k.with_noise = t == 0 ? with_noise : 0;
+    k.accumulate = t > 0;
+    k.kss = e->pw.dkss;
     hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
-  }
-  if (e->terms.size() > 1 &&
-      (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa)))
-    return rc;
-  return GMB_OK;
+    return GMB_OK;
+  });
 }
 
 // V <- V L^-T in dV (the solve), or V^T = L^-1 K(X, X*) into dV2 with the cross-covariance left in dV (`gemm_form`)
@@ -3300,13 +3270,14 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
     HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * Mr, 0, (size_t)((e->Np - e->N) * Mr) * sizeof(double), e->stream));
 
   // K(X*, X*): the training build's launch (build_sigma) on the test points -- direct distances on the diagonal tiles, so the
-  // diagonal is gmb_predict's k** to the bit
+  // diagonal is gmb_predict's k** to the bit.  Both point sets are the TEST points (workspace): the terms are visited without
+  // walk_terms, nothing resident is re-prepared.  predict_cross_cov left the test points with the last term's preparation.
   const bool additive = e->terms.size() > 1;
   if (additive && (rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[0].pa))) return rc;
   const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, M, Mr};
   CovTileArgs a{};
-  a.p = e->cp;
-  a.p.sigma2 = with_noise ? e->cp.sigma2 : 0.0;
+  a.p = e->terms[0].cp;
+  if (!with_noise) a.p.sigma2 = 0.0;
   a.p.jitter = jitter;
   a.rows = test;
   a.cols = test;
@@ -3484,10 +3455,8 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
   int nchunk;
   predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
   const PointSet test{e->pg.xs, e->pg.xl, e->pg.cat, mc, mpad};
-  for (size_t t = 0; t < e->terms.size(); ++t) {
+  return walk_terms(e, [&](int t) -> int {
     const gmb_engine::Term& tr = e->terms[t];
-    // term 0's preparation of the training points is the resident one; later terms bring their own (put back below)
-    if (t > 0 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &tr.pa))) return rc;
     if ((rc = prep_points(e, Xs, mc, e->D, mpad, e->pg.xs, e->pg.xl, e->pg.cat, &tr.pa))) return rc;
     PredGradArgs a{};
     a.p = tr.cp;
@@ -3534,9 +3503,8 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     ev_end(e);
     if (rc) return rc;
     HIP_TRY(e, hipGetLastError());
-  }
-  if (e->terms.size() > 1 && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[0].pa))) return rc;
-  return GMB_OK;
+    return GMB_OK;
+  });
 }
 
 // ---- what the five prediction entry points share -------------------------------------------------------------------------------

@@ -1,0 +1,33 @@
+// term_walk.hpp -- the order in which an additive model's covariance terms are visited.
+//
+// The engine keeps ONE prepared copy of the training points, and between calls it holds term 0's preparation.  A pass over the
+// terms re-prepares that copy for every further term; for_each_term is the one place that does so and the one place that puts
+// term 0's preparation back -- on the normal end, when a body fails and when a preparation itself fails.
+//
+// No engine types and no HIP: tools/term_walk_check.cpp drives this very header with recording stubs.
+#pragma once
+
+namespace gmb {
+
+// body(t) for t = 0 .. nterms - 1, prepare_train(t) before every t > 0; both return 0 or an error, and the first error ends the
+// walk and is what the walk returns.  Once a prepare_train(t > 0) has been issued, prepare_train(0) follows on EVERY way out (its
+// own failure is reported only when nothing failed before it).  One term: no prepare_train at all.
+template <typename PrepareTrain, typename Body>
+int for_each_term(int nterms, PrepareTrain&& prepare_train, Body&& body) {
+  int rc = 0;
+  bool moved = false;  // the resident preparation is (or may be) a later term's
+  for (int t = 0; t < nterms && !rc; ++t) {
+    if (t > 0) {
+      moved = true;
+      if ((rc = prepare_train(t))) break;
+    }
+    rc = body(t);
+  }
+  if (moved) {
+    const int back = prepare_train(0);
+    if (!rc) rc = back;
+  }
+  return rc;
+}
+
+}  // namespace gmb
