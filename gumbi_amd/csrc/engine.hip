@@ -43,6 +43,7 @@
 #include "predict_form.hpp"
 #include "joint_predict.hpp"
 #include "predict_grad.hpp"
+#include "predict_terms.hpp"
 
 using namespace gmb;
 
@@ -75,9 +76,10 @@ enum EvKind : int {
   EV_PREDICT_VGRAD = 14,      // gmb_predict_with_grad: the fused partial + finishing launches of one term
   EV_PREDICT_VGRAD_SOLVE = 15, // gmb_predict_with_grad: the second triangular pass W = V L^-1 of one M-tile
   // (ABI 16)
-  EV_SPLITK = 16              // the split-k product's launch pair (gemm_splitk.hpp): flags = slices
+  EV_SPLITK = 16,             // the split-k product's launch pair (gemm_splitk.hpp): flags = slices
+  EV_TERM_GRAM = 17           // gmb_predict_decompose: the reduction's partial + final launches of one M-tile (k = terms)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_SPLITK); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_TERM_GRAM); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -230,6 +232,24 @@ struct gmb_engine {
   bool bs_valid = false;
   // gmb_predict_with_grad: the variance gradient of an M-tile (its partials are a second set in pg_part)
   DevBuf<double> vg_grad;
+  // gmb_predict_decompose (predict_terms.hpp), beside a prediction's workspace of T stacked blocks: the chunked partials of an
+  // M-tile ([chunk][entry][Mt]) and its results (T means, T (T + 1) / 2 covariance rows, the noise: rows of Mt)
+  struct TermsWorkspace : RowGroup {
+    DevBuf<double> part, out;
+    int64_t per_row = 0;  // chunks x entries the rows were sized for
+    int reserve(DevPool& pool, int64_t Mt, int nchunk, int nt) {
+      const int64_t need = (int64_t)nchunk * tg_entries(nt);
+      if (per_row < need) stale();
+      return reserve_rows(Mt, [&] {
+        int rc;
+        per_row = 0;
+        if ((rc = part.renew(pool, need * Mt))) return rc;
+        if ((rc = out.renew(pool, (int64_t)(tg_entries(TG_MAX_TERMS) + 1) * Mt))) return rc;
+        per_row = need;
+        return 0;
+      });
+    }
+  } tg;
 
   // gradient workspace
   DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
@@ -559,7 +579,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_PREDICT_GRAD_ALPHA:
       case EV_PREDICT_VGRAD:
       case EV_PREDICT_VGRAD_SOLVE:
-      case EV_SPLITK: break;
+      case EV_SPLITK:
+      case EV_TERM_GRAM: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -1019,6 +1040,7 @@ int flush_deferred_prep(gmb_engine* e) {
 //   * the prepared points (pts) were marked by gmb_set_data only and stay there: resize_n keeps them when they are large enough.
 void stale_sized_by_n(gmb_engine* e) {
   e->pw.stale();
+  e->tg.stale();
   e->pw2.stale();
   e->dpart.stale();
   e->pg.stale();
@@ -1037,11 +1059,35 @@ FactorRef train_factor(gmb_engine* e) { return FactorRef{e->dA, e->ld, e->N, e->
 // The walk over the model's covariance terms (term_walk.hpp): body(t) runs with the resident training points prepared for term t.
 // This is the ONE place they are re-prepared for a term, and term 0's preparation is back when the walk returns, however it ends.
 // Test points are a body's own business (workspace, not engine state).
+// `mask` selects the terms visited (bit t = terms[t]); a selection is an argument of the call that makes it, never engine state.
+template <typename Body>
+int walk_terms(gmb_engine* e, uint32_t mask, Body&& body) {
+  return for_each_term(
+      (int)e->terms.size(), mask,
+      [e](int t) { return prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa); }, body);
+}
+
+// ... every term: what all train-side builds walk
 template <typename Body>
 int walk_terms(gmb_engine* e, Body&& body) {
-  return for_each_term(
-      (int)e->terms.size(),
-      [e](int t) { return prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, &e->terms[t].pa); }, body);
+  return walk_terms(e, ALL_TERMS, body);
+}
+
+// all bits of a model's selection mask (at most 1 + GMB_MAX_COREG terms)
+uint32_t all_terms_mask(const gmb_engine* e) { return (1u << e->terms.size()) - 1u; }
+
+// Term t's parameters for the pass that STORES (the first selected term): noise and jitter belong to no term and ride on that
+// pass, whichever term it is.  sigma2, the noise table and the jitter are terms[0].cp's -- a later term's own cp holds none of
+// them -- and the noise level is read from the OUTPUT table, which every term's preparation carries last.
+CovParams first_pass_params(const gmb_engine* e, int t) {
+  if (t == 0) return e->terms[0].cp;
+  CovParams p = e->terms[t].cp;
+  const CovParams& p0 = e->terms[0].cp;
+  p.sigma2 = p0.sigma2;
+  p.jitter = p0.jitter;
+  p.noise_mult = p0.noise_mult;
+  p.noise_tab = p0.noise_tab >= 0 ? p.n_tab - 1 : -1;
+  return p;
 }
 
 // What every train x train build of Sigma passes the covariance launch: `out` (leading dimension ldo) takes ti x tj tiles of the
@@ -3077,15 +3123,17 @@ int predict_gemm_form_workspace(gmb_engine* e, int64_t Mt) { return e->pw2.reser
 
 // mc test points (Xs: their first row) -> prepared points in txs / txl / tcat, the cross-covariance K(X*, X) in dV (mpad x Np,
 // test index fastest) and the prior variances (+ noise) in dkss
-int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, int32_t with_noise,
+int predict_cross_cov(gmb_engine* e, uint32_t terms, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, int32_t with_noise,
                       hipMemcpyKind in_kind) {
   int rc;
   HIP_TRY(e, hipMemcpy2DAsync(e->pw.dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double),
                               e->D * sizeof(double), mc, in_kind, e->stream));
   const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, mc, mpad};
-  // term 0 writes, an additive model's further terms add (the noise is the first pass's)
-  return walk_terms(e, [&](int t) -> int {
+  // the first selected term writes, an additive model's further terms add (the noise is the first pass's)
+  const int t_first = first_term(terms);
+  return walk_terms(e, terms, [&](int t) -> int {
     const gmb_engine::Term& tr = e->terms[t];
+    const bool first = t == t_first;
     if ((rc = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &tr.pa))) return rc;
     CovTileArgs a{};  // cross-covariance W[m + i*mpad] = k(x*_m, x_i)
     a.p = tr.cp;
@@ -3096,16 +3144,16 @@ int predict_cross_cov(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
     a.ti = (int)(mpad / TILE);
     a.tj = (int)(e->Np / TILE);
     a.mode = COV_CROSS;
-    a.accumulate = t > 0;
-    if (t == 0) ev_begin(e, e->stream, EV_PREDICT_COV, 0.0, a.ti, a.tj);  // (while profiling: the launch on its own in GMB_TRACE_FILE)
+    a.accumulate = !first;
+    if (first) ev_begin(e, e->stream, EV_PREDICT_COV, 0.0, a.ti, a.tj);  // (while profiling: the launch on its own in GMB_TRACE_FILE)
     rc = launch_cov(e, a);
-    if (t == 0) ev_end(e);
+    if (first) ev_end(e);
     if (rc) return rc;
     KssArgs k{};
-    k.p = tr.cp;
+    k.p = first ? first_pass_params(e, t) : tr.cp;
     k.pts = test;
-    k.with_noise = t == 0 ? with_noise : 0;
-    k.accumulate = t > 0;
+    k.with_noise = first ? with_noise : 0;
+    k.accumulate = !first;
     k.kss = e->pw.dkss;
     hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
     return GMB_OK;
@@ -3252,13 +3300,13 @@ int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, 
 // The posterior mean of all M points into dmean and the lower-triangle tiles of
 //   C = K(X*, X*) - V V^T (+ noise) + jitter I
 // into jt.dC (bordered layout of the training build: Mr x Mp, identity on the padding, a zero row where y would sit).
-int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter, bool gemm_form,
-                     hipMemcpyKind in_kind) {
+int joint_covariance(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                     bool gemm_form, hipMemcpyKind in_kind) {
   JointState& jt = e->jt;
   const int64_t Mr = jt.Mr, Mp = jt.Mp;
   int rc;
   // V for all M points at once, in the form gmb_predict would take, and the mean by gmb_predict's own reductions
-  if ((rc = predict_cross_cov(e, Xs, M, Mr, ldxs, with_noise, in_kind))) return rc;
+  if ((rc = predict_cross_cov(e, terms, Xs, M, Mr, ldxs, with_noise, in_kind))) return rc;
   if ((rc = predict_solve_v(e, Mr, gemm_form))) return rc;
   if ((rc = predict_reduce(e, M, Mr, gemm_form))) return rc;
   // the product form leaves V with the training index fastest: turned into the update's k-major layout (the cross-covariance
@@ -3271,14 +3319,14 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
 
   // K(X*, X*): the training build's launch (build_sigma) on the test points -- direct distances on the diagonal tiles, so the
   // diagonal is gmb_predict's k** to the bit.  Both point sets are the TEST points (workspace): the terms are visited without
-  // walk_terms, nothing resident is re-prepared.  predict_cross_cov left the test points with the last term's preparation.
-  const bool additive = e->terms.size() > 1;
-  if (additive && (rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[0].pa))) return rc;
+  // walk_terms, nothing resident is re-prepared.  predict_cross_cov left the test points with the last selected term's
+  // preparation, so a selection of one term builds on it as it is.  The first selected term's pass stores -- identity padding,
+  // zero border row, and the model's noise and the call's jitter on the diagonal (first_pass_params) -- and the others add.
+  const int nterms = (int)e->terms.size();
+  int nsel = 0;
+  for (int t = 0; t < nterms; ++t) nsel += (int)((terms >> t) & 1u);
   const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, M, Mr};
   CovTileArgs a{};
-  a.p = e->terms[0].cp;
-  if (!with_noise) a.p.sigma2 = 0.0;
-  a.p.jitter = jitter;
   a.rows = test;
   a.cols = test;
   a.out = jt.dC;
@@ -3289,12 +3337,20 @@ int joint_covariance(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
   a.lower_only = 1;
   a.tri_grid = 1;
   a.y = jt.dzero;
-  if ((rc = launch_cov(e, a))) return rc;
-  for (size_t t = 1; t < e->terms.size(); ++t) {
-    if ((rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[t].pa))) return rc;
-    a.p = e->terms[t].cp;
-    a.accumulate = 1;
+  bool first = true;
+  for (int t = 0; t < nterms; ++t) {
+    if (!((terms >> t) & 1u)) continue;
+    if (nsel > 1 && (rc = prep_points(e, e->pw.dXs, M, e->D, Mr, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[t].pa))) return rc;
+    if (first) {
+      a.p = first_pass_params(e, t);
+      if (!with_noise) a.p.sigma2 = 0.0;
+      a.p.jitter = jitter;
+    } else {
+      a.p = e->terms[t].cp;
+      a.accumulate = 1;
+    }
     if ((rc = launch_cov(e, a))) return rc;
+    first = false;
   }
 
   // C -= V V^T: the trailing update's launch with contraction length Np (rows of the border stay as built: V is zero there)
@@ -3446,7 +3502,7 @@ int predict_grad_workspace(gmb_engine* e, int64_t Mt, int nset) {
 
 // d mu / d x* of one M-tile (mc raw points on the device, D per row, first row Xs) into pg_grad (mc x D, row-major); with
 // W = K(X*, X) Sigma^-1 of the tile (mpad rows, test index fastest) also d sigma^2 / d x* into vg_grad.  W == nullptr: the mean only.
-int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, const double* alpha, const double* W) {
+int predict_grad_tile(gmb_engine* e, uint32_t terms, const double* Xs, int64_t mc, int64_t mpad, const double* alpha, const double* W) {
   int rc;
   const int nset = W ? 2 : 1;
   HIP_TRY(e, hipMemsetAsync(e->pg.grad, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
@@ -3455,7 +3511,7 @@ int predict_grad_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad,
   int nchunk;
   predict_grad_chunk(e->N, mpad, &chunk, &nchunk);
   const PointSet test{e->pg.xs, e->pg.xl, e->pg.cat, mc, mpad};
-  return walk_terms(e, [&](int t) -> int {
+  return walk_terms(e, terms, [&](int t) -> int {
     const gmb_engine::Term& tr = e->terms[t];
     if ((rc = prep_points(e, Xs, mc, e->D, mpad, e->pg.xs, e->pg.xl, e->pg.cat, &tr.pa))) return rc;
     PredGradArgs a{};
@@ -3538,6 +3594,244 @@ int predict_end(gmb_engine* e, PhaseTimer* tp, int rc) {
   return GMB_OK;
 }
 
+// The selection of a prediction call: `sel` null = every term (the entry points without a selection), else the caller's mask,
+// refused -- before anything is launched -- when it is empty or names a term the model does not have.
+int resolve_terms(gmb_engine* e, const uint32_t* sel, const char* what, uint32_t* mask) {
+  const uint32_t all = all_terms_mask(e);
+  if (!sel) {
+    *mask = all;
+    return GMB_OK;
+  }
+  if (*sel == 0 || (*sel & ~all))
+    return fail(e, GMB_EINVAL, "%s: terms = 0x%x selects %s (the model has %d term%s: bits 0 .. %d)", what, (unsigned)*sel,
+                *sel == 0 ? "nothing" : "a term the model does not have", (int)e->terms.size(), e->terms.size() == 1 ? "" : "s",
+                (int)e->terms.size() - 1);
+  *mask = *sel;
+  return GMB_OK;
+}
+
+// the M-tile of gmb_predict_decompose: T stacked blocks within the prediction's 8 GiB rule
+int64_t decompose_tile_rows(const gmb_engine* e, int64_t M) {
+  const int64_t T = (int64_t)e->terms.size();
+  const int64_t mt_max = predict_tile_rows(e, (int64_t)1 << 40);  // a prediction's largest M-tile behind this N
+  return std::min<int64_t>(std::max<int64_t>(TILE, mt_max / T / TILE * TILE), round_up(M, TILE));
+}
+
+template <int NT>
+void launch_term_gram_nt(gmb_engine* e, dim3 grid, int64_t ldz, int64_t mpad) {
+  hipLaunchKernelGGL(term_gram_partial_kernel<NT>, grid, dim3(256), 0, e->stream, e->pw.dV, ldz, mpad, e->dv, e->N, e->tg.part);
+}
+
+// one M-tile of gmb_predict_decompose: the T cross-covariances stacked in dV, one solve, the reductions; results in tg.out
+int decompose_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs, hipMemcpyKind in_kind) {
+  int rc;
+  const int T = (int)e->terms.size();
+  const int64_t ldz = (int64_t)T * mpad;
+  double* means = e->tg.out;
+  double* cov = means + (int64_t)T * mpad;
+  double* noise = cov + (int64_t)(T * (T + 1) / 2) * mpad;
+  HIP_TRY(e, hipMemcpy2DAsync(e->pw.dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double), e->D * sizeof(double), mc, in_kind, e->stream));
+  const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, mc, mpad};
+  rc = walk_terms(e, all_terms_mask(e), [&](int t) -> int {
+    const gmb_engine::Term& tr = e->terms[t];
+    int r;
+    if ((r = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &tr.pa))) return r;
+    CovTileArgs a{};  // term t's block: W[t mpad + m + i ldz] = k_t(x*_m, x_i)
+    a.p = tr.cp;
+    a.rows = test;
+    a.cols = train_set(e);
+    a.out = e->pw.dV + (int64_t)t * mpad;
+    a.ldo = ldz;
+    a.ti = (int)(mpad / TILE);
+    a.tj = (int)(e->Np / TILE);
+    a.mode = COV_CROSS;
+    a.accumulate = 0;
+    if ((r = launch_cov(e, a))) return r;
+    KssArgs k{};
+    k.p = tr.cp;
+    k.pts = test;
+    k.with_noise = 0;
+    k.accumulate = 0;
+    k.kss = e->pw.dkss + (int64_t)t * mpad;
+    hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
+    if (t == 0)  // (the test points hold term 0's preparation here)
+      hipLaunchKernelGGL(term_noise_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, tr.cp, test, noise);
+    HIP_TRY(e, hipGetLastError());
+    return GMB_OK;
+  });
+  if (rc) return rc;
+  if ((rc = predict_solve_v(e, ldz, false))) return rc;  // all T blocks at once; neither dW nor U is touched
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const dim3 grid((unsigned)((mpad + 255) / 256), (unsigned)nchunk);
+  ev_begin(e, e->stream, EV_TERM_GRAM, 0.0, (int)(mpad / TILE), nchunk, T);
+  switch (T) {
+    case 1: launch_term_gram_nt<1>(e, grid, ldz, mpad); break;
+    case 2: launch_term_gram_nt<2>(e, grid, ldz, mpad); break;
+    case 3: launch_term_gram_nt<3>(e, grid, ldz, mpad); break;
+    case 4: launch_term_gram_nt<4>(e, grid, ldz, mpad); break;
+    case 5: launch_term_gram_nt<5>(e, grid, ldz, mpad); break;
+    default: break;  // (gmb_predict_decompose has refused more than TG_MAX_TERMS terms)
+  }
+  hipLaunchKernelGGL(term_gram_final_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)tg_entries(T)), dim3(256), 0, e->stream,
+                     e->tg.part, nchunk, T, mpad, e->pw.dkss, mc, means, cov);
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// ---- the selecting forms of the four prediction calls; `sel` null: every term, i.e. the calls without a selection ---------------
+
+int predict_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                double* mean, double* var, int32_t memspace) {
+  int rc = require_ready(e, true);
+  if (rc) return rc;
+  if (sel && (e->solve_hook || e->dist_mode != 0 || e->factor_kind != gmb_engine::FK_SINGLE))
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode): factorise with gmb_factorize on one device", what);
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !mean || !var)) || ldxs < e->D)
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var");
+  if (M == 0) return GMB_OK;
+  // (the capacity driver's passes come through here with their own triangular solve; everybody else reads the factor in dA)
+  if ((rc = e->solve_hook ? require_capacity_factor(e, what) : require_full_factor(e, what))) return rc;
+  if (e->factor_consumed)
+    return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
+  HIP_TRY(e, hipSetDevice(e->device));
+  reset_predict_timings(e);
+
+  const int64_t Mt = predict_tile_rows(e, M);
+  if ((rc = predict_workspace(e, Mt))) return rc;
+  // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
+  const bool use_gemm_form = predict_takes_gemm_form(e);
+  if (use_gemm_form && (rc = predict_gemm_form_workspace(e, Mt))) return rc;
+  e->tm.predict_gemm_form = use_gemm_form ? 1 : 0;
+
+  const CopyKinds ck = copy_kinds(memspace);
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = predict_cross_cov(e, terms, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
+      if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
+      if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream));
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
+int predict_grad_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, double* grad,
+                     int64_t ldg, int32_t memspace) {
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !grad)) || ldxs < e->D || ldg < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/grad/ldg");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  // 16384 points per tile: 256 blocks of 64, i.e. four chunks of the training set -- partials of 4 x the tile's gradient
+  const int64_t Mt = std::min<int64_t>(round_up(M, TILE), 16384);
+  if ((rc = predict_grad_workspace(e, Mt, 1))) return rc;
+  const double* alpha = nullptr;
+  if ((rc = resident_alpha(e, &alpha))) return predict_end(e, nullptr, rc);
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      HIP_TRY(e, hipMemcpy2DAsync(e->pg.Xs, row, Xs + m0 * ldxs, ldxs * sizeof(double), row, mc, ck.in, e->stream));
+      if ((rc = predict_grad_tile(e, terms, e->pg.Xs, mc, round_up(mc, TILE), alpha, nullptr))) return rc;
+      if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, mc, ck.out, e->stream) != hipSuccess)
+        return fail(e, GMB_EHIP, "%s: copying the gradient out failed", what);
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, nullptr, tiles());
+}
+
+int predict_joint_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                      double jitter, double* mean, double* cov, int64_t ldc, int32_t memspace) {
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !mean || !cov)) || ldxs < e->D || ldc < M || !(jitter >= 0.0))
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/cov/ldc/jitter");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = joint_workspace(e, what, M, gemm_form, host ? (double)M * (double)M : 0.0))) return rc;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+  const CopyKinds ck = copy_kinds(memspace);
+  PhaseTimer tp(e);
+  auto work = [&]() -> int {
+    if ((rc = joint_covariance(e, terms, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
+    SymArgs sa{};
+    sa.C = e->jt.dC;
+    sa.ldc = e->jt.Mr;
+    sa.out = host ? e->jt.dstage : cov;
+    sa.ldo = host ? M : ldc;
+    sa.M = M;
+    const unsigned nb = (unsigned)((M + 31) / 32);
+    hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
+                                  hipMemcpyDeviceToHost, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
+}
+
+int draw_joint_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                   double jitter, const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace) {
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (M < 0 || S < 0 || S > 0x7fffffff || (M > 0 && S > 0 && (!Xs || !Z || !Y)) || ldxs < e->D || ldz < M || ldy < M || !(jitter >= 0.0))
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/Z/S/ldz/Y/ldy/jitter");
+  if (M == 0 || S == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = joint_workspace(e, what, M, gemm_form, host ? 2.0 * (double)S * (double)M : 0.0))) return rc;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+  const CopyKinds ck = copy_kinds(memspace);
+  PhaseTimer tp(e);
+  auto work = [&]() -> int {
+    if ((rc = joint_covariance(e, terms, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
+    if ((rc = joint_factor(e))) return rc;
+    DrawArgs da{};
+    da.L = e->jt.dC;
+    da.ldl = e->jt.Mr;
+    da.mean = e->pw.dmean;
+    da.M = M;
+    da.S = (int32_t)S;
+    if (host) {
+      double* dZ = e->jt.dstage;
+      double* dY = e->jt.dstage + S * M;
+      HIP_TRY(e, hipMemcpy2DAsync(dZ, M * sizeof(double), Z, ldz * sizeof(double), M * sizeof(double), S, hipMemcpyHostToDevice, e->stream));
+      da.Z = dZ, da.ldz = M, da.Y = dY, da.ldy = M;
+    } else {
+      da.Z = Z, da.ldz = ldz, da.Y = Y, da.ldy = ldy;
+    }
+    if ((rc = launch_draw(e, da))) return rc;
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
+    if (mean) HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
+}
+
 }  // namespace
 
 extern "C" {
@@ -3558,66 +3852,21 @@ int gmb_nlml(gmb_engine* e, double* nlml, double* grad) {
 
 int gmb_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
                 double* mean, double* var, int32_t memspace) {
-  int rc = require_ready(e, true);
-  if (rc) return rc;
-  if (M < 0 || (M > 0 && (!Xs || !mean || !var)) || ldxs < e->D)
-    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var");
-  if (M == 0) return GMB_OK;
-  // (the capacity driver's passes come through here with their own triangular solve; everybody else reads the factor in dA)
-  if ((rc = e->solve_hook ? require_capacity_factor(e, "gmb_predict") : require_full_factor(e, "gmb_predict"))) return rc;
-  if (e->factor_consumed)
-    return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
-  HIP_TRY(e, hipSetDevice(e->device));
-  reset_predict_timings(e);
+  return predict_sel(e, nullptr, "gmb_predict", Xs, M, ldxs, with_noise, mean, var, memspace);
+}
 
-  const int64_t Mt = predict_tile_rows(e, M);
-  if ((rc = predict_workspace(e, Mt))) return rc;
-  // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
-  const bool use_gemm_form = predict_takes_gemm_form(e);
-  if (use_gemm_form && (rc = predict_gemm_form_workspace(e, Mt))) return rc;
-  e->tm.predict_gemm_form = use_gemm_form ? 1 : 0;
-
-  const CopyKinds ck = copy_kinds(memspace);
-  PhaseTimer tp(e);
-  auto tiles = [&]() -> int {
-    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
-      const int64_t mc = std::min<int64_t>(Mt, M - m0);
-      const int64_t mpad = round_up(mc, TILE);
-      if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
-      if ((rc = predict_solve_v(e, mpad, use_gemm_form))) return rc;
-      if ((rc = predict_reduce(e, mc, mpad, use_gemm_form))) return rc;
-      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream));
-      HIP_TRY(e, hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream));
-    }
-    return GMB_OK;
-  };
-  return predict_end(e, &tp, tiles());
+int gmb_predict_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                      double* mean, double* var, int32_t memspace) {
+  return predict_sel(e, &terms, "gmb_predict_terms", Xs, M, ldxs, with_noise, mean, var, memspace);
 }
 
 int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg, int32_t memspace) {
-  int rc = joint_ready(e, "gmb_predict_grad");
-  if (rc) return rc;
-  if (M < 0 || (M > 0 && (!Xs || !grad)) || ldxs < e->D || ldg < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/grad/ldg");
-  if (M == 0) return GMB_OK;
-  HIP_TRY(e, hipSetDevice(e->device));
-  // 16384 points per tile: 256 blocks of 64, i.e. four chunks of the training set -- partials of 4 x the tile's gradient
-  const int64_t Mt = std::min<int64_t>(round_up(M, TILE), 16384);
-  if ((rc = predict_grad_workspace(e, Mt, 1))) return rc;
-  const double* alpha = nullptr;
-  if ((rc = resident_alpha(e, &alpha))) return predict_end(e, nullptr, rc);
-  const CopyKinds ck = copy_kinds(memspace);
-  const size_t row = e->D * sizeof(double);
-  auto tiles = [&]() -> int {
-    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
-      const int64_t mc = std::min<int64_t>(Mt, M - m0);
-      HIP_TRY(e, hipMemcpy2DAsync(e->pg.Xs, row, Xs + m0 * ldxs, ldxs * sizeof(double), row, mc, ck.in, e->stream));
-      if ((rc = predict_grad_tile(e, e->pg.Xs, mc, round_up(mc, TILE), alpha, nullptr))) return rc;
-      if (hipMemcpy2DAsync(grad + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, mc, ck.out, e->stream) != hipSuccess)
-        return fail(e, GMB_EHIP, "gmb_predict_grad: copying the gradient out failed");
-    }
-    return GMB_OK;
-  };
-  return predict_end(e, nullptr, tiles());
+  return predict_grad_sel(e, nullptr, "gmb_predict_grad", Xs, M, ldxs, grad, ldg, memspace);
+}
+
+int gmb_predict_grad_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, double* grad, int64_t ldg,
+                           int32_t memspace) {
+  return predict_grad_sel(e, &terms, "gmb_predict_grad_terms", Xs, M, ldxs, grad, ldg, memspace);
 }
 
 int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
@@ -3642,12 +3891,12 @@ int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
     for (int64_t m0 = 0; m0 < M; m0 += Mt) {
       const int64_t mc = std::min<int64_t>(Mt, M - m0);
       const int64_t mpad = round_up(mc, TILE);
-      if ((rc = predict_cross_cov(e, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
+      if ((rc = predict_cross_cov(e, ALL_TERMS, Xs + m0 * ldxs, mc, mpad, ldxs, with_noise, ck.in))) return rc;
       if ((rc = predict_solve_v(e, mpad, false))) return rc;
       if ((rc = predict_reduce(e, mc, mpad, false))) return rc;
       if ((rc = predict_solve_w(e, mpad))) return rc;
       // (the tile's raw points are in dXs: predict_cross_cov; W = K(X*, X) Sigma^-1 in dV)
-      if ((rc = predict_grad_tile(e, e->pw.dXs, mc, mpad, alpha, e->pw.dV))) return rc;
+      if ((rc = predict_grad_tile(e, ALL_TERMS, e->pw.dXs, mc, mpad, alpha, e->pw.dV))) return rc;
       if (hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
           hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
           hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, mc, ck.out, e->stream) != hipSuccess ||
@@ -3661,78 +3910,65 @@ int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
 
 int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
                       double* mean, double* cov, int64_t ldc, int32_t memspace) {
-  int rc = joint_ready(e, "gmb_predict_joint");
-  if (rc) return rc;
-  if (M < 0 || (M > 0 && (!Xs || !mean || !cov)) || ldxs < e->D || ldc < M || !(jitter >= 0.0))
-    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/cov/ldc/jitter");
-  if (M == 0) return GMB_OK;
-  HIP_TRY(e, hipSetDevice(e->device));
-  const bool host = memspace != GMB_DEVICE;
-  const bool gemm_form = predict_takes_gemm_form(e);
-  if ((rc = joint_workspace(e, "gmb_predict_joint", M, gemm_form, host ? (double)M * (double)M : 0.0))) return rc;
-  reset_predict_timings(e);
-  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
-  const CopyKinds ck = copy_kinds(memspace);
-  PhaseTimer tp(e);
-  auto work = [&]() -> int {
-    if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
-    SymArgs sa{};
-    sa.C = e->jt.dC;
-    sa.ldc = e->jt.Mr;
-    sa.out = host ? e->jt.dstage : cov;
-    sa.ldo = host ? M : ldc;
-    sa.M = M;
-    const unsigned nb = (unsigned)((M + 31) / 32);
-    hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
-    if (host)
-      HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), e->jt.dstage, M * sizeof(double), M * sizeof(double), M,
-                                  hipMemcpyDeviceToHost, e->stream));
-    return GMB_OK;
-  };
-  return predict_end(e, &tp, work());
+  return predict_joint_sel(e, nullptr, "gmb_predict_joint", Xs, M, ldxs, with_noise, jitter, mean, cov, ldc, memspace);
+}
+
+int gmb_predict_joint_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                            double* mean, double* cov, int64_t ldc, int32_t memspace) {
+  return predict_joint_sel(e, &terms, "gmb_predict_joint_terms", Xs, M, ldxs, with_noise, jitter, mean, cov, ldc, memspace);
 }
 
 int gmb_draw_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
                    const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace) {
-  int rc = joint_ready(e, "gmb_draw_joint");
+  return draw_joint_sel(e, nullptr, "gmb_draw_joint", Xs, M, ldxs, with_noise, jitter, Z, S, ldz, Y, ldy, mean, memspace);
+}
+
+int gmb_draw_joint_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                         const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace) {
+  return draw_joint_sel(e, &terms, "gmb_draw_joint_terms", Xs, M, ldxs, with_noise, jitter, Z, S, ldz, Y, ldy, mean, memspace);
+}
+
+int gmb_num_terms(const gmb_engine* e) {
+  if (!e || !e->have_theta || e->terms.empty()) return GMB_EINVAL;
+  return (int)e->terms.size();
+}
+
+int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* means, int64_t ldm, double* cov,
+                          int64_t ldcv, double* noise, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_predict_decompose");
   if (rc) return rc;
-  if (M < 0 || S < 0 || S > 0x7fffffff || (M > 0 && S > 0 && (!Xs || !Z || !Y)) || ldxs < e->D || ldz < M || ldy < M || !(jitter >= 0.0))
-    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/Z/S/ldz/Y/ldy/jitter");
-  if (M == 0 || S == 0) return GMB_OK;
+  if (M < 0 || (M > 0 && (!Xs || !means || !cov)) || ldxs < e->D || ldm < M || ldcv < M)
+    return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/means/ldm/cov/ldcv");
+  if (M == 0) return GMB_OK;
+  const int T = (int)e->terms.size();
+  if (T > TG_MAX_TERMS) return fail(e, GMB_EINVAL, "gmb_predict_decompose: %d terms (at most %d)", T, TG_MAX_TERMS);
   HIP_TRY(e, hipSetDevice(e->device));
-  const bool host = memspace != GMB_DEVICE;
-  const bool gemm_form = predict_takes_gemm_form(e);
-  if ((rc = joint_workspace(e, "gmb_draw_joint", M, gemm_form, host ? 2.0 * (double)S * (double)M : 0.0))) return rc;
   reset_predict_timings(e);
-  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+  e->tm.predict_gemm_form = 0;  // the stacked V is always solved for, as in gmb_predict_with_grad: neither dW nor U is touched
+  const int64_t Mt = decompose_tile_rows(e, M);
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  // every allocation before the first launch: T stacked blocks in the prediction's workspace, the partials, the results
+  if ((rc = predict_workspace(e, (int64_t)T * Mt))) return rc;
+  if ((rc = e->tg.reserve(e->pool, Mt, nchunk, T))) return rc;
   const CopyKinds ck = copy_kinds(memspace);
+  const int np = T * (T + 1) / 2;
   PhaseTimer tp(e);
-  auto work = [&]() -> int {
-    if ((rc = joint_covariance(e, Xs, M, ldxs, with_noise, jitter, gemm_form, ck.in))) return rc;
-    if ((rc = joint_factor(e))) return rc;
-    DrawArgs da{};
-    da.L = e->jt.dC;
-    da.ldl = e->jt.Mr;
-    da.mean = e->pw.dmean;
-    da.M = M;
-    da.S = (int32_t)S;
-    if (host) {
-      double* dZ = e->jt.dstage;
-      double* dY = e->jt.dstage + S * M;
-      HIP_TRY(e, hipMemcpy2DAsync(dZ, M * sizeof(double), Z, ldz * sizeof(double), M * sizeof(double), S, hipMemcpyHostToDevice, e->stream));
-      da.Z = dZ, da.ldz = M, da.Y = dY, da.ldy = M;
-    } else {
-      da.Z = Z, da.ldz = ldz, da.Y = Y, da.ldy = ldy;
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = decompose_tile(e, Xs + m0 * ldxs, mc, mpad, ldxs, ck.in))) return rc;
+      const double* dmeans = e->tg.out;
+      const double* dcov = dmeans + (int64_t)T * mpad;
+      const double* dnoise = dcov + (int64_t)np * mpad;
+      if (hipMemcpy2DAsync(means + m0, ldm * sizeof(double), dmeans, mpad * sizeof(double), mc * sizeof(double), T, ck.out, e->stream) != hipSuccess ||
+          hipMemcpy2DAsync(cov + m0, ldcv * sizeof(double), dcov, mpad * sizeof(double), mc * sizeof(double), np, ck.out, e->stream) != hipSuccess ||
+          (noise && hipMemcpyAsync(noise + m0, dnoise, mc * sizeof(double), ck.out, e->stream) != hipSuccess))
+        return fail(e, GMB_EHIP, "gmb_predict_decompose: copying the results out failed");
     }
-    if ((rc = launch_draw(e, da))) return rc;
-    if (host)
-      HIP_TRY(e, hipMemcpy2DAsync(Y, ldy * sizeof(double), da.Y, M * sizeof(double), M * sizeof(double), S, hipMemcpyDeviceToHost, e->stream));
-    if (mean) HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, M * sizeof(double), ck.out, e->stream));
     return GMB_OK;
   };
-  return predict_end(e, &tp, work());
+  return predict_end(e, &tp, tiles());
 }
 
 int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, int64_t nc, double* out) {

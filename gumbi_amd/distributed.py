@@ -281,6 +281,12 @@ def make_comm(device_index: int, group=None, prefer: str | None = None):
     return TorchDistComm(device_index, group)
 
 
+def _no_terms(terms, what):
+    if terms is not None:
+        raise NotImplementedError(f"{what}: the components of an additive model are not built for distributed GPs "
+                                  "(the *_terms calls need the complete factor of a single-engine factorisation)")
+
+
 class DistributedEngine:
     """Same calls as :class:`gumbi_amd.engine.Engine` (``set_data / set_kernel / set_theta / factorize / nlml /
     predict``), executed by the native multi-GPU driver over the ranks of ``group``.  Every rank makes the same
@@ -354,16 +360,20 @@ class DistributedEngine:
             self._raise_transport()
             raise
 
-    def predict(self, Xs, with_noise=True):
+    def predict_decompose(self, Xs):
+        _no_terms(0, "predict_decompose")
+
+    def predict(self, Xs, with_noise=True, terms=None):
         """Every rank passes the same ``Xs``; the points are sharded over the ranks and every rank receives
         the complete (mean, var)."""
+        _no_terms(terms, "predict(terms=...)")
         try:
             return self.eng.dist_predict(self.comm, np.asarray(Xs, dtype=np.float64), with_noise)
         except GumbiHipError:
             self._raise_transport()
             raise
 
-    def predict_grad(self, Xs):
+    def predict_grad(self, Xs, terms=None):
         raise NotImplementedError("predict_grad: the posterior mean's gradient is not built for distributed GPs (gmb_predict_grad "
                                   "needs the complete factor of a single-engine factorisation)")
 

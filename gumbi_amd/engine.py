@@ -337,6 +337,16 @@ _SIGNATURES = {
     "gmb_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
     "gmb_truncate": (C.c_int, [C.c_void_p, C.c_int64]),
     "gmb_num_obs": (C.c_int64, [C.c_void_p]),
+    "gmb_num_terms": (C.c_int, [C.c_void_p]),
+    "gmb_predict_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_int32]),
+    "gmb_predict_grad_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_predict_joint_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_draw_joint_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
+                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    "gmb_predict_decompose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int32]),
 }
 
 
@@ -379,7 +389,9 @@ def _preload_hip_runtime():
 #: ``gmb_predict_joint`` / ``gmb_draw_joint``; version 12 periodic kernels: ``gmb_set_periodic``; version 13 the GEMM test door
 #: ``gmb_blk_gemm_ex`` / ``gmb_gemm_desc``; version 14 the posterior mean's gradient ``gmb_predict_grad``; version 15 mean and
 #: variance with both gradients in one call, ``gmb_predict_with_grad``; version 16 ``gmb_append`` / ``gmb_truncate`` -- observations
-#: appended to / cut from the resident factor -- and the split-k GEMM's test door ``gmb_blk_gemm_splitk``)
+#: appended to / cut from the resident factor -- and the split-k GEMM's test door ``gmb_blk_gemm_splitk``; added to version 16
+#: without a change of layout: the components of an additive model, ``gmb_num_terms``, the ``gmb_*_terms`` forms of the four
+#: prediction calls and ``gmb_predict_decompose``)
 ABI_VERSION = 16
 
 
@@ -409,6 +421,24 @@ def load_library():
 
 def _ptr(arr):
     return arr.ctypes.data_as(C.c_void_p)
+
+
+def terms_mask(terms) -> int:
+    """A term selection as the ``*_terms`` calls take it: an ``int`` is the mask itself (bit t = term t: 0 the global kernel,
+    1 + j coregion dimension j), anything else an iterable of term indices.  Whether the model has those terms is the engine's
+    to say (``ValueError``)."""
+    if isinstance(terms, (int, np.integer)) and not isinstance(terms, bool):
+        mask = int(terms)
+    else:
+        mask = 0
+        for t in terms:
+            t = int(t)
+            if not 0 <= t < 32:
+                raise ValueError(f"term index {t} out of range")
+            mask |= 1 << t
+    if not 0 <= mask < 2 ** 32:
+        raise ValueError(f"terms mask {mask} does not fit 32 bits")
+    return mask
 
 
 def _dptr(arr):
@@ -571,13 +601,31 @@ class Engine:
         self._check(self._lib.gmb_evaluate(self._h, _dptr(theta), theta.size, C.byref(val), _dptr(g) if grad else None), "gmb_evaluate")
         return (val.value, g) if grad else val.value
 
-    def predict(self, Xs, with_noise=True):
+    @property
+    def num_terms(self) -> int:
+        """Covariance terms of the model (``gmb_num_terms``): 1, or 1 + the coregion dimensions of an additive spec."""
+        n = int(self._lib.gmb_num_terms(self._h))
+        if n < 0:
+            raise ValueError("gmb_num_terms: gmb_set_theta has not been called")
+        return n
+
+    def predict(self, Xs, with_noise=True, terms=None):
+        """Posterior mean and variance at the rows of ``Xs``.  ``terms`` (a mask or an iterable of term indices,
+        :func:`terms_mask`) restricts an additive model to a selection of its terms (``gmb_predict_terms``); ``with_noise`` then
+        still adds the model's noise."""
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)
         if Xs.ndim != 2 or Xs.shape[1] != self.D:
             raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
         M = Xs.shape[0]
         mean = np.empty(M, dtype=np.float64)
         var = np.empty(M, dtype=np.float64)
+        if terms is not None:
+            self._check(
+                self._lib.gmb_predict_terms(self._h, terms_mask(terms), _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), _ptr(mean),
+                                            _ptr(var), GMB_HOST),
+                "gmb_predict_terms",
+            )
+            return mean, var
         self._check(
             self._lib.gmb_predict(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), _ptr(mean), _ptr(var),
                                   GMB_HOST),
@@ -591,7 +639,7 @@ class Engine:
             raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
         return Xs
 
-    def predict_joint(self, Xs, with_noise=True, jitter=0.0):
+    def predict_joint(self, Xs, with_noise=True, jitter=0.0, terms=None):
         """Posterior mean (M) and the full M x M posterior covariance ``K** - V V^T (+ noise) + jitter I`` at the rows of
         ``Xs`` (``gmb_predict_joint``; ``pm.gp.Marginal._build_conditional(..., diag=False)``).  ``MemoryError`` -- raised
         before anything is computed -- when the device cannot hold the request."""
@@ -599,6 +647,13 @@ class Engine:
         M = Xs.shape[0]
         mean = np.empty(M, dtype=np.float64)
         cov = np.empty((M, M), dtype=np.float64)
+        if terms is not None:  # a selection of an additive model's terms (gmb_predict_joint_terms)
+            self._check(
+                self._lib.gmb_predict_joint_terms(self._h, terms_mask(terms), _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)),
+                                                  float(jitter), _ptr(mean), _ptr(cov), M, GMB_HOST),
+                "gmb_predict_joint_terms",
+            )
+            return mean, cov
         self._check(
             self._lib.gmb_predict_joint(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), float(jitter), _ptr(mean),
                                         _ptr(cov), M, GMB_HOST),
@@ -606,7 +661,7 @@ class Engine:
         )
         return mean, cov
 
-    def draw_joint(self, Xs, Z, with_noise=False, jitter=1e-6, return_mean=False):
+    def draw_joint(self, Xs, Z, with_noise=False, jitter=1e-6, return_mean=False, terms=None):
         """``Y[s] = mean + L* Z[s]`` for the S rows of ``Z`` (S x M standard normals of the caller's), ``L*`` the lower Cholesky
         factor of ``predict_joint``'s covariance (``gmb_draw_joint``): S correlated draws of the posterior at the rows of
         ``Xs``, a deterministic function of (model, theta, Xs, Z).  ``LinAlgError`` when that covariance is not positive
@@ -619,6 +674,13 @@ class Engine:
         S = Z.shape[0]
         Y = np.empty((S, M), dtype=np.float64)
         mean = np.empty(M, dtype=np.float64)
+        if terms is not None:  # a selection of an additive model's terms (gmb_draw_joint_terms)
+            self._check(
+                self._lib.gmb_draw_joint_terms(self._h, terms_mask(terms), _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), float(jitter),
+                                               _ptr(Z), S, max(M, 1), _ptr(Y), max(M, 1), _ptr(mean), GMB_HOST),
+                "gmb_draw_joint_terms",
+            )
+            return (Y, mean) if return_mean else Y
         self._check(
             self._lib.gmb_draw_joint(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), float(jitter), _ptr(Z), S, max(M, 1),
                                      _ptr(Y), max(M, 1), _ptr(mean), GMB_HOST),
@@ -626,7 +688,7 @@ class Engine:
         )
         return (Y, mean) if return_mean else Y
 
-    def predict_grad(self, Xs):
+    def predict_grad(self, Xs, terms=None):
         """Gradient of the posterior mean with respect to the test point at the rows of ``Xs``: ``(M, D)``, one column per
         column of ``X`` -- the kernel's continuous columns carry the derivative, every other column 0 (``gmb_predict_grad``).
         Needs the resident factor as ``predict`` does and leaves it, and everything a fit left beside it, untouched."""
@@ -635,8 +697,32 @@ class Engine:
             raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
         M = Xs.shape[0]
         grad = np.empty((M, self.D), dtype=np.float64)
+        if terms is not None:  # a selection of an additive model's terms (gmb_predict_grad_terms)
+            self._check(self._lib.gmb_predict_grad_terms(self._h, terms_mask(terms), _ptr(Xs), M, self.D, _ptr(grad), self.D, GMB_HOST),
+                        "gmb_predict_grad_terms")
+            return grad
         self._check(self._lib.gmb_predict_grad(self._h, _ptr(Xs), M, self.D, _ptr(grad), self.D, GMB_HOST), "gmb_predict_grad")
         return grad
+
+    def predict_decompose(self, Xs):
+        """Every component of an additive model at the rows of ``Xs`` from one pass (``gmb_predict_decompose``):
+        ``(means, cov, noise)`` -- ``means`` (T, M) the posterior means of the T terms, ``cov`` (T, T, M) the symmetric pointwise
+        posterior covariance of the latent components (``cov[t, u, m] = delta_tu k_t(x*, x*) - <V_t, V_u>``: no noise, no jitter),
+        ``noise`` (M) the model's noise variance at each point.  ``means.sum(0)`` is ``predict``'s mean and ``cov.sum((0, 1))`` its
+        noise-free variance."""
+        Xs = self._joint_points(Xs)
+        M = Xs.shape[0]
+        T = self.num_terms
+        means = np.empty((T, M), dtype=np.float64)
+        packed = np.empty((T * (T + 1) // 2, M), dtype=np.float64)
+        noise = np.empty(M, dtype=np.float64)
+        self._check(self._lib.gmb_predict_decompose(self._h, _ptr(Xs), M, Xs.shape[1], _ptr(means), max(M, 1), _ptr(packed), max(M, 1),
+                                                    _ptr(noise), GMB_HOST), "gmb_predict_decompose")
+        cov = np.empty((T, T, M), dtype=np.float64)
+        for t in range(T):
+            for u in range(t + 1):
+                cov[t, u] = cov[u, t] = packed[t * (t + 1) // 2 + u]
+        return means, cov, noise
 
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with

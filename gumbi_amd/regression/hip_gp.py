@@ -69,6 +69,12 @@ _BLAS_CONTROLLER = None
 _BLAS_LIBS_SEEN = -1
 
 
+class UnknownAdditiveLevel(ValueError, NotImplementedError):
+    """``additive_level`` names a level the model does not have.  A ``ValueError`` -- the argument is wrong, and the message
+    lists the levels there are -- that is also a ``NotImplementedError``: the reference raises that for every level but
+    "total", and a non-additive model still has no other level to offer callers written against it."""
+
+
 def _single_threaded_host_blas(engine):
     """Context for the optimiser's loop when the evaluations run on the GPU: scipy's L-BFGS-B factors its m x m (m <= 10)
     matrices with LAPACK, and a many-threaded OpenBLAS spends 0.1 - 20 ms per iteration waking its pool for them -- more than a
@@ -143,6 +149,8 @@ class HipGP(Regressor):
         self.kronecker = kronecker
         self.model = None
         self.gp_dict = None
+        self.additive_levels = None  # {level: the engine's term selection} (build_model)
+        self.component_cov = self.component_levels = None  # decompose_points: covariance between the components, and its axes
         self.MAP = None
         self.trace = None
         self.engine = None
@@ -336,7 +344,16 @@ class HipGP(Regressor):
             self.engine = Engine(device=self.device)
         self.engine.set_data(X, y)
         self.engine.set_kernel(spec)
-        self.gp_dict = {"total": self.engine}
+        # The levels of an additive model as term selections of the engine (bit 0: the global kernel, bit 1 + j: the kernel of
+        # the j-th categorical dimension other than the output column); every other model has "total" alone.
+        n_terms = 1 + len(coreg) if spec.additive else 1
+        self.additive_levels = {"total": (1 << n_terms) - 1}
+        if spec.additive:
+            self.additive_levels["global"] = 1
+            for j, d in enumerate(d for d in self.categorical_dims if d != self.out_col):
+                self.additive_levels[d] = 1 << (1 + j)
+        self.gp_dict = dict.fromkeys(self.additive_levels, self.engine)
+        self.component_cov = self.component_levels = None
         self.MAP = None
         self._theta_fitted = None
         return self
@@ -525,11 +542,19 @@ class HipGP(Regressor):
     def predict(self, points_array, with_noise=True, additive_level="total", **kwargs):
         """Posterior mean / variance at standardized points (reference :837-849): one call into
         ``gmb_predict`` against the factor left resident by :meth:`find_MAP`."""
-        if additive_level != "total":
-            raise NotImplementedError("Prediction for additive sublevels is not yet supported.")
+        terms = self._level_terms(additive_level)
         if self.MAP is None or self.engine is None:
             raise ValueError("The model must be fit (find_MAP) before predicting")
-        return self.engine.predict(np.asarray(points_array, dtype=np.float64), with_noise=with_noise)
+        return self.engine.predict(np.asarray(points_array, dtype=np.float64), with_noise=with_noise, **terms)
+
+    def _level_terms(self, additive_level):
+        """The engine's term selection for ``additive_level`` as keyword arguments of its prediction calls: none for ``"total"``
+        (the call without a selection, on any engine), ``terms=`` the level's mask otherwise (the reference raises for every
+        level but "total", pymc/GP.py:839-841)."""
+        levels = self.additive_levels if self.additive_levels is not None else {"total": 1}
+        if additive_level not in levels:
+            raise UnknownAdditiveLevel(f"Unknown additive_level {additive_level!r}: this model has the levels {list(levels)}")
+        return {} if additive_level == "total" else {"terms": levels[additive_level]}
 
     # -- slope of the fitted surface --------------------------------------------------------------------------------------------
     def predict_grad(self, points_array, additive_level="total"):
@@ -537,13 +562,12 @@ class HipGP(Regressor):
         dimension in ``dims`` order (categorical columns and the output index: 0) -- the reference's autograd pass
         (botorch/GP.py:535-576) in closed form: one call into ``gmb_predict_grad`` against the factor left resident by
         :meth:`find_MAP`."""
-        if additive_level != "total":
-            raise NotImplementedError("Prediction for additive sublevels is not yet supported.")
+        terms = self._level_terms(additive_level)
         if self.MAP is None or self.engine is None:
             raise ValueError("The model must be fit (find_MAP) before predicting")
-        return self.engine.predict_grad(np.asarray(points_array, dtype=np.float64))
+        return self.engine.predict_grad(np.asarray(points_array, dtype=np.float64), **terms)
 
-    def predict_points_grad(self, points, output=None, norm=True):
+    def predict_points_grad(self, points, output=None, norm=True, additive_level="total"):
         """Slope of the fitted surface at a 1-D parray of points (reference botorch/GP.py:579-622): a parray with one layer
         ``δ[{y}]/δ[{x}]`` per output and continuous dimension, or, with ``norm=True``, one layer ``|∇|{y}`` per output (the
         Euclidean norm over the continuous dimensions).
@@ -553,7 +577,7 @@ class HipGP(Regressor):
         the layer is the slope with respect to (or of) its logarithm."""
         output = self._parse_prediction_output(output)
         points_array, tall, param_coords = self._prepare_points_for_prediction(points, output=output)
-        grad_z = self.predict_grad(points_array)
+        grad_z = self.predict_grad(points_array, additive_level=additive_level)
         task = tall[self.out_col].values().squeeze() if param_coords is not None else None
         partials = {}
         for i, y_var in enumerate(output):
@@ -565,7 +589,7 @@ class HipGP(Regressor):
         grad = self.parray(**partials)
         return self._get_pgrad_norm(grad) if norm else grad
 
-    def predict_grid_grad(self, output=None, categorical_levels=None, norm=True):
+    def predict_grid_grad(self, output=None, categorical_levels=None, norm=True, additive_level="total"):
         """:meth:`predict_points_grad` on the grid :meth:`prepare_grid` left behind, in the grid's shape (reference
         botorch/GP.py:625-633)."""
         if self.grid_points is None:
@@ -573,7 +597,7 @@ class HipGP(Regressor):
         points = self.grid_points
         if self.categorical_dims:
             points = self.append_categorical_points(points, categorical_levels=categorical_levels)
-        return self.predict_points_grad(points, output=output, norm=norm).reshape(self.grid_parray.shape)
+        return self.predict_points_grad(points, output=output, norm=norm, additive_level=additive_level).reshape(self.grid_parray.shape)
 
     @staticmethod
     def _get_pgrad_norm(pgrad):
@@ -874,22 +898,22 @@ class HipGP(Regressor):
 
     # -- joint posterior: covariance and draws ---------------------------------------------------------------------------------
     def _joint_engine(self, additive_level, what):
-        if additive_level != "total":
-            raise NotImplementedError("Prediction for additive sublevels is not yet supported.")
+        """The engine of a joint-posterior call and the term selection of ``additive_level`` (:meth:`_level_terms`)."""
+        terms = self._level_terms(additive_level)
         if self.MAP is None or self.engine is None:
             raise ValueError("The model must be fit (find_MAP) before predicting")
         if self.distributed:
             raise NotImplementedError(f"{what}: the joint posterior is not built for distributed GPs (the factor is spread over ranks)")
         if isinstance(self.engine, icm.IcmEngine):
             raise NotImplementedError(f"{what}: the joint posterior is not built for the Kronecker path (pass kronecker=False)")
-        return self.engine
+        return self.engine, terms
 
     def predict_joint(self, points_array, with_noise=True, additive_level="total"):
         """Posterior mean (M) and full M x M covariance at standardized points, in standardized units
         (``pm.gp.Marginal._build_conditional(..., diag=False)``): one call into ``gmb_predict_joint`` against the factor
         left resident by :meth:`find_MAP`.  No jitter is added; the diagonal is :meth:`predict`'s variance."""
-        engine = self._joint_engine(additive_level, "predict_joint")
-        return engine.predict_joint(np.asarray(points_array, dtype=np.float64), with_noise=with_noise, jitter=0.0)
+        engine, terms = self._joint_engine(additive_level, "predict_joint")
+        return engine.predict_joint(np.asarray(points_array, dtype=np.float64), with_noise=with_noise, jitter=0.0, **terms)
 
     def draw_point_samples(self, points, *args, source=None, output=None, var_name="posterior_samples", additive_level="total",
                            increment_var=True, n_draws=1, with_noise=False, rng=None, z=None, **kwargs):
@@ -918,7 +942,7 @@ class HipGP(Regressor):
         if not (source is None or source is self.MAP or
                 (isinstance(source, (list, tuple)) and len(source) == 1 and source[0] is self.MAP)):
             raise NotImplementedError("draw_point_samples draws from the stored MAP only; `source` must be None or that MAP")
-        engine = self._joint_engine(additive_level, "draw_point_samples")
+        engine, terms = self._joint_engine(additive_level, "draw_point_samples")
 
         M = points_array.shape[0]
         if z is None:
@@ -932,11 +956,47 @@ class HipGP(Regressor):
             if z.shape != (int(n_draws), M):
                 raise ValueError(f"z must have shape (n_draws, M) = ({int(n_draws)}, {M}), got {z.shape}")
         jitter = 0.0 if with_noise else float(self.model.spec.jitter)
-        samples = engine.draw_joint(points_array, z, with_noise=with_noise, jitter=jitter)
+        samples = engine.draw_joint(points_array, z, with_noise=with_noise, jitter=jitter, **terms)
 
         self.predictions = self.parray(**{output[0]: samples}, stdzd=True)
         self.predictions_X = points
         return self.predictions
+
+    # -- the components of an additive model ------------------------------------------------------------------------------------
+    def decompose_points(self, points, output=None):
+        """Every additive level at a 1-D parray of points, from ONE pass of the engine (``gmb_predict_decompose``):
+        ``{level: uparray}`` for ``"total"`` and each level of :attr:`additive_levels`, for one output.  The values are the
+        LATENT components (no noise): level t has mean ``mu_t`` and variance ``cov_tt``; ``"total"`` is their sum,
+        ``sum_t mu_t`` and ``sum_tu cov_tu`` -- :meth:`predict_points` with ``with_noise=False``.  The standardized pointwise
+        covariance BETWEEN the components, ``(T, T, M)``, stays in :attr:`component_cov` with :attr:`component_levels` naming
+        its axes: a strongly negative off-diagonal says the data cannot tell two components apart."""
+        output = self._parse_prediction_output(output)
+        if len(output) > 1:
+            raise NotImplementedError("Decomposing multiple outputs at once is not yet implemented.")
+        points_array, _, _ = self._prepare_points_for_prediction(points, output=output)
+        engine, _ = self._joint_engine("total", "decompose_points")
+        means, cov, _ = engine.predict_decompose(points_array)
+        by_bit = {mask: level for level, mask in self.additive_levels.items() if level != "total" or len(self.additive_levels) == 1}
+        self.component_levels = [by_bit[1 << t] for t in range(means.shape[0])]
+        self.component_cov = cov
+        parts = {"total": self.uparray(output[0], means.sum(axis=0), cov.sum(axis=(0, 1)), stdzd=True)}
+        if len(self.additive_levels) > 1:
+            for t, level in enumerate(self.component_levels):
+                parts[level] = self.uparray(output[0], means[t], cov[t, t], stdzd=True)
+        self.predictions_X = points
+        return parts
+
+    def decompose_grid(self, output=None, categorical_levels=None):
+        """:meth:`decompose_points` on the grid :meth:`prepare_grid` left behind, every level in the grid's shape."""
+        if self.grid_points is None:
+            raise ValueError("Grid must first be specified with `prepare_grid`")
+        points = self.grid_points
+        if self.categorical_dims:
+            points = self.append_categorical_points(points, categorical_levels=categorical_levels)
+        shape = self.grid_parray.shape
+        parts = {level: up.reshape(shape) for level, up in self.decompose_points(points, output=output).items()}
+        self.predictions_X = self.predictions_X.reshape(shape)
+        return parts
 
     def draw_grid_samples(self, *args, source=None, output=None, categorical_levels=None, var_name="posterior_samples",
                           additive_level="total", increment_var=True, n_draws=1, with_noise=False, rng=None, z=None, **kwargs):

@@ -54,6 +54,12 @@ def aligned_outputs(X, spec) -> bool:
     return bool(np.all(blocks[:, :, :-1] == blocks[0:1, :, :-1]))
 
 
+def _no_terms(terms, what):
+    if terms is not None:
+        raise NotImplementedError(f"{what}: the components of an additive model are not built for the Kronecker engine "
+                                  "(it is never chosen for additive specs)")
+
+
 class IcmEngine:
     """Same calls as :class:`gumbi_amd.engine.Engine` (``set_data / set_kernel / set_theta / factorize /
     nlml / predict / close``) for an aligned multi-output table; ``theta`` keeps the stacked model's layout."""
@@ -255,7 +261,11 @@ class IcmEngine:
             grad_out[k + 5 * P: k + 6 * P] = gbn
         return val, grad_out
 
-    def predict(self, Xs, with_noise=True):
+    def predict_decompose(self, Xs):
+        _no_terms(0, "predict_decompose")
+
+    def predict(self, Xs, with_noise=True, terms=None):
+        _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)
         if Xs.ndim != 2 or Xs.shape[1] != self.spec.D:
             raise ValueError(f"points_array must be (M, {self.spec.D}), got {Xs.shape}")
@@ -277,10 +287,11 @@ class IcmEngine:
             var += st["sigma"] ** 2 * st["bn"][task]
         return mean, var
 
-    def predict_grad(self, Xs):
+    def predict_grad(self, Xs, terms=None):
         """Gradient of the posterior mean at the rows of ``Xs``, ``(M, D)``: the Kronecker mean is a fixed linear combination
         of the P systems' means (:meth:`predict`), so its gradient is the same combination of their gradients; the output
         column gets 0."""
+        _no_terms(terms, "predict_grad(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)
         if Xs.ndim != 2 or Xs.shape[1] != self.spec.D:
             raise ValueError(f"points_array must be (M, {self.spec.D}), got {Xs.shape}")

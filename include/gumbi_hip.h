@@ -344,6 +344,63 @@ int gmb_predict_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, d
 int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
                           double* dmean, double* dvar, int64_t ldg, int32_t memspace);
 
+/* ---- The components of an additive model (csrc/predict_terms.hpp, csrc/term_walk.hpp).  Additive to ABI 16: new functions only.
+ * The reference carries `additive_level=` in its signatures and raises NotImplementedError for every level but "total"
+ * (gumbi/regression/pymc/GP.py:839-841); these calls go beyond that line.
+ *
+ * The model's covariance is a sum of T terms, K = sum_t K_t: term 0 the global kernel, term 1 + j the kernel of coregion dimension
+ * j of an additive spec (T = 1 otherwise).  Bit t of a `terms` mask selects term t.  Let S be a selection, K_S = sum_{t in S} K_t,
+ * and L, v = L^-1 y, alpha = Sigma^-1 y the resident state of the WHOLE model.  Then
+ *   mu_S(x*)   = K_S(x*, X) alpha,          V_S = K_S(X*, X) L^-T = sum_{t in S} V_t
+ *   cov_S(X*)  = K_S(X*, X*) - V_S V_S^T
+ *   cov(f_t, f_u | y)(x*) = -<V_t(x*), V_u(x*)>   for t != u (the priors of different terms are independent).
+ * Noise and jitter belong to no term: with_noise adds the model's noise diagonal to a selection's variance, exactly as to the
+ * total's (what pm.gp.Marginal.predict(..., given=..., pred_noise=True) would do).
+ *
+ * terms == 0 or a bit at or beyond T returns GMB_EINVAL and launches nothing.  With all T bits set a *_terms call issues the
+ * launches of the call it is named after, in the same order: the same bits.  The selection changes only K(X*, X) and K(X*, X*);
+ * behind a gradient evaluation gmb_predict_terms and the joint pair take the product form exactly as their parents do.
+ * State contract of all six calls: the factor, v, both alphas, U and the inverse factor with their flags, the joint state and
+ * gmb_factor_valid are left as found; the same bits call after call. */
+
+/* T: 1, or 1 + n_coreg for additive specs; a negative status before gmb_set_theta. */
+int gmb_num_terms(const gmb_engine* e);
+
+/* gmb_predict for the selection: mean = mu_S, var = diag cov_S (+ noise).  Readiness, tiling and forms as gmb_predict, except that
+ * distributed and capacity-mode engines are refused (GMB_EINVAL); M == 0 is GMB_OK.  Beyond pymc/GP.py:839-841. */
+int gmb_predict_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                      double* mean, double* var, int32_t memspace);
+
+/* gmb_predict_grad for the selection: d mu_S / d x* = sum_{t in S} d K_t(x*, X) / d x* alpha, alpha the whole model's.  Readiness,
+ * refusals and layout as gmb_predict_grad.  Beyond pymc/GP.py:839-841. */
+int gmb_predict_grad_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs,
+                           double* grad, int64_t ldg, int32_t memspace);
+
+/* gmb_predict_joint for the selection: mean = mu_S and C = K_S(X*, X*) - V_S V_S^T (+ the model's noise diagonal if with_noise)
+ * + jitter * I.  Arguments, readiness, refusals and memory rule as gmb_predict_joint.  Beyond pymc/GP.py:839-841. */
+int gmb_predict_joint_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
+                            double jitter, double* mean, double* cov, int64_t ldc, int32_t memspace);
+
+/* gmb_draw_joint for the selection: Y[s, :] = mu_S + L* Z[s, :] with L* the factor of the C above.  Draws of different selections
+ * are draws of their own marginals: they do not add up to one draw of the total.  Beyond pymc/GP.py:839-841. */
+int gmb_draw_joint_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
+                         const double* Z, int64_t S, int64_t ldz, double* Y, int64_t ldy, double* mean, int32_t memspace);
+
+/* ALL components at M points from one pass: the T blocks V_t are stacked ((T * M padded) x (N padded) doubles, M tiled so that
+ * this stays within gmb_predict's 8 GiB rule), solved by ONE triangular solve (always the solve: neither the inverse factor nor U
+ * is touched) and reduced without atomics.
+ *   means: T rows of M (leading dimension ldm >= M), row t = mu_t = <V_t, v>
+ *   cov:   T (T + 1) / 2 rows of M (ldcv >= M), the packed lower triangle of the pointwise T x T posterior covariance of the LATENT
+ *          components, row p = t (t + 1) / 2 + u (u <= t):  delta_tu k_t(x*, x*) - <V_t, V_u>  -- no noise, no jitter
+ *   noise: M, may be NULL: the model's noise variance at each point (what with_noise adds)
+ * The sum of the means is gmb_predict's mean, the sum over the full T x T matrix its noise-free variance, the sum over a
+ * selection's rows and columns gmb_predict_terms' -- to rounding.  Nothing beyond column M of a row is written.  Readiness and
+ * refusals as gmb_predict_joint (a complete, unconsumed single-engine factor; GMB_EINVAL for distributed and capacity engines);
+ * a workspace the device cannot hold returns GMB_ENOMEM before anything is launched; M == 0 is GMB_OK.
+ * Beyond pymc/GP.py:839-841. */
+int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* means, int64_t ldm, double* cov,
+                          int64_t ldcv, double* noise, int32_t memspace);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
