@@ -122,17 +122,9 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   }
   e->coll_count = e->coll_hash = 0;
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_factorize (set-up)"))) return rc;
-  e->factored = false;
-  e->factor_kind = gmb_engine::FK_CAPACITY;
-  e->factor_consumed = false;
-  e->have_alpha = false;
-  e->bs_valid = false;
-  e->notpd = -1;
+  begin_factorisation(e, FactorState::CAPACITY);
   e->own_world = G;
   e->own_rank = rank;
-  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
-  tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
-  tm.chol_gemm_launches = 0;
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   hipStream_t mainS = e->stream, bulkS = e->aux[2], commS = e->aux[0];
   e->sync_next = 0;
@@ -311,18 +303,7 @@ int cap_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
     }
     tm.dist_chol_comm_exposed_ms += dist_exposed_from_probes(probe, chain_comm, &tm.dist_chol_main_wait_ms, &tm.dist_chol_bulk_wait_ms);
   }
-  if (info != 0) {
-    e->notpd = (int64_t)info - 1;
-    return fail(e, GMB_ENOTPD, "covariance matrix is not positive definite at row %lld", (long long)e->notpd);
-  }
-  e->logdet = hs[0];
-  e->vnorm2 = hs[1];
-  if (!std::isfinite(e->logdet) || !std::isfinite(e->vnorm2)) {
-    e->notpd = 0;
-    return fail(e, GMB_ENOTPD, "factorisation produced non-finite values");
-  }
-  e->factored = true;
-  return GMB_OK;
+  return accept_factor(e, info, hs[0], hs[1]);
 }
 
 // padding columns [n, npad) of this rank's block rows of U = L^-T: identity (they picked up the y row's products)
@@ -531,7 +512,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   for (const DistProbe::Wait& w : probe.waits)
     if (w.kind == 2) waited += dist_ms(w.arrive, w.release);
   tm.dist_grad_comm_exposed_ms += std::min(waited, on_comm_stream);
-  e->have_alpha = true;
+  e->fs.alpha_gathered();
   h.assign(GACC_DOUBLES, 0.0);
   for (int q = 0; q < G; ++q)
     for (int i = 0; i < GACC_DOUBLES; ++i) h[i] += all[(size_t)q * GACC_DOUBLES + i];

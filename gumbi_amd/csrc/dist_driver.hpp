@@ -356,15 +356,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   }
   e->coll_count = e->coll_hash = 0;  // the issue log covers this call: its closing agreement compares the ranks' sequences
   if ((rc = dist_agree(e, comm, rc, "gmb_dist_factorize (set-up)"))) return rc;
-  e->factored = false;
-  e->factor_kind = gmb_engine::FK_REPLICATED;
-  e->factor_consumed = false;
-  e->have_alpha = false;
-  e->bs_valid = false;
-  e->notpd = -1;
-  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
-  tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
-  tm.chol_gemm_launches = 0;
+  begin_factorisation(e, FactorState::REPLICATED);
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   hipStream_t mainS = e->stream, bulkS = e->aux[2], commS = e->aux[0];
   e->sync_next = 0;
@@ -530,18 +522,7 @@ int dist_factorize(gmb_engine* e, const gmb_comm* comm, int panel_blocks) {
   }
   // every rank factored every diagonal square itself: log-det and the failure index are already global and
   // identical on all ranks (same kernels on the same bits) -- no reduction
-  if (info != 0) {
-    e->notpd = (int64_t)info - 1;
-    return fail(e, GMB_ENOTPD, "covariance matrix is not positive definite at row %lld", (long long)e->notpd);
-  }
-  e->logdet = hs[0];
-  e->vnorm2 = hs[1];
-  if (!std::isfinite(e->logdet) || !std::isfinite(e->vnorm2)) {
-    e->notpd = 0;
-    return fail(e, GMB_ENOTPD, "factorisation produced non-finite values");
-  }
-  e->factored = true;
-  return GMB_OK;
+  return accept_factor(e, info, hs[0], hs[1]);
 }
 
 // ---- gradient ----------------------------------------------------------------------------------------
@@ -561,7 +542,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   rc = require_ready(e, true);
   if (!rc) rc = require_full_factor(e, "gmb_dist_nlml (replicated mode)");
   if (!rc && !nlml) rc = fail(e, GMB_EINVAL, "nlml output pointer is null");
-  if (!rc && e->factor_consumed) rc = fail(e, GMB_EINVAL, "the factor was already consumed by a gradient call; refactorize");
+  if (!rc && e->fs.consumed()) rc = fail(e, GMB_EINVAL, "the factor was already consumed by a gradient call; refactorize");
   if (!rc && hipSetDevice(e->device) != hipSuccess) rc = fail(e, GMB_EHIP, "hipSetDevice(%d) failed", e->device);
   const int nt = (int)(e->Np / TILE);
   int first = 0, owned = 0;
@@ -586,7 +567,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   PhaseTimer tg(e);
   e->sync_next = 0;
   e->time_next = 0;
-  e->factor_consumed = true;  // the upper triangle (and the diagonal squares) of the factor buffer become U
+  e->fs.consume();  // the upper triangle (and the diagonal squares) of the factor buffer become U
   DistDeferred bad;
   DistProbe probe;
   auto hip_ok = [&](hipError_t st, const char* what) {
@@ -684,7 +665,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
     for (const DistProbe::Wait& w : probe.waits)
       if (w.kind == 2) tm.dist_grad_comm_exposed_ms += std::min(dist_ms(w.arrive, w.release), on_comm_stream);
   }
-  e->have_alpha = true;
+  e->fs.alpha_gathered();
   h.assign(GACC_DOUBLES, 0.0);
   for (int q = 0; q < G; ++q)
     for (int i = 0; i < GACC_DOUBLES; ++i) h[i] += all[(size_t)q * GACC_DOUBLES + i];

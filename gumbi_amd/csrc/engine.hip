@@ -32,6 +32,7 @@
 #include "../../include/gumbi_hip.h"
 #include "device_buffers.hpp"
 #include "term_walk.hpp"
+#include "factor_state.hpp"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_splitk.hpp"
@@ -169,13 +170,7 @@ struct gmb_engine {
   DevBuf<double> dscal;     // the scalar block (SCAL_DOUBLES, uncounted): [0] logdet, [1] |v|^2, [2..] partials of that sum
   int32_t* dinfo = nullptr; // = dscal + SCAL_INFO_AT (and dgpart = dscal + SCAL_GACC_AT)
   DevBuf<double> dv;
-  bool factored = false;
-  // which path produced the resident factorisation (meaningful while `factored`): the single-engine and the replicated
-  // multi-GPU paths leave the COMPLETE factor in dA; the capacity driver leaves this rank's rows in dAown and nothing in dA
-  enum { FK_NONE = 0, FK_SINGLE = 1, FK_REPLICATED = 2, FK_CAPACITY = 3 };
-  int factor_kind = FK_NONE;
-  bool factor_consumed = false;  // U = L^-T sits in the factor buffer's diagonal tiles (multi-GPU gradient; or a failed one)
-  bool have_alpha = false;       // dalpha holds Sigma^-1 y of the current factorisation
+  FactorState fs;                // what of the last factorisation is resident and valid (factor_state.hpp)
   DevBuf<double> dDiagSave;      // the factor's diagonal blocks while the gradient keeps U in their place
   DevBuf<double> dsk;            // partials of the split-k product (gemm_splitk.hpp): [tile][slice][128 * 128]
   int64_t notpd = -1;
@@ -197,10 +192,8 @@ struct gmb_engine {
       });
     }
   } pw;
-  // GEMM-form prediction (predict_form.hpp): behind a gradient on the tile path U = L^-T of the resident factor sits in the
-  // factor buffer's upper triangle + dUdiag (`u_valid`); the first prediction transposes it into dW's lower triangle
-  // (`linv_valid`; Sigma^-1 is dead by then) and every prediction until the next factorisation is one GEMM into dV2
-  bool u_valid = false, linv_valid = false;
+  // GEMM-form prediction (predict_form.hpp): U = L^-T behind a tile-path gradient sits in the factor buffer's upper triangle +
+  // dUdiag; the first prediction transposes it into dW's lower triangle, every one until the next factorisation is one GEMM into dV2
   int predict_form = -1;   // -1 = GEMM form whenever U is there; 0 = always the triangular solve; 1 = as -1 (explicit)
   struct GemmFormWorkspace : RowGroup {
     DevBuf<double> dV2;    // Np x Mt: the solved cross-covariance with the TRAINING index fastest
@@ -211,8 +204,7 @@ struct gmb_engine {
   JointState jt;           // the second matrix of gmb_predict_joint / gmb_draw_joint (joint_predict.hpp)
   DevBuf<double> dpart;    // the prediction's chunked partial sums (2 x chunks x pw.rows)
   // gmb_predict_grad (predict_grad.hpp): workspaces of its own -- a prediction's (Mt x Np and friends) stay as they are --
-  // and alpha by back substitution for the states in which no gradient evaluation left one (`have_alpha` false); `bs_valid`
-  // falls wherever the factorisation does
+  // and alpha by back substitution for the states in which no gradient evaluation left one
   struct PredictGradWorkspace : RowGroup {
     DevBuf<double> Xs, xs, xl;
     DevBuf<int32_t> cat;
@@ -229,7 +221,6 @@ struct gmb_engine {
   } pg;
   DevBuf<double> pg_part;
   DevBuf<double> dalpha_bs;  // Np: alpha, then Np: the running right-hand side
-  bool bs_valid = false;
   // gmb_predict_with_grad: the variance gradient of an M-tile (its partials are a second set in pg_part)
   DevBuf<double> vg_grad;
   // gmb_predict_decompose (predict_terms.hpp), beside a prediction's workspace of T stacked blocks: the chunked partials of an
@@ -1374,7 +1365,7 @@ int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
   const int64_t words = eval_tiles_words(nct, nrt);
   if ((rc = e->dct.reserve(e->pool, words + 2))) return rc;
   if ((rc = e->dW.reserve(e->pool, e->Np * e->Np))) return rc;
-  e->u_valid = e->linv_valid = false;  // (U is rewritten, Sigma^-1 takes dW: set again once the launch is known to have succeeded)
+  e->fs.inverse_rewrites_u();  // (Sigma^-1 takes dW; U is marked again once the launch is known to have succeeded)
   if ((rc = e->dUdiag.reserve(e->pool, (int64_t)nct * TILE * TILE))) return rc;
   if ((rc = e->dApart.reserve(e->pool, (int64_t)nct * nct * TILE + nct))) return rc;  // (+ the partials of |v|^2)
   if ((rc = grad_workspace(e))) return rc;
@@ -2070,7 +2061,7 @@ bool grad_by_tiles(const gmb_engine* e) {
 // into dW, reductions.  The factor is consumed.
 int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   HIP_TRY(e, hipSetDevice(e->device));
-  if (e->factor_consumed)
+  if (e->fs.consumed())
     return fail(e, GMB_EINVAL, "the factor was already consumed by a gradient call; refactorize");
   int rc;
   gmb_timings& tm = e->tm;
@@ -2108,17 +2099,15 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
     if (light) {
       for (size_t t = 0; t < e->terms.size(); ++t)
         std::copy(e->hl->gacc + t * GACC_REGION, e->hl->gacc + (t + 1) * GACC_REGION, h.begin() + t * GACC_REGION);
-      e->have_alpha = true;
-      e->u_valid = true;  // (gmb_evaluate takes both back if factorize_finish reports a failure)
+      e->fs.gradient_left_u_and_alpha();  // (gmb_evaluate takes both back if factorize_finish reports a failure)
       return GMB_OK;  // (abort word, failure index: factorize_finish, which gmb_evaluate calls next)
     }
     if (ab != 0) return fail(e, GMB_EHIP, "tile inverse: a workgroup waited longer than its time-out for a tile (launch abandoned)");
-    e->have_alpha = true;
-    e->u_valid = true;
+    e->fs.gradient_left_u_and_alpha();
     return GMB_OK;
   }
   if ((rc = e->dDiagSave.reserve(e->pool, (int64_t)nt * TILE * TILE))) return rc;
-  e->u_valid = e->linv_valid = false;
+  e->fs.inverse_rewrites_u();
   PhaseTimer tg(e);
   // the diagonal blocks of L are put back at the end: U takes their place in between
   hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 1);
@@ -2139,7 +2128,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
     HIP_TRY(e, hipGetLastError());
   }
   // 1. W = L^-1 (dW, lower) and U = L^-T (factor buffer, upper); the factor is consumed from here on
-  e->factor_consumed = true;
+  e->fs.consume();
   if (!e->fact_in_flight) e->sync_next = 0;  // (gmb_evaluate: the factorisation's cross-stream waits may still be pending on pooled events)
   if (e->par_inverse) {
     if ((rc = winv_levels(e, nt))) return rc;
@@ -2167,8 +2156,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   tm.grad_ms = tg.ms();
   ev_collect(e);
-  e->factor_consumed = false;  // lower triangle = L again (the upper triangle keeps U: scratch as far as L goes)
-  e->have_alpha = true;
+  e->fs.restore();  // lower triangle = L again (the upper triangle keeps U: scratch as far as L goes)
   return GMB_OK;
 }
 
@@ -2264,7 +2252,7 @@ int require_ready(gmb_engine* e, bool need_factor) {
   if (e->N <= 0) return fail(e, GMB_EINVAL, "gmb_set_data has not been called");
   if (!e->have_spec) return fail(e, GMB_EINVAL, "gmb_set_kernel has not been called");
   if (!e->have_theta) return fail(e, GMB_EINVAL, "gmb_set_theta has not been called");
-  if (need_factor && !e->factored)
+  if (need_factor && !e->fs.valid())
     return fail(e, GMB_EINVAL, "no valid factorisation: call gmb_factorize first");
   return GMB_OK;
 }
@@ -2273,16 +2261,16 @@ int require_ready(gmb_engine* e, bool need_factor) {
 // multi-GPU passes) against a factorisation of the capacity driver, which leaves none there -- and the reverse: the capacity
 // passes against anything else than a capacity factorisation (their dAown would be an older theta's).
 int require_full_factor(gmb_engine* e, const char* what) {
-  if (e->factor_kind == gmb_engine::FK_CAPACITY || !e->dA || e->dA.cap <= 0)
+  if (e->fs.capacity() || !e->dA || e->dA.cap <= 0)
     return fail(e, GMB_EINVAL, "%s needs the complete factor on this device, but the resident factorisation is a capacity-mode one "
                                "(gmb_dist_set_mode(e, 1): no rank holds the factor) -- use the gmb_dist_* calls, or gmb_factorize first", what);
   return GMB_OK;
 }
 
 int require_capacity_factor(gmb_engine* e, const char* what) {
-  if (e->factor_kind != gmb_engine::FK_CAPACITY || !e->dAown)
+  if (!e->fs.capacity() || !e->dAown)
     return fail(e, GMB_EINVAL, "%s in capacity mode needs a factorisation made by gmb_dist_factorize in capacity mode; the resident "
-                               "one was made by %s", what, e->factor_kind == gmb_engine::FK_SINGLE ? "gmb_factorize / gmb_evaluate" : "the replicated multi-GPU driver");
+                               "one was made by %s", what, e->fs.single() ? "gmb_factorize / gmb_evaluate" : "the replicated multi-GPU driver");
   return GMB_OK;
 }
 
@@ -2503,16 +2491,13 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   }
   HIP_TRY(e, hipSetDevice(e->device));
   // not ready until every allocation below has succeeded; workspaces sized for the previous N / D are dropped
-  e->factored = false;
-  e->bs_valid = false;
-  e->factor_kind = gmb_engine::FK_NONE;  // (no factorisation of THIS data has been attempted: gmb_debug_assume_factored must refuse)
+  e->fs.feature_map_changed();  // (no factorisation of THIS data has been attempted: gmb_debug_assume_factored must refuse)
   e->have_theta = false;
   e->N = 0;
   stale_sized_by_n(e);
   // (here only: new data gets prepared points of exactly its own size.  resize_n keeps a block that is large enough -- after
   // a truncation it is larger than Nr asks for, and renewing it there would move gmb_resident_bytes.)
   e->pts.stale();
-  e->u_valid = e->linv_valid = false;
   e->D = D;
   e->Np = round_up(N, TILE);
   e->Nr = round_up(N + 1, TILE);
@@ -2544,9 +2529,7 @@ int gmb_set_y(gmb_engine* e, const double* y, int32_t memspace) {
   if (!y) return fail(e, GMB_EINVAL, "y is null");
   HIP_TRY(e, hipSetDevice(e->device));
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  e->factored = false;  // the y row of the factor (v = L^-1 y) belongs to the old observations
-  e->bs_valid = false;
-  e->factor_kind = gmb_engine::FK_NONE;
+  e->fs.inputs_changed();  // the y row of the factor (v = L^-1 y) belongs to the old observations
   HIP_TRY(e, hipMemcpyAsync(e->dy, y, e->N * sizeof(double), kind, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller may reuse its buffer
   return GMB_OK;
@@ -2559,9 +2542,7 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->spec = *spec;
   e->have_spec = true;
   e->have_theta = false;
-  e->factored = false;
-  e->bs_valid = false;
-  e->factor_kind = gmb_engine::FK_NONE;
+  e->fs.inputs_changed();
   e->nc_pad = pick_nc(spec->n_cont);
   e->periodic = 0;
   e->pts.stale();
@@ -2589,10 +2570,7 @@ int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t
   e->nc_pad = pick_nc(mode != 0 ? 2 * s.n_cont : s.n_cont);
   // the prepared coordinates and everything factored from them belong to the previous feature map
   e->have_theta = false;
-  e->factored = false;
-  e->bs_valid = false;
-  e->factor_kind = gmb_engine::FK_NONE;
-  e->u_valid = e->linv_valid = false;
+  e->fs.feature_map_changed();
   return GMB_OK;
 }
 
@@ -2606,9 +2584,7 @@ int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) {
     if (!std::isfinite(theta[i])) return fail(e, GMB_EINVAL, "theta[%d] is not finite", i);
   HIP_TRY(e, hipSetDevice(e->device));
   e->theta.assign(theta, theta + n);
-  e->factored = false;
-  e->bs_valid = false;
-  e->factor_kind = gmb_engine::FK_NONE;
+  e->fs.inputs_changed();
   int rc = apply_theta(e);
   if (rc) return rc;
   if ((rc = e->pts.reserve(e->pool, e->Nr))) return rc;
@@ -2662,9 +2638,53 @@ int gmb_timings_get(const gmb_engine* e, gmb_timings* out) {
 
 int64_t gmb_notpd_index(const gmb_engine* e) { return e ? e->notpd : -1; }
 
-int gmb_factor_valid(const gmb_engine* e) { return (e && e->N > 0 && e->have_theta && e->factored && !e->factor_consumed) ? 1 : 0; }
+int gmb_factor_valid(const gmb_engine* e) { return (e && e->N > 0 && e->have_theta && e->fs.usable()) ? 1 : 0; }
 
 namespace {
+
+// What every factorisation does first -- gmb_factorize / gmb_evaluate, the two multi-GPU drivers and (`tail`) the bordered update
+// behind gmb_append / gmb_truncate: nothing of the previous one stays valid, no failure index, the phase timings start from zero.
+void begin_factorisation(gmb_engine* e, FactorState::Kind kind, bool tail = false) {
+  tail ? e->fs.begin_tail() : e->fs.begin(kind);
+  e->notpd = -1;
+  gmb_timings& tm = e->tm;
+  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
+  tm.chol_gemm_launches = 0;
+}
+
+// ... and what every one of them does last, with the failure index, log-det and |v|^2 its host has read
+int accept_factor(gmb_engine* e, int32_t info, double logdet, double vnorm2) {
+  if (info != 0) {
+    e->notpd = (int64_t)info - 1;
+    return fail(e, GMB_ENOTPD, "covariance matrix is not positive definite at row %lld", (long long)e->notpd);
+  }
+  e->logdet = logdet;
+  e->vnorm2 = vnorm2;
+  if (!std::isfinite(e->logdet) || !std::isfinite(e->vnorm2)) {
+    e->notpd = 0;
+    return fail(e, GMB_ENOTPD, "factorisation produced non-finite values");
+  }
+  e->fs.accepted();
+  return GMB_OK;
+}
+
+// the events around the covariance build and the Cholesky (kbuild_ms, chol_ms)
+int ensure_phase_events(gmb_engine* e) {
+  for (auto& ev : e->fe)
+    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  return GMB_OK;
+}
+
+// the pinned block the factorisation's scalars land in, with no failure and no abandoned launch on record
+int ensure_host_landing(gmb_engine* e) {
+  if (!e->hl) {
+    HIP_TRY(e, hipHostMalloc((void**)&e->hl, sizeof(gmb_engine::HostLanding), hipHostMallocDefault));
+    HIP_TRY(e, hipHostGetDevicePointer((void**)&e->hl_dev, e->hl, 0));
+  }
+  e->hl->info = 0;
+  e->hl->abort = 0;
+  return GMB_OK;
+}
 
 // Everything of gmb_factorize up to (not including) the host's look at the results: K-build, Cholesky, v = L^-1 y, and the
 // asynchronous copies of log-det / |v|^2 / failure index / abort word into the engine.  Nothing is synchronised.
@@ -2672,20 +2692,9 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   int rc = require_ready(e, false);
   if (rc) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
-  e->factored = false;
-  e->factor_kind = gmb_engine::FK_SINGLE;
-  e->factor_consumed = false;
-  e->have_alpha = false;
-  e->bs_valid = false;
-  e->u_valid = e->linv_valid = false;
-  e->notpd = -1;
+  begin_factorisation(e, FactorState::SINGLE);
   if ((rc = ensure_factor_buffer(e))) return rc;
-  gmb_timings& tm = e->tm;
-  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
-  tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
-  tm.chol_gemm_launches = 0;
-  for (auto& ev : e->fe)
-    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  if ((rc = ensure_phase_events(e))) return rc;
   if (e->panel_auto) {
     // wider panels for larger matrices: a k = 1024 trailing update pays its C read-modify-write and
     // epilogue per 1024 of contraction; measured at N = 60k: 8 blocks 58.0, 16: 62.2, 32: 63.9 TF/s
@@ -2733,12 +2742,7 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   }
   if (events) HIP_TRY(e, hipEventRecord(e->fe[3], e->stream));
   HIP_TRY(e, hipGetLastError());
-  if (!e->hl) {
-    HIP_TRY(e, hipHostMalloc((void**)&e->hl, sizeof(gmb_engine::HostLanding), hipHostMallocDefault));
-    HIP_TRY(e, hipHostGetDevicePointer((void**)&e->hl_dev, e->hl, 0));
-  }
-  e->hl->info = 0;
-  e->hl->abort = 0;
+  if ((rc = ensure_host_landing(e))) return rc;
   if (!e->light) {
     HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2748,10 +2752,10 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   return GMB_OK;
 }
 
-// The host's look at an enqueued factorisation: synchronise, timings, failure checks; sets e->factored.
+// The host's look at an enqueued factorisation: synchronise, timings, failure checks; accepts the factor or not.
 int factorize_finish(gmb_engine* e) {
   gmb_timings& tm = e->tm;
-  e->factored = false;
+  e->fs.not_accepted();
   e->fact_in_flight = false;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (!e->hl) return fail(e, GMB_EINVAL, "internal: no factorisation enqueued");
@@ -2770,19 +2774,7 @@ int factorize_finish(gmb_engine* e) {
     tm.total_kbuild_bytes += tm.kbuild_bytes;
     tm.total_kbuild_launches += 1;
   }
-  if (e->hl->info != 0) {
-    e->notpd = (int64_t)e->hl->info - 1;
-    return fail(e, GMB_ENOTPD, "covariance matrix is not positive definite at row %lld",
-                (long long)e->notpd);
-  }
-  e->logdet = e->hl->scal[0];
-  e->vnorm2 = e->hl->scal[1];
-  if (!std::isfinite(e->logdet) || !std::isfinite(e->vnorm2)) {
-    e->notpd = 0;
-    return fail(e, GMB_ENOTPD, "factorisation produced non-finite values");
-  }
-  e->factored = true;
-  return GMB_OK;
+  return accept_factor(e, e->hl->info, e->hl->scal[0], e->hl->scal[1]);
 }
 
 }  // namespace
@@ -2831,23 +2823,20 @@ int gmb_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlml, do
   if (grad) {
     // the gradient's launches follow the factorisation's on the same stream with no host round trip in between; if the
     // factorisation turns out to have failed they ran on garbage and their result is dropped below
-    e->factored = true;
+    e->fs.accepted();
     const bool light = e->light;
     rc_grad = grad_accumulate(e, h);
     e->light = false;
     if (rc_grad && light) {  // nothing has landed on the host: there is no factorisation to look at
       (void)hipStreamSynchronize(e->stream);
-      e->factored = false;
+      e->fs.not_accepted();
       e->fact_in_flight = false;
       e->et_fused = false;
       return rc_grad;
     }
   }
   if ((rc = factorize_finish(e))) {
-    // the gradient ran on garbage: nothing of it may outlive this call (gmb_copy_alpha checks have_alpha only)
-    e->have_alpha = false;
-    e->u_valid = e->linv_valid = false;
-    e->factor_consumed = false;
+    e->fs.gradient_ran_on_garbage();
     e->et_fused = false;
     if (factorize_retry_after_abort(e, rc) != GMB_OK) return rc;
     rc_grad = grad ? grad_accumulate(e, h) : GMB_OK;  // (an abandoned tile launch: the recursion's factor, the gradient again)
@@ -2894,16 +2883,16 @@ int launch_gemm_splitk(gmb_engine* e, hipStream_t s, SplitKArgs a, int pin, int3
 
 // a complete, unconsumed single-engine factor of the current (data, kernel, theta) sits in dA
 bool has_live_factor(const gmb_engine* e) {
-  return e->factored && e->factor_kind == gmb_engine::FK_SINGLE && !e->factor_consumed && e->dA && e->dA.cap > 0;
+  return e->fs.live_single() && e->dA && e->dA.cap > 0;
 }
 
 // what gmb_append and gmb_truncate refuse alike
 int resize_ready(gmb_engine* e, const char* what) {
   int rc = require_ready(e, false);
   if (rc) return rc;
-  if (e->solve_hook || e->dist_mode != 0 || e->factor_kind == gmb_engine::FK_REPLICATED || e->factor_kind == gmb_engine::FK_CAPACITY)
+  if (e->solve_hook || e->dist_mode != 0 || e->fs.distributed())
     return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode)", what);
-  if (e->factored && e->factor_consumed)
+  if (e->fs.valid_but_consumed())
     return fail(e, GMB_EINVAL, "%s: the factor was consumed by a gradient call: call gmb_factorize again", what);
   return GMB_OK;
 }
@@ -2916,22 +2905,14 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
   const AppendRegions reg = append_regions(lay);
   const int I0 = (int)lay.I0, nct = (int)reg.nct, nrt = (int)reg.nrt;
   hipStream_t s = e->stream;
-  e->factored = false;
-  e->factor_kind = gmb_engine::FK_SINGLE;
-  e->factor_consumed = false;
-  e->notpd = -1;
+  begin_factorisation(e, FactorState::SINGLE, true);
   e->chol = CholResult{};
   e->et_fused = false;
   e->light = false;
   // phase events as behind gmb_factorize: kbuild_ms = the rebuilt rows of Sigma, chol_ms = panel solve + corner update + corner
   // factorisation + v (tools/gpu_append.py)
-  for (auto& ev : e->fe)
-    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  if ((rc = ensure_phase_events(e))) return rc;
   e->fe_recorded = true;
-  gmb_timings& tm = e->tm;
-  tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = 0.0;
-  tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
-  tm.chol_gemm_launches = 0;
   HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), s));
   const FactorRef f = train_factor(e);
   HIP_TRY(e, hipEventRecord(e->fe[0], s));
@@ -2988,12 +2969,7 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
   hipLaunchKernelGGL(extract_v_kernel, dim3(EXTRACT_V_BLOCKS), dim3(TILE), 0, s, e->dA, e->ld, e->N, e->dv, e->dscal + 1);
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipEventRecord(e->fe[3], s));
-  if (!e->hl) {
-    HIP_TRY(e, hipHostMalloc((void**)&e->hl, sizeof(gmb_engine::HostLanding), hipHostMallocDefault));
-    HIP_TRY(e, hipHostGetDevicePointer((void**)&e->hl_dev, e->hl, 0));
-  }
-  e->hl->info = 0;
-  e->hl->abort = 0;
+  if ((rc = ensure_host_landing(e))) return rc;
   HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   e->fact_in_flight = true;
@@ -3025,14 +3001,9 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
                                  "copy, %.0f are free -- nothing was changed", what, (long long)N_new, (long long)ld_old, (long long)ld_new, need, (double)free_b);
     if ((rc = newA.reserve(e->pool, ld_new * Np_new))) return rc;
   }
-  e->factored = false;
-  e->have_alpha = false;
-  e->bs_valid = false;
-  e->u_valid = e->linv_valid = false;
-  if (!live) e->factor_kind = gmb_engine::FK_NONE;
+  e->fs.resized(live);
   auto bail = [&](int code) {  // a failure half-way: no factor; the data may be of either size, so nothing is ready
-    e->factored = false;
-    e->factor_kind = gmb_engine::FK_NONE;
+    e->fs.resize_failed();
     e->have_theta = false;
     return code;
   };
@@ -3114,8 +3085,7 @@ int predict_workspace(gmb_engine* e, int64_t Mt) {
 // Which form V = K(X*, X) L^-T takes (gmb_set_predict_form): the product with the resident inverse factor needs what the tile
 // path's gradient leaves behind; everything else is the triangular solve.
 bool predict_takes_gemm_form(const gmb_engine* e) {
-  return !e->solve_hook && e->predict_form != 0 && e->u_valid && e->have_alpha && e->factor_kind == gmb_engine::FK_SINGLE &&
-         e->dW && e->dUdiag && e->dW.cap >= e->Np * e->Np;
+  return !e->solve_hook && e->predict_form != 0 && e->fs.gemm_form_ready() && e->dW && e->dUdiag && e->dW.cap >= e->Np * e->Np;
 }
 
 // ... and the second Mt x Np buffer that form needs
@@ -3181,7 +3151,7 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
   } else if (use_gemm_form) {
     // U = L^-T of this factor is resident (the fit's last evaluation left it): V^T = L^-1 K(X, X*) as ONE product with a
     // triangular operand (predict_form.hpp) instead of a solve
-    if (!e->linv_valid) {
+    if (e->fs.linv_missing()) {
       LinvArgs la{};
       la.U = e->dA;
       la.ldu = e->ld;
@@ -3191,7 +3161,7 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
       la.nct = nblocks;
       hipLaunchKernelGGL(linv_from_u_kernel, dim3((unsigned)((long long)nblocks * (nblocks + 1) / 2)), dim3(256), 0, e->stream, la);
       HIP_TRY(e, hipGetLastError());
-      e->linv_valid = true;
+      e->fs.linv_transposed();
     }
     GemmArgs g{};
     g.C = e->pw2.dV2;
@@ -3251,10 +3221,10 @@ FactorRef joint_factor_ref(JointState& jt) { return FactorRef{jt.dC, jt.Mr, jt.M
 int joint_ready(gmb_engine* e, const char* what) {
   int rc = require_ready(e, true);
   if (rc) return rc;
-  if (e->solve_hook || e->dist_mode != 0 || e->factor_kind != gmb_engine::FK_SINGLE)
+  if (e->solve_hook || e->dist_mode != 0 || !e->fs.single())
     return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode): factorise with gmb_factorize on one device", what);
   if ((rc = require_full_factor(e, what))) return rc;
-  if (e->factor_consumed) return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
+  if (e->fs.consumed()) return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
   return GMB_OK;
 }
 
@@ -3459,7 +3429,7 @@ int backsub_alpha(gmb_engine* e) {
   }
   ev_end(e);
   HIP_TRY(e, hipGetLastError());
-  e->bs_valid = true;
+  e->fs.back_substituted();
   return GMB_OK;
 }
 
@@ -3483,8 +3453,8 @@ int predict_solve_w(gmb_engine* e, int64_t mpad) {
 // factorisation
 int resident_alpha(gmb_engine* e, const double** alpha) {
   int rc;
-  if (!e->have_alpha && !e->bs_valid && (rc = backsub_alpha(e))) return rc;
-  *alpha = e->have_alpha ? e->dalpha : e->dalpha_bs;
+  if (e->fs.needs_backsub() && (rc = backsub_alpha(e))) return rc;
+  *alpha = e->fs.gradient_alpha() ? e->dalpha : e->dalpha_bs;
   return GMB_OK;
 }
 
@@ -3685,7 +3655,7 @@ int predict_sel(gmb_engine* e, const uint32_t* sel, const char* what, const doub
                 double* mean, double* var, int32_t memspace) {
   int rc = require_ready(e, true);
   if (rc) return rc;
-  if (sel && (e->solve_hook || e->dist_mode != 0 || e->factor_kind != gmb_engine::FK_SINGLE))
+  if (sel && (e->solve_hook || e->dist_mode != 0 || !e->fs.single()))
     return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode): factorise with gmb_factorize on one device", what);
   uint32_t terms;
   if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
@@ -3694,7 +3664,7 @@ int predict_sel(gmb_engine* e, const uint32_t* sel, const char* what, const doub
   if (M == 0) return GMB_OK;
   // (the capacity driver's passes come through here with their own triangular solve; everybody else reads the factor in dA)
   if ((rc = e->solve_hook ? require_capacity_factor(e, what) : require_full_factor(e, what))) return rc;
-  if (e->factor_consumed)
+  if (e->fs.consumed())
     return fail(e, GMB_EINVAL, "the factor was consumed by a gradient call: call gmb_factorize again");
   HIP_TRY(e, hipSetDevice(e->device));
   reset_predict_timings(e);
@@ -3974,7 +3944,7 @@ int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
 int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, int64_t nc, double* out) {
   gmb_engine* e = const_cast<gmb_engine*>(ce);
   if (!e || !out) return GMB_EINVAL;
-  if (e->factored && require_full_factor(e, "gmb_copy_factor")) return GMB_EINVAL;
+  if (e->fs.valid() && require_full_factor(e, "gmb_copy_factor")) return GMB_EINVAL;
   if (!e->dA || e->dA.cap <= 0 || r0 < 0 || c0 < 0 || nr < 0 || nc < 0 || r0 + nr > e->Nr || c0 + nc > e->Np)
     return fail(e, GMB_EINVAL, "factor window out of range");
   if (nr == 0 || nc == 0) return GMB_OK;
@@ -3999,7 +3969,7 @@ int gmb_copy_alpha(const gmb_engine* ce, double* out) {
   int rc = require_ready(e, false);
   if (rc) return rc;
   if (!out) return fail(e, GMB_EINVAL, "null output");
-  if (!e->have_alpha || !e->dalpha)
+  if (!e->fs.gradient_alpha() || !e->dalpha)  // (the mark alone: an invalidating call leaves the previous alpha readable)
     return fail(e, GMB_EINVAL, "alpha exists only after a gradient evaluation (gmb_nlml with grad)");
   HIP_TRY(e, hipMemcpy(out, e->dalpha, e->N * sizeof(double), hipMemcpyDeviceToHost));
   return GMB_OK;
@@ -4218,9 +4188,8 @@ int gmb_debug_assume_factored(gmb_engine* e) {
   // in the environment
   const char* door = getenv("GUMBI_HIP_DEBUG_DOORS");
   if (!door || door[0] != '1') return fail(e, GMB_EINVAL, "gmb_debug_assume_factored needs GUMBI_HIP_DEBUG_DOORS=1 in the environment");
-  if (e->factor_kind == gmb_engine::FK_NONE || !e->have_theta) return fail(e, GMB_EINVAL, "no factorisation has been attempted at this theta");
-  e->factored = true;
-  e->factor_consumed = false;
+  if (e->fs.none() || !e->have_theta) return fail(e, GMB_EINVAL, "no factorisation has been attempted at this theta");
+  e->fs.assume_factored();
   e->notpd = -1;
   if (!std::isfinite(e->logdet)) e->logdet = 0.0;
   if (!std::isfinite(e->vnorm2)) e->vnorm2 = 0.0;
@@ -4476,22 +4445,14 @@ extern "C" {
 int gmb_dist_set_mode(gmb_engine* e, int32_t mode) {
   if (!e || mode < 0 || mode > 1) return GMB_EINVAL;
   const int old = e->dist_mode;
-  if (old != mode) {
-    e->factored = false;
-    e->bs_valid = false;
-    e->factor_kind = gmb_engine::FK_NONE;
-  }
+  if (old != mode) e->fs.inputs_changed();
   e->dist_mode = mode;
-  if (mode == 1) {
-    // the point of the mode is that no rank keeps an Nr x Np buffer: one left behind by an earlier single-engine or replicated
-    // factorisation goes now (its factorisation was just invalidated, or is of no use to the capacity passes)
-    if (e->dA && e->dA.cap > 0) {
-      if (hipSetDevice(e->device) == hipSuccess) (void)hipStreamSynchronize(e->stream);
-      e->dA.drop(e->pool);
-      e->factored = false;
-      e->bs_valid = false;
-      e->factor_kind = gmb_engine::FK_NONE;
-    }
+  // the point of mode 1 is that no rank keeps an Nr x Np buffer: one left behind by an earlier single-engine or replicated
+  // factorisation goes now (its factorisation was just invalidated, or is of no use to the capacity passes)
+  if (mode == 1 && e->dA && e->dA.cap > 0) {
+    if (hipSetDevice(e->device) == hipSuccess) (void)hipStreamSynchronize(e->stream);
+    e->dA.drop(e->pool);
+    e->fs.inputs_changed();
   }
   return old;
 }
