@@ -482,7 +482,7 @@ int cap_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   bad.note(e, dist_all_gather(e, comm, mainS, a_send, e->drecv, ldv, &probe, true));  // (behind the last wait: the other stream is idle)
   if (!bad.rc) bad.note(e, dist_pack(e, mainS, e->dalpha, e->Np, e->drecv, ldv, ldv, 1, false, G, 0, 0, G, 0, nt, maxown));
   std::vector<double> h;
-  if (!bad.rc) bad.note(e, grad_reduce(e, rank, G, Z, ldv, true, h));
+  if (!bad.rc) bad.note(e, grad_reduce(e, rank, G, Z, ldv, true, h, GradLanding{}));
   if (!bad.rc) hip_ok(hipMemcpyAsync(e->dsend, e->dgpart, GACC_DOUBLES * sizeof(double), hipMemcpyDeviceToDevice, mainS), "hipMemcpyAsync");
   bad.note(e, dist_all_gather(e, comm, mainS, e->dsend, e->drecv, GACC_DOUBLES, &probe, true));
   std::vector<double> all((size_t)G * GACC_DOUBLES);

@@ -635,7 +635,7 @@ int dist_nlml(gmb_engine* e, const gmb_comm* comm, double* nlml, double* grad) {
   // this rank's block rows of Sigma^-1 = U U^T, packed, into the buffer V occupied; reductions over them
   std::vector<double> h;
   if (!bad.rc) bad.note(e, grad_sigma_inv_rows(e, mainS, rank, G, e->dW, ldv, true));
-  if (!bad.rc) bad.note(e, grad_reduce(e, rank, G, e->dW, ldv, true, h));
+  if (!bad.rc) bad.note(e, grad_reduce(e, rank, G, e->dW, ldv, true, h, GradLanding{}));
   // accumulators of all ranks, summed in rank order on every rank (bit-identical results everywhere)
   if (!bad.rc) hip_ok(hipMemcpyAsync(e->dsend, e->dgpart, GACC_DOUBLES * sizeof(double), hipMemcpyDeviceToDevice, mainS), "hipMemcpyAsync");
   bad.note(e, dist_all_gather(e, comm, mainS, e->dsend, e->drecv, GACC_DOUBLES, &probe, true));

@@ -33,6 +33,7 @@
 #include "device_buffers.hpp"
 #include "term_walk.hpp"
 #include "factor_state.hpp"
+#include "eval_plan.hpp"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_splitk.hpp"
@@ -295,7 +296,6 @@ struct gmb_engine {
   bool ct_trace = false;
   CholResult chol;           // what the tile kernel did in the last TRAINING factorisation
   int ct_lose = 0;           // fault injection (gmb_debug_chol_lose_tickets): one shot
-  bool fact_in_flight = false;  // factorize_enqueue has run, factorize_finish has not
   // a factorisation that has been enqueued but not checked yet (factorize_enqueue / factorize_finish): where its scalars
   // land on the host, and the events around its two phases
   // (PINNED host memory: an asynchronous copy into pageable memory makes the host wait for the stream, and the gradient of
@@ -309,20 +309,9 @@ struct gmb_engine {
   HostLanding* hl = nullptr;
   HostLanding* hl_dev = nullptr;  // the same memory as the device addresses it
   hipEvent_t fe[4] = {nullptr, nullptr, nullptr, nullptr};  // K-build begin / end, Cholesky begin / end
-  // gmb_evaluate with a gradient on the fused launch (`light`): one memset for scalars + accumulators, no copies in between --
-  // eval_land_kernel writes everything the host wants into hl at the end -- and, below 4096 rows and without gmb_set_profiling,
-  // no phase events (six event records were ~30 us of a 380 us evaluation at N = 392)
-  bool eval_call = false;     // set by gmb_evaluate around its factorize_enqueue
-  bool light = false;         // the evaluation in flight runs that way
-  bool gacc_zeroed = false;   // ... and its memset covered the accumulators (grad_reduce skips its own)
-  unsigned long long* prep_zero[2] = {nullptr, nullptr};  // what the NEXT prep_points launch clears besides its own work
-  int64_t prep_zero_words[2] = {0, 0};
-  bool prezeroed = false;     // gmb_evaluate's prep_points launch has cleared the scalar block and the tile launch's words
-  bool prep_deferred = false; // small gmb_evaluate: the points are prepared (and those words cleared) by the covariance build itself
-                              // (CovTileArgs::inline_prep) -- raised by gmb_set_theta, consumed by build_sigma, flushed by gmb_evaluate
-                              // if the build was never reached
-  int inline_prep_max_rows = 4096;
-  bool fe_recorded = false;   // fe[] belong to the factorisation in flight
+  // (how one evaluation uses them -- the fused `light` path, the launch that clears instead of a memset, whether the events are
+  // recorded -- is an EvalPlan, made by gmb_evaluate and passed down in a FactorJob: eval_plan.hpp)
+  int inline_prep_max_rows = 4096;  // small evaluations: the covariance build prepares the points itself (CovTileArgs::inline_prep)
   // persistent evaluation launch (eval_tiles.hpp): L^-T by rows and Sigma^-1 as tile tasks, fused with the tile Cholesky
   // when the caller asks for the gradient together with the factorisation (gmb_evaluate)
   int grad_scheme = -1;        // -1 = by size; 0 = launch tree (winv_levels); 1 = tile tasks behind the factorisation; 2 = fused
@@ -335,7 +324,6 @@ struct gmb_engine {
   int et_ntasks = 0;
   DevBuf<double> dUdiag;       // diagonal tiles of U = L^-T
   DevBuf<double> dApart;       // partial products U(r,c) v_c
-  bool et_fused = false;       // the factorisation in flight carries INV / ZZ tasks: Sigma^-1 (dW) and the alpha parts come with it
   int et_min_blocks = 1;       // smallest matrix (in 128-blocks) whose MAP evaluation runs as the fused launch by default
   // the bottom of the plain recursion (matrices beyond tiles_max_blocks): panels of <= panel_tiles_w block columns, with every
   // row below them, are factored by ONE launch of the tile kernel instead of leaf / strip / small-product launches
@@ -990,13 +978,18 @@ int apply_theta(gmb_engine* e) {
   return GMB_OK;
 }
 
+// what ONE preparation launch clears besides its own work: 64-bit words at two addresses (PrepArgs::zero).  Default: nothing.
+struct PrepClears {
+  unsigned long long* p[2] = {nullptr, nullptr};
+  int64_t words[2] = {0, 0};
+};
+
 PrepArgs prep_args(gmb_engine* e, const double* dXraw, int64_t n, int64_t ldx, int64_t npad, double* xs, double* xl, int32_t* cat,
-                   const PrepArgs* proto) {
+                   const PrepArgs* proto, const PrepClears& clears = PrepClears{}) {
   PrepArgs a = proto ? *proto : e->terms[0].pa;  // (every caller sits behind gmb_set_theta's apply_theta: terms is not empty)
-  for (int z = 0; z < 2; ++z) {  // (one shot: gmb_set_theta inside gmb_evaluate)
-    a.zero[z] = e->prep_zero[z];
-    a.zero_words[z] = e->prep_zero_words[z];
-    e->prep_zero[z] = nullptr;
+  for (int z = 0; z < 2; ++z) {
+    a.zero[z] = clears.p[z];
+    a.zero_words[z] = clears.words[z];
   }
   a.X = dXraw;
   a.n = n;
@@ -1009,26 +1002,16 @@ PrepArgs prep_args(gmb_engine* e, const double* dXraw, int64_t n, int64_t ldx, i
 }
 
 int prep_points(gmb_engine* e, const double* dXraw, int64_t n, int64_t ldx, int64_t npad, double* xs,
-                double* xl, int32_t* cat, const PrepArgs* proto = nullptr) {
-  const PrepArgs a = prep_args(e, dXraw, n, ldx, npad, xs, xl, cat, proto);
+                double* xl, int32_t* cat, const PrepArgs* proto = nullptr, const PrepClears& clears = PrepClears{}) {
+  const PrepArgs a = prep_args(e, dXraw, n, ldx, npad, xs, xl, cat, proto, clears);
   hipLaunchKernelGGL(prep_points_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, e->stream, a);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
 
-// the training points' preparation that a small gmb_evaluate left to its covariance build, if that build was never reached
-int flush_deferred_prep(gmb_engine* e) {
-  if (!e->prep_deferred) return GMB_OK;
-  e->prep_deferred = false;
-  return prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat);
-}
-
 // N (hence Np, Nr, ld) changes -- gmb_set_data, resize_n: every workspace whose size or layout follows from them is stale, and
-// so is the cached launch plan of the triangular inverse.  The union of what the two sites used to mark, one line each:
-//   * prep_deferred was cleared by resize_n only.  It is raised by gmb_set_theta inside a gmb_evaluate and lowered again before
-//     that gmb_evaluate returns (build_sigma consumes it, flush_deferred_prep otherwise), so it is false on entry to either
-//     site and clearing it is a no-op at both.
-//   * the prepared points (pts) were marked by gmb_set_data only and stay there: resize_n keeps them when they are large enough.
+// so is the cached launch plan of the triangular inverse.  The union of what the two sites used to mark, one line each.  (The
+// prepared points (pts) were marked by gmb_set_data only and stay there: resize_n keeps them when they are large enough.)
 void stale_sized_by_n(gmb_engine* e) {
   e->pw.stale();
   e->tg.stale();
@@ -1036,7 +1019,6 @@ void stale_sized_by_n(gmb_engine* e) {
   e->dpart.stale();
   e->pg.stale();
   e->plan_N = -1;
-  e->prep_deferred = false;
 }
 
 PointSet train_set(const gmb_engine* e) { return PointSet{e->pts.xs, e->pts.xl, e->pts.cat, e->N, e->Nr}; }
@@ -1107,14 +1089,14 @@ int launch_train_cov(gmb_engine* e, CovTileArgs& a) {
 }
 
 // Covariance build: lower-triangular tiles of Sigma = K + noise + jitter, the y row, identity padding, written
-// column-major into `out` (Nr x Np, leading dimension ldo) -- the factor buffer in gmb_factorize.
-int build_sigma(gmb_engine* e, double* out, int64_t ldo) {
+// column-major into `out` (Nr x Np, leading dimension ldo) -- the factor buffer in gmb_factorize.  `inline_prep`, if given (a small
+// gmb_evaluate, EvalPlan::inline_prep): this launch prepares the points it stages, and clears what prep_points_kernel would have.
+int build_sigma(gmb_engine* e, double* out, int64_t ldo, const PrepClears* inline_prep = nullptr) {
   CovTileArgs a = train_cov_args(e, out, ldo, (int)(e->Nr / TILE), (int)(e->Np / TILE));
   a.tri_grid = 1;
-  if (e->prep_deferred) {  // small gmb_evaluate: this launch prepares the points it stages (and clears prep_points_kernel's words)
-    e->prep_deferred = false;
+  if (inline_prep) {
     a.inline_prep = 1;
-    a.prep = prep_args(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, nullptr);
+    a.prep = prep_args(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, nullptr, *inline_prep);
   }
   return launch_train_cov(e, a);
 }
@@ -1326,14 +1308,39 @@ int grad_workspace(gmb_engine* e);
 // [4 control | nrt x nct tile flags | 3 nct chain words | nct x nct U flags | nct counts of finished INV tasks per block row]
 int64_t eval_tiles_words(int nct, int nrt) { return 4 + (int64_t)nrt * nct + 3 * (int64_t)nct + (int64_t)nct * nct + nct; }
 
-// gmb_evaluate with a gradient runs as the fused launch (the test factorize_enqueue applies)
+// gmb_evaluate with a gradient runs as the fused launch (what its plan's `light` rests on)
 bool eval_will_fuse(const gmb_engine* e) {
   const int nblocks = (int)(e->Np / TILE);
   return !e->naive_leaf && (e->chol_scheme == 3 || e->chol_scheme < 0) && e->grad_scheme != 0 && e->grad_scheme != 1 &&
          nblocks <= e->tiles_max_blocks && (e->grad_scheme == 2 ? nblocks >= 1 : nblocks >= e->et_min_blocks);
 }
 
-int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
+// gmb_evaluate's plan (eval_plan.hpp), from the engine as it stands when the call begins -- data and kernel are set, theta need
+// not be: an additive model has one term for the whole table and one per coregion dimension (apply_theta)
+EvalPlan plan_evaluate_call(const gmb_engine* e, bool with_grad) {
+  EvalPlanIn in;
+  in.with_grad = with_grad;
+  in.will_fuse = eval_will_fuse(e);
+  in.ct_lose = e->ct_lose;
+  in.nterms = e->spec.additive ? 1 + e->spec.n_coreg : 1;
+  in.Nr = e->Nr;
+  in.Np = e->Np;
+  in.inline_prep_max_rows = e->inline_prep_max_rows;
+  in.naive_leaf = e->naive_leaf;
+  in.profiling = e->profiling;
+  return plan_evaluation(in);
+}
+
+// what the preparation launch of a plan with `prezero` clears: the scalar block and the tile launch's control words (which
+// set_theta has reserved by then)
+PrepClears eval_clears(gmb_engine* e) {
+  const int64_t words = eval_tiles_words((int)(e->Np / TILE), (int)(e->Nr / TILE));
+  using U64 = unsigned long long;
+  return PrepClears{{reinterpret_cast<U64*>(e->dscal.p), reinterpret_cast<U64*>(e->dct.p)}, {SCAL_DOUBLES, (words + 1) / 2}};
+}
+
+// `words_cleared`: the launch that prepared the points has cleared the control words already (EvalPlan::prezero)
+int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol, bool words_cleared) {
   const FactorRef f = train_factor(e);
   const int nct = (int)(e->Np / TILE), nrt = (int)(e->Nr / TILE);
   int rc;
@@ -1369,7 +1376,7 @@ int eval_tiles(gmb_engine* e, hipStream_t s, bool with_chol) {
   if ((rc = e->dUdiag.reserve(e->pool, (int64_t)nct * TILE * TILE))) return rc;
   if ((rc = e->dApart.reserve(e->pool, (int64_t)nct * nct * TILE + nct))) return rc;  // (+ the partials of |v|^2)
   if ((rc = grad_workspace(e))) return rc;
-  if (!(with_chol && e->prezeroed)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), s));
+  if (!(with_chol && words_cleared)) HIP_TRY(e, hipMemsetAsync(e->dct, 0, (size_t)words * sizeof(uint32_t), s));
   // a factor that is final already: every tile flag reads "final" (any non-zero word)
   if (!with_chol) HIP_TRY(e, hipMemsetAsync(e->dct + 4, 1, (size_t)nrt * nct * sizeof(uint32_t), s));
   const int lose = with_chol ? e->ct_lose : 0;
@@ -1849,12 +1856,17 @@ int grad_sigma_inv_rows(gmb_engine* e, hipStream_t s, int shard, int nshards, do
   return launch_gemm(e, s, g, EV_GRAD_GEMM);
 }
 
+// how a pass of grad_reduce begins and ends.  Default (gmb_nlml, the multi-GPU drivers): it clears its accumulators and copies them to `h`.
+struct GradLanding {
+  bool acc_cleared = false;  // the accumulators are clear already: the evaluation's one memset, or its preparation launch
+  bool by_kernel = false;    // the results land in the pinned block (eval_land_kernel / grad_finish_kernel): gmb_evaluate's light path
+};
+
 int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t ldz, bool packed,
-                std::vector<double>& h) {
+                std::vector<double>& h, const GradLanding& landing) {
   const gmb_kernel_spec& s = e->spec;
   const int nt = (int)(e->Np / TILE);
-  if (!e->gacc_zeroed) HIP_TRY(e, hipMemsetAsync(e->dgpart, 0, (GACC_DOUBLES + 64) * sizeof(double), e->stream));
-  e->gacc_zeroed = false;
+  if (!landing.acc_cleared) HIP_TRY(e, hipMemsetAsync(e->dgpart, 0, (GACC_DOUBLES + 64) * sizeof(double), e->stream));
   const int n_ls = s.ard ? s.n_cont : 1;
   long long total = 0;
   for (int i = shard; i < nt; i += nshards) total += i + 1;
@@ -1943,7 +1955,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
         ++r.n;
       };
       double* tmp = e->dgpart + GACC_DOUBLES;  // scratch behind the accumulators
-      merged = e->light && e->terms.size() == 1 && s.ard && !e->periodic && big == 0 && nvec <= 8192 && e->N <= 16384;
+      merged = landing.by_kernel && e->terms.size() == 1 && s.ard && !e->periodic && big == 0 && nvec <= 8192 && e->N <= 16384;
       if (e->periodic) add(0, ncols, (int)(tmp - acc));      // per-column sums, folded into the dimensions' parameters below
       else if (s.ard) add(0, s.n_cont, 0);
       else add(0, s.n_cont, (int)(tmp - acc));               // per-dimension sums, folded into the one parameter below
@@ -1997,7 +2009,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
   });
   if (walked) return walked;
   h.assign(GACC_DOUBLES, 0.0);
-  if (e->light) {
+  if (landing.by_kernel) {
     // gmb_evaluate on the fused launch: scalars, failure index, abort word and the used head of every accumulator region go to
     // the pinned landing in one launch; grad_accumulate hands them on after its synchronisation
     EvalLandArgs la{};
@@ -2058,8 +2070,9 @@ bool grad_by_tiles(const gmb_engine* e) {
 }
 
 // Single-GPU gradient: W = L^-1 and U = L^-T by recursive block inversion, alpha = W^T v, Sigma^-1 = U U^T
-// into dW, reductions.  The factor is consumed.
-int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
+// into dW, reductions.  The factor is consumed.  `job`: the factorisation this gradient is enqueued behind before the host has
+// looked at it (gmb_evaluate), or null behind a factor that is final (gmb_nlml, gmb_evaluate's retry).
+int grad_accumulate(gmb_engine* e, std::vector<double>& h, FactorJob* job) {
   HIP_TRY(e, hipSetDevice(e->device));
   if (e->fs.consumed())
     return fail(e, GMB_EINVAL, "the factor was already consumed by a gradient call; refactorize");
@@ -2069,27 +2082,25 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   if ((rc = e->dW.reserve(e->pool, e->Np * e->Np))) return rc;
   if ((rc = grad_workspace(e))) return rc;
   const int nt = (int)(e->Np / TILE);
-  if (e->et_fused || grad_by_tiles(e)) {
+  const bool fused = job && job->fused_pending;
+  if (fused || grad_by_tiles(e)) {
     // Sigma^-1 and the alpha parts come from the persistent evaluation launch: already enqueued with the factorisation
     // (gmb_evaluate), or launched here behind a factor that is final.  L stays intact: nothing to save or restore.
-    const bool light = e->light && e->et_fused;  // (gmb_evaluate: results land through eval_land_kernel, see grad_reduce)
-    const bool timed = !(light && !e->fe_recorded);
+    const bool light = fused;  // (only gmb_evaluate's light plan enqueues it: results land through eval_land_kernel, see grad_reduce)
+    const bool timed = !(light && !job->events_recorded);
     std::unique_ptr<PhaseTimer> tgt(timed ? new PhaseTimer(e) : nullptr);
     bool own_launch = false;
-    if (!e->et_fused) {
-      if ((rc = eval_tiles(e, e->stream, false))) return rc;
+    if (!fused) {
+      if ((rc = eval_tiles(e, e->stream, false, false))) return rc;
       own_launch = true;
     }
-    e->et_fused = false;
+    if (fused) job->fused_pending = false;
     {  // alpha = U v of the launch, refined against L (intact, diagonal tiles in place) before the a a^T term reads it
       const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
       const TriOperand U{e->dA, e->ld, e->dUdiag, TILE, (int64_t)TILE * TILE};
       if ((rc = refine_alpha(e, L, &U, nullptr, 0))) return rc;
     }
-    e->light = light;
-    rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h);
-    e->light = false;
-    if (rc) return rc;
+    if ((rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h, GradLanding{light, light}))) return rc;  // (light: its clear covered the accumulators)
     if (tgt) tgt->stop();
     uint32_t ab = 0;
     if (own_launch) HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2129,7 +2140,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   }
   // 1. W = L^-1 (dW, lower) and U = L^-T (factor buffer, upper); the factor is consumed from here on
   e->fs.consume();
-  if (!e->fact_in_flight) e->sync_next = 0;  // (gmb_evaluate: the factorisation's cross-stream waits may still be pending on pooled events)
+  if (!(job && job->in_flight)) e->sync_next = 0;  // (gmb_evaluate: the factorisation's cross-stream waits may still be pending on pooled events)
   if (e->par_inverse) {
     if ((rc = winv_levels(e, nt))) return rc;
   } else if ((rc = winv_cols(e, e->stream, 0, nt))) {
@@ -2151,7 +2162,7 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h) {
   hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 0);
   HIP_TRY(e, hipGetLastError());
   // 4. fused trace reductions
-  if ((rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h))) return rc;
+  if ((rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h, GradLanding{}))) return rc;
   tg.stop();
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   tm.grad_ms = tg.ms();
@@ -2574,7 +2585,9 @@ int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t
   return GMB_OK;
 }
 
-int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) {
+// gmb_set_theta; inside a gmb_evaluate, `plan` says what the preparation of the points clears and whether it is left to the
+// covariance build
+static int set_theta(gmb_engine* e, const double* theta, int32_t n, const EvalPlan* plan) {
   if (!e || !theta) return GMB_EINVAL;
   if (!e->have_spec) return fail(e, GMB_EINVAL, "gmb_set_kernel must precede gmb_set_theta");
   if (e->N <= 0) return fail(e, GMB_EINVAL, "gmb_set_data must precede gmb_set_theta");
@@ -2588,23 +2601,19 @@ int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) {
   int rc = apply_theta(e);
   if (rc) return rc;
   if ((rc = e->pts.reserve(e->pool, e->Nr))) return rc;
-  e->prezeroed = false;
-  if (e->eval_call && eval_will_fuse(e) && e->ct_lose == 0) {
+  PrepClears clears;
+  if (plan && plan->prezero) {
     // gmb_evaluate: this launch also clears the scalar block and the tile launch's control words (factorize_enqueue, eval_tiles)
-    const int64_t words = eval_tiles_words((int)(e->Np / TILE), (int)(e->Nr / TILE));
-    if ((rc = e->dct.reserve(e->pool, words + 2))) return rc;
-    e->prep_zero[0] = reinterpret_cast<unsigned long long*>(e->dscal.p);
-    e->prep_zero_words[0] = SCAL_DOUBLES;
-    e->prep_zero[1] = reinterpret_cast<unsigned long long*>(e->dct.p);
-    e->prep_zero_words[1] = (words + 1) / 2;
-    e->prezeroed = true;
+    if ((rc = e->dct.reserve(e->pool, eval_tiles_words((int)(e->Np / TILE), (int)(e->Nr / TILE)) + 2))) return rc;
+    clears = eval_clears(e);
   }
   // small evaluations: the covariance build of this same gmb_evaluate prepares the points itself (one launch less)
-  e->prep_deferred = e->prezeroed && e->terms.size() == 1 && e->Nr <= e->inline_prep_max_rows && !e->naive_leaf;
-  if (!e->prep_deferred && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat))) return rc;
+  if (!(plan && plan->inline_prep) && (rc = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat, nullptr, clears))) return rc;
   e->have_theta = true;
   return GMB_OK;
 }
+
+int gmb_set_theta(gmb_engine* e, const double* theta, int32_t n) { return set_theta(e, theta, n, nullptr); }
 
 int gmb_set_profiling(gmb_engine* e, int32_t on) {
   if (!e) return GMB_EINVAL;
@@ -2688,7 +2697,8 @@ int ensure_host_landing(gmb_engine* e) {
 
 // Everything of gmb_factorize up to (not including) the host's look at the results: K-build, Cholesky, v = L^-1 y, and the
 // asynchronous copies of log-det / |v|^2 / failure index / abort word into the engine.  Nothing is synchronised.
-int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
+int factorize_enqueue(gmb_engine* e, FactorJob& job) {
+  const auto [light, prezero, inline_prep, events] = job.plan;
   int rc = require_ready(e, false);
   if (rc) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
@@ -2703,31 +2713,27 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
     e->panel_blocks = std::max(8, ((nct / 16 + 4) / 8) * 8);
   }
   // the fused evaluation launch pays at every size (per evaluation, stream schedules -> fused: N = 100: 0.21 -> 0.14 ms, N = 392:
-  // 0.44 -> 0.27, N = 1000: 0.76 -> 0.45; tools/gpu_small_eval.py), the tile Cholesky on its own only from six block columns
-  const bool fused = with_grad && eval_will_fuse(e);
-  // gmb_evaluate on the fused launch: everything the host wants lands through eval_land_kernel at the end of the gradient
-  e->light = e->eval_call && fused;
-  const bool events = !(e->light && !e->profiling && e->Np < 4096);
-  e->fe_recorded = events;
-  // scalars + failure index (+ the gradient's accumulators): one memset -- or none, when the evaluation's prep_points launch
-  // has cleared them already (gmb_evaluate)
-  e->prezeroed = e->prezeroed && e->light;
-  if (!e->prezeroed) HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)(e->light ? SCAL_DOUBLES : SCAL_GACC_AT) * sizeof(double), e->stream));
-  e->gacc_zeroed = e->light;
+  // 0.44 -> 0.27, N = 1000: 0.76 -> 0.45; tools/gpu_small_eval.py), the tile Cholesky on its own only from six block columns:
+  // a `light` plan is gmb_evaluate on that launch, and everything the host wants lands through eval_land_kernel at the end of the gradient
+  job.events_recorded = events;
+  // scalars + failure index (+ the gradient's accumulators): one memset -- or none, when the evaluation's preparation launch
+  // clears them (`prezero`)
+  if (!prezero) HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)(light ? SCAL_DOUBLES : SCAL_GACC_AT) * sizeof(double), e->stream));
 
   // 1. covariance build: lower-triangular tiles of Sigma, y row, identity padding
   if (events) HIP_TRY(e, hipEventRecord(e->fe[0], e->stream));
-  if ((rc = build_sigma(e, e->dA, e->ld))) return rc;
+  job.build_reached = true;
+  const PrepClears clears = inline_prep ? eval_clears(e) : PrepClears{};
+  if ((rc = build_sigma(e, e->dA, e->ld, inline_prep ? &clears : nullptr))) return rc;
   if (events) HIP_TRY(e, hipEventRecord(e->fe[1], e->stream));
   // 2. Cholesky
   if (events) HIP_TRY(e, hipEventRecord(e->fe[2], e->stream));
   e->chol = CholResult{};
-  e->et_fused = false;
-  if (fused) {
+  if (light) {
     // the gradient's inverse and Sigma^-1 ride in the factorisation's launch (eval_tiles.hpp); v = L^-1 y (row N of the factor)
     // and |v|^2 come out of the launch that adds up alpha
-    if ((rc = eval_tiles(e, e->stream, true))) return rc;
-    e->et_fused = true;
+    if ((rc = eval_tiles(e, e->stream, true, prezero))) return rc;
+    job.fused_pending = true;
   } else {
     CholOpts o;
     o.masked_ok = true;
@@ -2743,20 +2749,20 @@ int factorize_enqueue(gmb_engine* e, bool with_grad = false) {
   if (events) HIP_TRY(e, hipEventRecord(e->fe[3], e->stream));
   HIP_TRY(e, hipGetLastError());
   if ((rc = ensure_host_landing(e))) return rc;
-  if (!e->light) {
+  if (!light) {
     HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     if (e->chol.tiles) HIP_TRY(e, hipMemcpyAsync(&e->hl->abort, e->dct + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   }
-  e->fact_in_flight = true;
+  job.in_flight = true;
   return GMB_OK;
 }
 
 // The host's look at an enqueued factorisation: synchronise, timings, failure checks; accepts the factor or not.
-int factorize_finish(gmb_engine* e) {
+int factorize_finish(gmb_engine* e, FactorJob& job) {
   gmb_timings& tm = e->tm;
   e->fs.not_accepted();
-  e->fact_in_flight = false;
+  job.in_flight = false;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (!e->hl) return fail(e, GMB_EINVAL, "internal: no factorisation enqueued");
   if (e->hl->abort != 0) {
@@ -2764,8 +2770,8 @@ int factorize_finish(gmb_engine* e) {
     return fail(e, GMB_EHIP, "tile Cholesky: a workgroup waited longer than its time-out for a tile (launch abandoned)");
   }
   float t = 0.f;
-  if (e->fe_recorded && hipEventElapsedTime(&t, e->fe[0], e->fe[1]) == hipSuccess) tm.kbuild_ms = t;
-  if (e->fe_recorded && hipEventElapsedTime(&t, e->fe[2], e->fe[3]) == hipSuccess) tm.chol_ms = t;
+  if (job.events_recorded && hipEventElapsedTime(&t, e->fe[0], e->fe[1]) == hipSuccess) tm.kbuild_ms = t;
+  if (job.events_recorded && hipEventElapsedTime(&t, e->fe[2], e->fe[3]) == hipSuccess) tm.chol_ms = t;
   tm.kbuild_bytes = 8.0 * (double)e->N * (double)(e->N + 1) / 2.0 +
                     8.0 * (double)e->N * (double)(e->spec.n_cont + 1);
   ev_collect(e);
@@ -2787,59 +2793,52 @@ static int factorize_retry_after_abort(gmb_engine* e, int rc) {
   fprintf(stderr, "libgumbi_hip: tile Cholesky abandoned after a time-out; refactorising with the plain recursion\n");
   const int scheme = e->chol_scheme;
   e->chol_scheme = 0;  // (scheme 0 = launches only: no tile kernel anywhere, the recursion's bottom panels included)
-  int rc2 = factorize_enqueue(e);
-  if (!rc2) rc2 = factorize_finish(e);
+  FactorJob job;  // (a fresh plain one)
+  int rc2 = factorize_enqueue(e, job);
+  if (!rc2) rc2 = factorize_finish(e, job);
   e->chol_scheme = scheme;
   return rc2;
 }
 
 int gmb_factorize(gmb_engine* e) {
-  int rc = factorize_enqueue(e);
-  if (!rc) rc = factorize_retry_after_abort(e, factorize_finish(e));
+  FactorJob job;
+  int rc = factorize_enqueue(e, job);
+  if (!rc) rc = factorize_retry_after_abort(e, factorize_finish(e, job));
   return rc;
 }
 
 int gmb_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlml, double* grad) {
   if (!e || !nlml) return GMB_EINVAL;
-  e->eval_call = grad != nullptr;
-  int rc = gmb_set_theta(e, theta, n);
-  if (rc) {
-    e->eval_call = false;
-    return rc;
-  }
-  rc = factorize_enqueue(e, grad != nullptr);
-  e->eval_call = false;
-  e->prezeroed = false;
-  if (e->prep_deferred) {  // the covariance build was not reached (an allocation failed): the points are prepared now
-    const int rc2 = flush_deferred_prep(e);
+  FactorJob job;
+  job.plan = plan_evaluate_call(e, grad != nullptr);
+  int rc = set_theta(e, theta, n, &job.plan);
+  if (rc) return rc;
+  rc = factorize_enqueue(e, job);
+  if (job.plan.inline_prep && !job.build_reached) {
+    // the covariance build was not reached (an allocation failed): the points are prepared now -- without the plan's clears:
+    // nothing reads those words before the next factorisation clears them itself
+    const int rc2 = prep_points(e, e->dX, e->N, e->D, e->Nr, e->pts.xs, e->pts.xl, e->pts.cat);
     if (!rc) rc = rc2;
   }
-  if (rc) {
-    e->light = false;
-    return rc;
-  }
+  if (rc) return rc;
   int rc_grad = GMB_OK;
   std::vector<double> h;
   if (grad) {
     // the gradient's launches follow the factorisation's on the same stream with no host round trip in between; if the
     // factorisation turns out to have failed they ran on garbage and their result is dropped below
     e->fs.accepted();
-    const bool light = e->light;
-    rc_grad = grad_accumulate(e, h);
-    e->light = false;
-    if (rc_grad && light) {  // nothing has landed on the host: there is no factorisation to look at
+    const bool fused = job.fused_pending;  // (a light plan: the factorisation's results land with the gradient's)
+    rc_grad = grad_accumulate(e, h, &job);
+    if (rc_grad && fused) {  // nothing has landed on the host: there is no factorisation to look at
       (void)hipStreamSynchronize(e->stream);
       e->fs.not_accepted();
-      e->fact_in_flight = false;
-      e->et_fused = false;
       return rc_grad;
     }
   }
-  if ((rc = factorize_finish(e))) {
+  if ((rc = factorize_finish(e, job))) {
     e->fs.gradient_ran_on_garbage();
-    e->et_fused = false;
     if (factorize_retry_after_abort(e, rc) != GMB_OK) return rc;
-    rc_grad = grad ? grad_accumulate(e, h) : GMB_OK;  // (an abandoned tile launch: the recursion's factor, the gradient again)
+    rc_grad = grad ? grad_accumulate(e, h, nullptr) : GMB_OK;  // (an abandoned tile launch: the recursion's factor, the gradient again)
   }
   if (rc_grad) return rc_grad;
   *nlml = 0.5 * (double)e->N * std::log(2.0 * M_PI) + e->logdet + 0.5 * e->vnorm2;
@@ -2907,12 +2906,11 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
   hipStream_t s = e->stream;
   begin_factorisation(e, FactorState::SINGLE, true);
   e->chol = CholResult{};
-  e->et_fused = false;
-  e->light = false;
+  FactorJob job;  // (the plain plan)
   // phase events as behind gmb_factorize: kbuild_ms = the rebuilt rows of Sigma, chol_ms = panel solve + corner update + corner
   // factorisation + v (tools/gpu_append.py)
   if ((rc = ensure_phase_events(e))) return rc;
-  e->fe_recorded = true;
+  job.events_recorded = true;
   HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), s));
   const FactorRef f = train_factor(e);
   HIP_TRY(e, hipEventRecord(e->fe[0], s));
@@ -2972,8 +2970,8 @@ int refactor_tail(gmb_engine* e, const AppendLayout& lay) {
   if ((rc = ensure_host_landing(e))) return rc;
   HIP_TRY(e, hipMemcpyAsync(e->hl->scal, e->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(&e->hl->info, e->dinfo, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  e->fact_in_flight = true;
-  return factorize_finish(e);
+  job.in_flight = true;
+  return factorize_finish(e, job);
 }
 
 // N -> N_new under the engine: K rows appended (Xnew, ynew) or the tail cut (Xnew == nullptr).  Kernel, periods and theta stay.
@@ -3814,7 +3812,7 @@ int gmb_nlml(gmb_engine* e, double* nlml, double* grad) {
   if (grad) {
     if ((rc = require_full_factor(e, "gmb_nlml with a gradient"))) return rc;
     std::vector<double> h;
-    if ((rc = grad_accumulate(e, h))) return rc;
+    if ((rc = grad_accumulate(e, h, nullptr))) return rc;
     return grad_chain_rule(e, h, grad);
   }
   return GMB_OK;
