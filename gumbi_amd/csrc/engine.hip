@@ -46,6 +46,7 @@
 #include "joint_predict.hpp"
 #include "predict_grad.hpp"
 #include "predict_terms.hpp"
+#include "leave_out.hpp"
 
 using namespace gmb;
 
@@ -3800,6 +3801,239 @@ int draw_joint_sel(gmb_engine* e, const uint32_t* sel, const char* what, const d
   return predict_end(e, &tp, work());
 }
 
+// ---- leave-one-out and leave-group-out predictions of the training rows (leave_out.hpp) ---------------------------------------------
+
+// what comes off 1 / d_i: the jitter, and the row's noise unless the caller wants it (noise, jitter and the output table are
+// term 0's -- the preparation the resident points hold between calls)
+LeaveOutDiag leave_out_diag(const gmb_engine* e, int32_t with_noise) {
+  const CovParams& p0 = e->terms[0].cp;
+  LeaveOutDiag o{};
+  o.noise.sigma2 = p0.sigma2;
+  o.noise.mult = p0.noise_tab >= 0 ? p0.noise_mult : nullptr;
+  o.noise.cat = p0.noise_tab >= 0 ? e->pts.cat + (int64_t)p0.noise_tab * e->Nr : nullptr;
+  o.jitter = p0.jitter;
+  o.with_noise = with_noise ? 1 : 0;
+  return o;
+}
+
+// gmb_loo sums the resident U = L^-T instead of solving: behind a tile-path gradient (U and the refined alpha are this
+// factorisation's), unless gmb_set_predict_form(e, 0) asks for the solve.  (Two rows per load: an odd leading dimension -- the
+// GMB_LD_PAD probe -- takes the solve.)
+bool loo_takes_product_form(const gmb_engine* e) {
+  return e->predict_form != 0 && e->fs.live_single() && e->fs.u_resident() && e->fs.gradient_alpha() && e->dUdiag && e->dalpha && e->ld % 2 == 0;
+}
+
+// A prediction's workspace for M-tiles of Mt rows, measured against the device before anything is allocated or launched
+// (joint_workspace's rule, without the second matrix)
+int leave_out_workspace(gmb_engine* e, const char* what, int64_t Mt) {
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const double per_row = 8.0 * ((double)e->Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;
+  double fresh = 0.0;
+  if (e->pw.rows < Mt) fresh += per_row * (double)(Mt - e->pw.rows);
+  if ((double)e->dpart.cap < 2.0 * nchunk * (double)Mt) fresh += 8.0 * (2.0 * nchunk * (double)Mt - (double)e->dpart.cap);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+  if (fresh > (double)free_b)
+    return fail(e, GMB_ENOMEM, "%s: tiles of %lld rows behind N = %lld need %.0f bytes on the device, %.0f more than it holds for the engine "
+                               "now; %.0f bytes are free -- nothing was computed",
+                what, (long long)Mt, (long long)e->N, per_row * (double)Mt + 16.0 * nchunk * (double)Mt, fresh, (double)free_b);
+  return predict_workspace(e, Mt);
+}
+
+// selection rows (idx, or i0 + j) into the cleared dV (mpad x Np, row index fastest), solved against L: row j = column idx[j] of
+// L^-1.  Every block column is solved, also those left of the first selected row, where V is and stays zero: the tile solve has no
+// first-column argument, and one schedule serves both.
+int leave_out_solve_rows(gmb_engine* e, const int64_t* didx, int64_t i0, int64_t mc, int64_t mpad) {
+  HIP_TRY(e, hipMemsetAsync(e->pw.dV, 0, (size_t)(mpad * e->Np) * sizeof(double), e->stream));
+  hipLaunchKernelGGL(lo_scatter_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->pw.dV, mpad, didx, i0, mc);
+  HIP_TRY(e, hipGetLastError());
+  return predict_solve_v(e, mpad, false);
+}
+
+int loo_impl(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* mean, double* var, int32_t memspace) {
+  int rc = joint_ready(e, "gmb_loo");
+  if (rc) return rc;
+  if (i0 < 0 || n < 0 || i0 > e->N || n > e->N - i0 || (n > 0 && (!mean || !var)))
+    return fail(e, GMB_EINVAL, "gmb_loo: bad range [%lld, %lld + %lld) of N = %lld rows, or null mean/var", (long long)i0, (long long)i0,
+                (long long)n, (long long)e->N);
+  if (n == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const LeaveOutDiag off = leave_out_diag(e, with_noise);
+  const CopyKinds ck = copy_kinds(memspace);
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  if (loo_takes_product_form(e)) {
+    const int nct = (int)(e->Np / TILE);
+    const int r0 = (int)(i0 / TILE), r1 = (int)((i0 + n - 1) / TILE);
+    const int nchunk = (nct - r0 + LOO_CH - 1) / LOO_CH;
+    if ((rc = e->dpart.reserve(e->pool, (int64_t)nchunk * e->Np + 2 * n))) return rc;
+    reset_predict_timings(e);
+    e->tm.predict_gemm_form = 0;
+    double* dmean = e->dpart + (int64_t)nchunk * e->Np;
+    double* dvar = dmean + n;
+    PhaseTimer tp(e);
+    auto work = [&]() -> int {
+      LooUArgs a{};
+      a.U = e->dA;
+      a.ldu = e->ld;
+      a.udiag = e->dUdiag;
+      a.n = e->N;
+      a.nct = nct;
+      a.r0 = r0;
+      a.part = e->dpart;
+      a.np = e->Np;
+      hipLaunchKernelGGL(loo_u_rowsumsq_kernel, dim3((unsigned)nchunk, (unsigned)(r1 - r0 + 1)), dim3(256), 0, e->stream, a);
+      hipLaunchKernelGGL(loo_u_final_kernel, dim3(nb), dim3(256), 0, e->stream, e->dpart, e->Np, nct, i0, n, e->dalpha, e->dy, off, dmean, dvar);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemcpyAsync(mean, dmean, n * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var, dvar, n * sizeof(double), ck.out, e->stream));
+      return GMB_OK;
+    };
+    return predict_end(e, &tp, work());
+  }
+  const int64_t Mt = predict_tile_rows(e, n);
+  if ((rc = leave_out_workspace(e, "gmb_loo", Mt))) return rc;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < n; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, n - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = leave_out_solve_rows(e, nullptr, i0 + m0, mc, mpad))) return rc;
+      double* pmu = e->dpart;
+      double* ps = e->dpart + (int64_t)nchunk * mpad;
+      hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0)), nchunk), dim3(256), 0, e->stream,
+                         e->pw.dV, mpad, e->dv, e->N, pmu, ps, mpad);
+      hipLaunchKernelGGL(loo_solve_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, pmu, ps, nchunk, mpad,
+                         i0 + m0, mc, e->dy, off, e->pw.dmean, e->pw.dvar);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream));
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
+int leave_out_impl(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_noise, double* mean, double* var, double* cov, int64_t ldc,
+                   int32_t memspace) {
+  const char* what = "gmb_leave_out";
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  if (!mean || (!var && !cov) || (cov && ldc < m)) return fail(e, GMB_EINVAL, "%s: null mean, neither var nor cov, or ldc < m", what);
+  int64_t pos = -1;
+  switch (leave_out_check_indices(idx, m, e->N, &pos)) {
+    case 0: break;
+    case 1: return fail(e, GMB_EINVAL, "%s: idx is null or m = %lld is not in [1, N = %lld]", what, (long long)m, (long long)e->N);
+    case 2: return fail(e, GMB_EINVAL, "%s: idx[%lld] = %lld is not a training row (N = %lld)", what, (long long)pos, (long long)idx[pos], (long long)e->N);
+    default: return fail(e, GMB_EINVAL, "%s: idx[%lld] = %lld appears twice", what, (long long)pos, (long long)idx[pos]);
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  // V (Mr x Np) in the prediction's workspace and C (Mr x Mp) on the joint posterior's second matrix, measured before anything runs
+  if ((rc = joint_workspace(e, what, m, false, host && cov ? (double)m * (double)m : 0.0))) return rc;
+  ScopedBuf<int64_t> didx(e->pool);
+  if ((rc = didx.reserve(e->pool, m))) return rc;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;
+  JointState& jt = e->jt;
+  const int64_t Mr = jt.Mr, Mp = jt.Mp;
+  const LeaveOutDiag off = leave_out_diag(e, with_noise);
+  const CopyKinds ck = copy_kinds(memspace);
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  // g = alpha_B and t = X^T g: two vectors in the prepared test points' block, which no launch of this call reads as points
+  double* g = e->pw.txs;
+  double* t = e->pw.txs + Mr;
+  PhaseTimer tp(e);
+  auto work = [&]() -> int {
+    HIP_TRY(e, hipMemcpyAsync(didx, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+    if ((rc = leave_out_solve_rows(e, didx, 0, m, Mr))) return rc;
+    {  // g_j = <V_j, v> = alpha_{idx[j]}
+      double* pmu = e->dpart;
+      double* ps = e->dpart + (int64_t)nchunk * Mr;
+      hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(Mr / 256 + (Mr % 256 ? 1 : 0)), nchunk), dim3(256), 0, e->stream, e->pw.dV,
+                         Mr, e->dv, e->N, pmu, ps, Mr);
+      hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, pmu, nchunk, Mr, m, g);
+      HIP_TRY(e, hipGetLastError());
+    }
+    // C = V V^T contracts over all Np columns: those of no training point are cleared first (as joint_covariance does)
+    if (e->Np > e->N) HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * Mr, 0, (size_t)((e->Np - e->N) * Mr) * sizeof(double), e->stream));
+    GemmArgs gc{};
+    gc.C = jt.dC;
+    gc.ldc = Mr;
+    gc.A = e->pw.dV;
+    gc.lda = Mr;
+    gc.B = e->pw.dV;
+    gc.ldb = Mr;
+    gc.mt = (int)(Mp / TILE);
+    gc.nt = (int)(Mr / TILE);
+    gc.k = (int)e->Np;
+    gc.alpha = 1.0;
+    gc.beta = 0.0;
+    gc.tri = 1;
+    if ((rc = launch_gemm(e, e->stream, gc, EV_PREDICT_GEMM))) return rc;
+    // rows and columns >= m are zero (V is); identity on the padding diagonal, the border row stays zero
+    if (Mp > m) hipLaunchKernelGGL(lo_pad_diag_kernel, dim3((unsigned)((Mp - m + 127) / 128)), dim3(128), 0, e->stream, jt.dC, Mr, m, Mp);
+    HIP_TRY(e, hipGetLastError());
+    if ((rc = joint_factor(e))) {
+      if (rc == GMB_ENOTPD)
+        return fail(e, GMB_ENOTPD, "%s: (Sigma^-1)_BB of the %lld rows is not positive definite at its row %lld", what, (long long)m, (long long)e->notpd);
+      return rc;
+    }
+    // X = R^-T: identity rows solved against R, in dV (V is dead); what the solve leaves right of column m belongs to no row
+    HIP_TRY(e, hipMemsetAsync(e->pw.dV, 0, (size_t)(Mr * Mp) * sizeof(double), e->stream));
+    hipLaunchKernelGGL(lo_scatter_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, e->stream, e->pw.dV, Mr, (const int64_t*)nullptr,
+                       (int64_t)0, Mp);
+    HIP_TRY(e, hipGetLastError());
+    if ((rc = trsm_cols(e, e->stream, joint_factor_ref(jt), e->pw.dV, Mr, (int)(Mp / TILE), 0, (int)(Mp / TILE), EV_PREDICT_GEMM, EV_SOLVE_STRIP)))
+      return rc;
+    if (Mp > m) HIP_TRY(e, hipMemsetAsync(e->pw.dV + m * Mr, 0, (size_t)((Mp - m) * Mr) * sizeof(double), e->stream));
+    // t = X^T g, then (X t)_j = (C^-1 g)_j and |X_j|^2 = (C^-1)_jj by the prediction's reduction
+    const int nchunk_m = (int)((m + RED_CHUNK - 1) / RED_CHUNK);
+    double* pmu = e->dpart;
+    double* ps = e->dpart + (int64_t)nchunk_m * Mp;
+    hipLaunchKernelGGL(lo_xt_g_kernel, dim3((unsigned)m), dim3(256), 0, e->stream, e->pw.dV, Mr, g, t);
+    hipLaunchKernelGGL(predict_partial_kernel, dim3((unsigned)(Mp / 256 + (Mp % 256 ? 1 : 0)), nchunk_m), dim3(256), 0, e->stream, e->pw.dV, Mr,
+                       t, m, pmu, ps, Mp);
+    hipLaunchKernelGGL(lo_group_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, pmu, ps, nchunk_m, Mp, m,
+                       (const int64_t*)didx, e->dy, off, e->pw.dmean, e->pw.dvar);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, m * sizeof(double), ck.out, e->stream));
+    if (var) HIP_TRY(e, hipMemcpyAsync(var, e->pw.dvar, m * sizeof(double), ck.out, e->stream));
+    if (!cov) return GMB_OK;
+    // C^-1 = X X^T over the factor (dead), symmetrised on its way out, the diagonal corrected there
+    GemmArgs gp{};
+    gp.C = jt.dC;
+    gp.ldc = Mr;
+    gp.A = e->pw.dV;
+    gp.lda = Mr;
+    gp.B = e->pw.dV;
+    gp.ldb = Mr;
+    gp.mt = (int)(Mp / TILE);
+    gp.nt = (int)(Mp / TILE);
+    gp.k = (int)Mp;
+    gp.alpha = 1.0;
+    gp.beta = 0.0;
+    gp.tri = 1;
+    if ((rc = launch_gemm(e, e->stream, gp, EV_PREDICT_GEMM))) return rc;
+    SymArgs sa{};
+    sa.C = jt.dC;
+    sa.ldc = Mr;
+    sa.out = host ? jt.dstage : cov;
+    sa.ldo = host ? m : ldc;
+    sa.M = m;
+    const unsigned nb = (unsigned)((m + 31) / 32);
+    hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
+    hipLaunchKernelGGL(lo_cov_diag_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, sa.out, sa.ldo, m, (const int64_t*)didx, off);
+    HIP_TRY(e, hipGetLastError());
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), jt.dstage, m * sizeof(double), m * sizeof(double), m, hipMemcpyDeviceToHost, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
+}
+
 }  // namespace
 
 extern "C" {
@@ -3937,6 +4171,15 @@ int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
     return GMB_OK;
   };
   return predict_end(e, &tp, tiles());
+}
+
+int gmb_loo(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* mean, double* var, int32_t memspace) {
+  return loo_impl(e, i0, n, with_noise, mean, var, memspace);
+}
+
+int gmb_leave_out(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_noise, double* mean, double* var, double* cov, int64_t ldc,
+                  int32_t memspace) {
+  return leave_out_impl(e, idx, m, with_noise, mean, var, cov, ldc, memspace);
 }
 
 int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, int64_t nc, double* out) {

@@ -363,6 +363,14 @@ class DistributedEngine:
     def predict_decompose(self, Xs):
         _no_terms(0, "predict_decompose")
 
+    def loo(self, rows=None, with_noise=True):
+        raise NotImplementedError("loo: leave-one-out predictions are not built for distributed GPs (they need the complete "
+                                  "factor of a single-engine factorisation)")
+
+    def leave_out(self, idx, with_noise=True, cov=False):
+        raise NotImplementedError("leave_out: leave-group-out predictions are not built for distributed GPs (they need the "
+                                  "complete factor of a single-engine factorisation)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         """Every rank passes the same ``Xs``; the points are sharded over the ranks and every rank receives
         the complete (mean, var)."""

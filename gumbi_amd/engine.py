@@ -347,6 +347,9 @@ _SIGNATURES = {
                                        C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "gmb_predict_decompose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_int32]),
+    "gmb_loo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "gmb_leave_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                C.c_int32]),
 }
 
 
@@ -391,7 +394,8 @@ def _preload_hip_runtime():
 #: variance with both gradients in one call, ``gmb_predict_with_grad``; version 16 ``gmb_append`` / ``gmb_truncate`` -- observations
 #: appended to / cut from the resident factor -- and the split-k GEMM's test door ``gmb_blk_gemm_splitk``; added to version 16
 #: without a change of layout: the components of an additive model, ``gmb_num_terms``, the ``gmb_*_terms`` forms of the four
-#: prediction calls and ``gmb_predict_decompose``)
+#: prediction calls and ``gmb_predict_decompose``; likewise the leave-out predictions of the training rows, ``gmb_loo`` /
+#: ``gmb_leave_out``)
 ABI_VERSION = 16
 
 
@@ -723,6 +727,34 @@ class Engine:
             for u in range(t + 1):
                 cov[t, u] = cov[u, t] = packed[t * (t + 1) // 2 + u]
         return means, cov, noise
+
+    def loo(self, rows=None, with_noise=True):
+        """Leave-one-out predictions of the training rows from the resident factor (``gmb_loo``): ``(mean, var)`` -- what the
+        model, at the resident theta, predicts for observation i from all the others, ``mean_i = y_i - alpha_i / d_i`` and
+        ``var_i = 1 / d_i - jitter`` (less the row's noise with ``with_noise=False``), ``d_i = (Sigma^-1)_ii``.  ``rows``:
+        ``None`` for every row, or a ``(start, stop)`` pair.  No refit: behind a fit it is one pass over the resident inverse
+        factor."""
+        start, stop = (0, self.N) if rows is None else (int(rows[0]), int(rows[1]))
+        n = stop - start
+        mean = np.empty(max(n, 0), dtype=np.float64)
+        var = np.empty(max(n, 0), dtype=np.float64)
+        self._check(self._lib.gmb_loo(self._h, start, n, int(bool(with_noise)), _ptr(mean), _ptr(var), GMB_HOST), "gmb_loo")
+        return mean, var
+
+    def leave_out(self, idx, with_noise=True, cov=False):
+        """The joint prediction of the training rows ``idx`` from all the others (``gmb_leave_out``): ``(mean, var)``, or
+        ``(mean, var, cov)`` with ``cov=True``, in the order of ``idx``.  ``mean = y_B - C^-1 alpha_B`` and
+        ``cov = C^-1 - jitter I`` (less the rows' noise with ``with_noise=False``), ``C = (Sigma^-1)_BB``.  ``ValueError`` for
+        duplicate or out-of-range rows, ``LinAlgError`` when C is not positive definite, ``MemoryError`` -- before anything is
+        computed -- when the device cannot hold the request."""
+        idx = np.ascontiguousarray(np.asarray(idx).ravel(), dtype=np.int64)
+        m = idx.shape[0]
+        mean = np.empty(m, dtype=np.float64)
+        var = np.empty(m, dtype=np.float64)
+        full = np.empty((m, m), dtype=np.float64) if cov else None
+        self._check(self._lib.gmb_leave_out(self._h, _ptr(idx), m, int(bool(with_noise)), _ptr(mean), _ptr(var),
+                                            _ptr(full) if cov else None, max(m, 1), GMB_HOST), "gmb_leave_out")
+        return (mean, var, full) if cov else (mean, var)
 
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with

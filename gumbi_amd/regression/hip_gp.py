@@ -31,6 +31,7 @@ import warnings
 from math import lgamma
 
 import numpy as np
+import pandas as pd
 
 from ..aggregation import DataSet
 from ..arrays import ParameterArray as parray
@@ -985,6 +986,129 @@ class HipGP(Regressor):
                 parts[level] = self.uparray(output[0], means[t], cov[t, t], stdzd=True)
         self.predictions_X = points
         return parts
+
+    # -- leave-one-out and leave-group-out predictions of the training rows -----------------------------------------------------
+    def _leave_out_engine(self, what):
+        if self.MAP is None or self.engine is None:
+            raise ValueError(f"{what}: the model must be fit (find_MAP) first")
+        if self.distributed:
+            raise NotImplementedError(f"{what}: leave-out predictions are not built for distributed GPs (the factor is spread over ranks)")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError(f"{what}: leave-out predictions are not built for the Kronecker path (pass kronecker=False)")
+        return self.engine
+
+    def _output_rows(self):
+        """``{output name: engine rows}``: the rows of ``model.X`` / ``model.y`` that belong to each output."""
+        n = len(self.model.y)
+        if self.out_col not in self.dims:
+            return {self.outputs[0]: np.arange(n)}
+        oc = self.dims.index(self.out_col)
+        col = np.asarray(self.model.X, float)[:, oc]
+        ordered = [name for name, _ in sorted(self.coords[self.out_col].items(), key=lambda kv: kv[1])]
+        coords = np.unique(col)
+        if len(coords) != len(ordered):
+            raise ValueError(f"the output column holds {len(coords)} levels, the model has {len(ordered)} outputs")
+        return {name: np.flatnonzero(col == c) for name, c in zip(ordered, coords)}
+
+    def _unit_rows(self, unit):
+        """The value of column ``unit`` of the table at every engine row (the order of :meth:`_shaped_rows`: a stacked table's
+        outputs one after the other, rows without an observation dropped)."""
+        df = self.get_filtered_data(standardized=False, metric="mean")
+        if unit not in df.columns:
+            raise ValueError(f'leave_group_out: "{unit}" is not a column of the data')
+        names = df[self.out_col].to_numpy()
+        values = df[self.data.values_column if self.data.values_column in df.columns else "Value"].to_numpy()
+        if self.out_col in self.dims:
+            ordered = [name for name, _ in sorted(self.coords[self.out_col].items(), key=lambda kv: kv[1])]
+        else:
+            ordered = [self.outputs[0]]
+        col = df[unit].to_numpy()
+        labels = np.concatenate([col[names == out] for out in ordered])
+        seen = np.concatenate([np.asarray(values[names == out], dtype=np.float64) for out in ordered])
+        labels = labels[~np.isnan(seen)]
+        _, y_table = self._shaped_rows()
+        if len(labels) != len(self.model.y) or not np.array_equal(y_table, np.asarray(self.model.y, float)):
+            raise ValueError("leave_group_out(unit=...): the engine's rows are no longer in the table's order (observations were "
+                             "appended to a stacked table); fit again, or name the rows with `groups`")
+        return labels
+
+    @staticmethod
+    def _gaussian_nlpd(resid, var):
+        return 0.5 * (np.log(2.0 * np.pi * var) + resid ** 2 / var)
+
+    def leave_one_out(self, with_noise=True):
+        """What the fitted model predicts for each observation from all the OTHERS, at the fitted hyper-parameters and without a
+        refit (``gmb_loo``; Rasmussen & Williams 5.4.2): a dict, everything standardized and in the engine's row order
+        (``model.X`` / ``model.y``) --
+
+        ``"mean"``, ``"var"`` (N each); ``"z_score"`` ``(y - mean) / sqrt(var)``; ``"nlpd"`` the Gaussian negative log predictive
+        density of each held-out observation; ``"predictions"`` ``{output name: uparray}`` of that output's rows.
+
+        With ``with_noise=True`` (the default, what a held-out MEASUREMENT is judged against) the variances are those of
+        :meth:`predict` with noise on the data without the row; ``with_noise=False`` gives the latent function's.  Behind
+        :meth:`find_MAP` this is one pass over the inverse factor the fit left on the device."""
+        engine = self._leave_out_engine("leave_one_out")
+        mean, var = engine.loo(with_noise=with_noise)
+        y = np.asarray(self.model.y, dtype=np.float64)
+        resid = y - mean
+        return {
+            "mean": mean,
+            "var": var,
+            "z_score": resid / np.sqrt(var),
+            "nlpd": self._gaussian_nlpd(resid, var),
+            "predictions": {name: self.uparray(name, mean[rows], var[rows], stdzd=True) for name, rows in self._output_rows().items()},
+        }
+
+    def leave_group_out(self, unit=None, groups=None, n_folds=None, seed=None, with_noise=True, joint=False):
+        """The JOINT prediction of each group of observations from all the others, at the fitted hyper-parameters and without a
+        refit (``gmb_leave_out``, one engine call per group).  Exactly one of
+
+        * ``unit``: a column of ``gp.data.wide`` -- rows sharing a value leave together, every output of a stacked table included
+          (the meaning of ``cross_validate(unit=...)``);
+        * ``groups``: a list of index arrays into the engine's rows (``model.X`` / ``model.y``);
+        * ``n_folds``: a random partition from ``np.random.default_rng(seed or self.seed)``.
+
+        Returns a list of dicts, one per group, standardized: ``"rows"``, ``"mean"``, ``"var"``, ``"nlpd"`` (per row), for ``unit``
+        also ``"unit"``; with ``joint=True`` also ``"cov"`` (m x m) and ``"nlpd"`` is the joint Gaussian negative log density of
+        the group's observations."""
+        engine = self._leave_out_engine("leave_group_out")
+        if sum(a is not None for a in (unit, groups, n_folds)) != 1:
+            raise ValueError("leave_group_out: give exactly one of `unit`, `groups` and `n_folds`")
+        n = len(self.model.y)
+        labels = None
+        if unit is not None:
+            if not isinstance(unit, str):
+                raise TypeError('Keyword "unit" must be a single string.')
+            col = self._unit_rows(unit)
+            labels = list(pd.unique(col))
+            parts = [np.flatnonzero(col == value) for value in labels]
+        elif groups is not None:
+            parts = [np.asarray(g, dtype=np.int64).ravel() for g in groups]
+        else:
+            n_folds = int(n_folds)
+            if not 1 <= n_folds <= n:
+                raise ValueError(f"leave_group_out: n_folds must be in [1, {n}], got {n_folds}")
+            perm = np.random.default_rng(seed or self.seed).permutation(n)
+            parts = [np.sort(part) for part in np.array_split(perm, n_folds)]
+        y = np.asarray(self.model.y, dtype=np.float64)
+        out = []
+        for k, rows in enumerate(parts):
+            res = engine.leave_out(rows, with_noise=with_noise, cov=joint)
+            mean, var = res[0], res[1]
+            resid = y[rows] - mean
+            entry = {"rows": rows, "mean": mean, "var": var}
+            if joint:
+                cov = res[2]
+                chol = np.linalg.cholesky(cov)
+                white = np.linalg.solve(chol, resid)
+                entry["cov"] = cov
+                entry["nlpd"] = float(0.5 * (white @ white) + np.log(np.diag(chol)).sum() + 0.5 * len(rows) * np.log(2.0 * np.pi))
+            else:
+                entry["nlpd"] = self._gaussian_nlpd(resid, var)
+            if labels is not None:
+                entry["unit"] = labels[k]
+            out.append(entry)
+        return out
 
     def decompose_grid(self, output=None, categorical_levels=None):
         """:meth:`decompose_points` on the grid :meth:`prepare_grid` left behind, every level in the grid's shape."""

@@ -264,6 +264,12 @@ class IcmEngine:
     def predict_decompose(self, Xs):
         _no_terms(0, "predict_decompose")
 
+    def loo(self, rows=None, with_noise=True):
+        raise NotImplementedError("loo: leave-one-out predictions are not built for the Kronecker engine (pass kronecker=False)")
+
+    def leave_out(self, idx, with_noise=True, cov=False):
+        raise NotImplementedError("leave_out: leave-group-out predictions are not built for the Kronecker engine (pass kronecker=False)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

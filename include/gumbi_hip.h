@@ -401,6 +401,37 @@ int gmb_draw_joint_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_
 int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* means, int64_t ldm, double* cov,
                           int64_t ldcv, double* noise, int32_t memspace);
 
+/* -- leave-one-out and leave-group-out predictions of the TRAINING rows (added to version 16 without a change of layout) ---------
+ * What the model, at the resident theta, predicts for observations it is not shown -- from the resident factorisation alone, no
+ * refit (Rasmussen & Williams 5.4.2).  With Sigma = L L^T the factored matrix (noise and jitter on its diagonal) and
+ * alpha = Sigma^-1 y:   y_B | y_-B ~ N(y_B - C^-1 alpha_B, C^-1),  C = (Sigma^-1)_BB.  Sigma holds the jitter and gmb_predict's
+ * with_noise variance does not, so the jitter is taken off every variance here: with_noise = 1 is gmb_predict(with_noise = 1) on
+ * the data without the rows, to rounding.  Beyond the reference, on state only this engine keeps.
+ *
+ * Readiness and refusals as gmb_predict_joint: a complete, unconsumed single-engine factor; GMB_EINVAL for distributed and
+ * capacity-mode engines, a consumed factor, no factorisation yet, null outputs, a range outside [0, N], duplicate or out-of-range
+ * idx, m < 1, ldc < m -- nothing launched, nothing written.  A workspace the device cannot hold returns GMB_ENOMEM before anything
+ * is launched, the bytes in gmb_last_error.  State contract of the *_terms calls: the factor, v, both alphas, U, L^-1 and their
+ * flags, the joint state's meaning and gmb_factor_valid are left as found; the same bits call after call (no atomics). */
+
+/* Leave-one-out predictive mean and variance of the training rows [i0, i0 + n): what the model predicts for observation i from all
+ * the others.  mean, var: length n, in `memspace`.  d_i = (Sigma^-1)_ii:
+ *   mean_i = y_i - alpha_i / d_i        var_i = 1 / d_i - jitter - (with_noise ? 0 : noise_i)
+ * (noise_i: the model's noise variance at row i).  Behind a tile-path gradient evaluation (gmb_evaluate / gmb_nlml with grad:
+ * U = L^-T and alpha resident) and unless gmb_set_predict_form(e, 0), d_i = sum_{j >= i} U_ij^2 is ONE pass over the resident
+ * triangle (4 N^2 bytes); otherwise selection rows are solved against L in gmb_predict's M-tiles.  n == 0 is GMB_OK. */
+int gmb_loo(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* mean, double* var, int32_t memspace);
+
+/* The JOINT predictive of the m training rows idx[0..m) from all the others.  idx: HOST memory always, distinct, each in [0, N),
+ * 1 <= m <= N; outputs in the order of idx.  C = (Sigma^-1)_BB:
+ *   mean = y_B - C^-1 alpha_B      cov = C^-1 - jitter I - (with_noise ? 0 : diag noise_B)      var = diag(cov)
+ * mean, var: length m; cov: m x m row-major, leading dimension ldc >= m, both triangles, exactly symmetric; cov may be NULL (then
+ * nothing of size m x m is formed beyond C's factor), var may be NULL when cov is not.  Always the triangular solve against L; C is
+ * factored by the engine's Cholesky on the joint posterior's second matrix: GMB_ENOTPD + gmb_notpd_index (a row of C) when C is
+ * not positive definite. */
+int gmb_leave_out(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_noise, double* mean, double* var,
+                  double* cov, int64_t ldc, int32_t memspace);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
