@@ -47,6 +47,7 @@
 #include "predict_grad.hpp"
 #include "predict_terms.hpp"
 #include "leave_out.hpp"
+#include "group_average.hpp"
 
 using namespace gmb;
 
@@ -80,9 +81,11 @@ enum EvKind : int {
   EV_PREDICT_VGRAD_SOLVE = 15, // gmb_predict_with_grad: the second triangular pass W = V L^-1 of one M-tile
   // (ABI 16)
   EV_SPLITK = 16,             // the split-k product's launch pair (gemm_splitk.hpp): flags = slices
-  EV_TERM_GRAM = 17           // gmb_predict_decompose: the reduction's partial + final launches of one M-tile (k = terms)
+  EV_TERM_GRAM = 17,          // gmb_predict_decompose: the reduction's partial + final launches of one M-tile (k = terms)
+  EV_GROUP_COV = 18           // gmb_predict_groups: the partial launches of one reduction of one term (mt = column blocks, nt = tasks,
+                              // flags = 0 the cross part A, 1 the prior part Q, 2 its diagonal only)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_TERM_GRAM); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_GROUP_COV); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -243,6 +246,23 @@ struct gmb_engine {
       });
     }
   } tg;
+  // gmb_predict_groups (group_average.hpp), sized by the call's M points and by nothing of size M x N: the raw and the prepared
+  // points, their weights and one row block of R (128 x M); beside them the task partials and the call's index arrays
+  struct GroupWorkspace : RowGroup {
+    DevBuf<double> Xs, xs, xl, w, R;
+    DevBuf<int32_t> cat;
+    int reserve(DevPool& pool, int64_t Mp, int D) {
+      return reserve_rows(Mp, [&] {
+        int rc;
+        if ((rc = Xs.renew(pool, Mp * (int64_t)D)) || (rc = xs.renew(pool, (int64_t)17 * Mp)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * Mp)) ||
+            (rc = w.renew(pool, Mp)) || (rc = R.renew(pool, (int64_t)GA_ROWS * Mp)))
+          return rc;
+        return cat.renew(pool, (int64_t)MAX_TABS * Mp);
+      });
+    }
+  } ga;
+  DevBuf<double> ga_part;   // [task][column] of one reduction
+  DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
 
   // gradient workspace
   DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
@@ -560,7 +580,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_PREDICT_VGRAD:
       case EV_PREDICT_VGRAD_SOLVE:
       case EV_SPLITK:
-      case EV_TERM_GRAM: break;
+      case EV_TERM_GRAM:
+      case EV_GROUP_COV: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -1019,6 +1040,7 @@ void stale_sized_by_n(gmb_engine* e) {
   e->pw2.stale();
   e->dpart.stale();
   e->pg.stale();
+  e->ga.stale();
   e->plan_N = -1;
 }
 
@@ -4034,6 +4056,282 @@ int leave_out_impl(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_no
   return predict_end(e, &tp, work());
 }
 
+// ---- averages of the posterior over groups of points (group_average.hpp) ------------------------------------------------------------
+
+template <int KIND, int NC>
+void launch_group_cov_nc(gmb_engine* e, const GroupCovArgs& a, dim3 grid, bool gen) {
+  auto go = [&](void (*kernel)(GroupCovArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
+  if (gen) go(group_cov_partial_kernel<KIND, NC, true>);
+  else go(group_cov_partial_kernel<KIND, NC, false>);
+}
+
+template <int KIND>
+void launch_group_cov_kind(gmb_engine* e, const GroupCovArgs& a, dim3 grid, bool gen) {
+  switch (e->nc_pad) {
+    case 1: launch_group_cov_nc<KIND, 1>(e, a, grid, gen); break;
+    case 2: launch_group_cov_nc<KIND, 2>(e, a, grid, gen); break;
+    case 4: launch_group_cov_nc<KIND, 4>(e, a, grid, gen); break;
+    case 8: launch_group_cov_nc<KIND, 8>(e, a, grid, gen); break;
+    default: launch_group_cov_nc<KIND, 16>(e, a, grid, gen); break;
+  }
+}
+
+constexpr int64_t GA_TASK_SLAB = 32768;  // tasks per launch (the grid's y extent)
+
+// The partials of `ntask` tasks (a.tasks: the first one's triple, a.part: its row) against a.cols, dispatched as launch_cov /
+// launch_predict_grad dispatch theirs; lists longer than the grid's y extent go in slabs.
+int launch_group_cov(gmb_engine* e, const GroupCovArgs& a_in, int64_t ntask) {
+  const bool gen = a_in.p.n_lin > 0 || a_in.p.n_tab > 0;
+  for (int64_t t0 = 0; t0 < ntask; t0 += GA_TASK_SLAB) {
+    GroupCovArgs a = a_in;
+    a.tasks += 3 * t0;
+    a.part += t0 * a.ldp;
+    const dim3 grid((unsigned)(a.ldp / GA_COLS), (unsigned)std::min<int64_t>(GA_TASK_SLAB, ntask - t0));
+    switch (a.p.kind) {
+      case GMB_EXPQUAD: launch_group_cov_kind<0>(e, a, grid, gen); break;
+      case GMB_MATERN52: launch_group_cov_kind<1>(e, a, grid, gen); break;
+      case GMB_MATERN32: launch_group_cov_kind<2>(e, a, grid, gen); break;
+      case GMB_MATERN12: launch_group_cov_kind<3>(e, a, grid, gen); break;
+      case GMB_EXPONENTIAL: launch_group_cov_kind<4>(e, a, grid, gen); break;
+      default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
+    }
+    HIP_TRY(e, hipGetLastError());
+  }
+  return GMB_OK;
+}
+
+// what a call's groups come to: tasks (group_tasks.hpp), and the most tasks any row block of 128 groups holds
+struct GroupPlan {
+  std::vector<int64_t> tasks, first_task;
+  int64_t ntask = 0, block_tasks = 0;
+};
+
+// Every buffer of gmb_predict_groups, measured against the device before anything is allocated, launched or written
+// (joint_workspace's rule): the feature's own workspace -- O(M D), one row block of R and the task partials -- a prediction's for
+// Gr = round_up(G + 1, 128) rows (NEVER for M), the product form's second V, and for a covariance the second matrix and the staging
+// of a host-side result.
+int group_workspace(gmb_engine* e, const char* what, int64_t M, int64_t G, const GroupPlan& plan, bool gemm_form, bool with_cov, double stage) {
+  JointState& jt = e->jt;
+  const int64_t mp = round_up(M, TILE), gr = round_up(G + 1, TILE), gp = round_up(G, TILE);
+  const double Mp = (double)mp, Gr = (double)gr, Gp = (double)gp, Np = (double)e->Np;
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const double ga_row = 8.0 * (e->D + 17 + MAX_LIN + 1 + GA_ROWS) + 4.0 * MAX_TABS;
+  const double part = std::max((double)plan.ntask * Np, (double)plan.block_tasks * Mp);
+  const double idx = 3.0 * (double)plan.ntask + 2.0 * (double)(G + 1);
+  const double per_row = 8.0 * (Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;  // predict_workspace, per row
+  const double total = ga_row * Mp + 8.0 * part + 8.0 * idx + per_row * Gr + 16.0 * nchunk * Gr + (gemm_form ? 8.0 * Gr * Np : 0.0) +
+                       (with_cov ? 8.0 * Gr * Gp + 8.0 * stage : 0.0);
+  double fresh = 0.0;
+  if ((double)e->ga.rows < Mp) fresh += ga_row * (Mp - (double)e->ga.rows);
+  if ((double)e->ga_part.cap < part) fresh += 8.0 * (part - (double)e->ga_part.cap);
+  if ((double)e->ga_idx.cap < idx) fresh += 8.0 * (idx - (double)e->ga_idx.cap);
+  if ((double)e->pw.rows < Gr) fresh += per_row * (Gr - (double)e->pw.rows);
+  if ((double)e->dpart.cap < 2.0 * nchunk * Gr) fresh += 8.0 * (2.0 * nchunk * Gr - (double)e->dpart.cap);
+  if (gemm_form && (double)e->pw2.rows < Gr) fresh += 8.0 * Np * (Gr - (double)e->pw2.rows);
+  if (with_cov && (double)jt.dC.cap < Gr * Gp) fresh += 8.0 * (Gr * Gp - (double)jt.dC.cap);
+  if (with_cov && (double)jt.dstage.cap < stage) fresh += 8.0 * (stage - (double)jt.dstage.cap);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+  // (every grid extent and index below stays inside 31 bits with these)
+  if (fresh > (double)free_b || Mp > 1073741824.0 || Gr * ((Np > Mp ? Np : Mp) / 256.0 + 1.0) > 2147483647.0)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld points in G = %lld groups behind N = %lld need %.0f bytes on the device (points and R: %.0f, "
+                               "task partials: %.0f, V: %.0f%s, C: %.0f), %.0f more than it holds for the engine now; %.0f bytes are free -- "
+                               "nothing was computed",
+                what, (long long)M, (long long)G, (long long)e->N, total, ga_row * Mp, 8.0 * part, 8.0 * Gr * Np, gemm_form ? " twice" : "",
+                with_cov ? 8.0 * Gr * Gp : 0.0, fresh, (double)free_b);
+  int rc;
+  if (with_cov) {
+    if ((rc = joint_workspace(e, what, G, gemm_form, stage))) return rc;
+  } else {
+    if ((rc = predict_workspace(e, gr))) return rc;
+    if (gemm_form && (rc = predict_gemm_form_workspace(e, gr))) return rc;
+  }
+  if ((rc = e->ga.reserve(e->pool, mp, e->D))) return rc;
+  if ((rc = e->ga_part.reserve(e->pool, (int64_t)part))) return rc;
+  return e->ga_idx.reserve(e->pool, (int64_t)idx);
+}
+
+int predict_groups_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets,
+                       int64_t G, const double* weights, double* mean, double* var, double* cov, int64_t ldc, int32_t memspace) {
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (!Xs || !offsets || !mean || (!var && !cov) || G < 1 || M < 1 || ldxs < e->D || (cov && ldc < G))
+    return fail(e, GMB_EINVAL, "%s: null Xs/offsets/mean, neither var nor cov, G < 1, M < 1, ldxs < D or ldc < G", what);
+  int64_t pos = -1;
+  switch (group_check_offsets(offsets, G, M, &pos)) {
+    case 0: break;
+    case 2: return fail(e, GMB_EINVAL, "%s: offsets[0] = %lld, not 0", what, (long long)offsets[0]);
+    case 3:
+      return fail(e, GMB_EINVAL, "%s: group %lld is empty or runs backwards (offsets[%lld] = %lld, offsets[%lld] = %lld)", what, (long long)pos,
+                  (long long)pos, (long long)offsets[pos], (long long)pos + 1, (long long)offsets[pos + 1]);
+    case 4: return fail(e, GMB_EINVAL, "%s: offsets[G] = %lld, not M = %lld", what, (long long)offsets[G], (long long)M);
+    default: return fail(e, GMB_EINVAL, "%s: bad offsets", what);
+  }
+  const bool host = memspace != GMB_DEVICE;
+  if (weights && host)
+    for (int64_t m = 0; m < M; ++m)
+      if (!std::isfinite(weights[m])) return fail(e, GMB_EINVAL, "%s: weights[%lld] is not finite", what, (long long)m);
+  HIP_TRY(e, hipSetDevice(e->device));
+
+  if (M > 1073741824)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld points are more than a call takes (2^30) -- nothing was computed", what, (long long)M);
+  GroupPlan plan;
+  plan.ntask = group_build_tasks(offsets, G, GROUP_CHUNK, &plan.tasks, &plan.first_task);
+  for (int64_t g0 = 0; g0 < G; g0 += GA_ROWS)
+    plan.block_tasks = std::max(plan.block_tasks, plan.first_task[std::min<int64_t>(G, g0 + GA_ROWS)] - plan.first_task[g0]);
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = group_workspace(e, what, M, G, plan, gemm_form, cov != nullptr, host && cov ? (double)G * (double)G : 0.0))) return rc;
+  std::vector<double> mean_w;  // weights == NULL: 1 / |g|, a plain mean (alive until the call's stream has drained)
+  if (!weights) {
+    mean_w.resize((size_t)M);
+    for (int64_t g = 0; g < G; ++g) {
+      const double wg = 1.0 / (double)(offsets[g + 1] - offsets[g]);
+      for (int64_t m = offsets[g]; m < offsets[g + 1]; ++m) mean_w[(size_t)m] = wg;
+    }
+  }
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+
+  JointState& jt = e->jt;
+  const int64_t Mp = round_up(M, TILE), Gr = round_up(G + 1, TILE), Gp = round_up(G, TILE);
+  const CopyKinds ck = copy_kinds(memspace);
+  const int64_t* d_tasks = e->ga_idx;
+  const int64_t* d_first = e->ga_idx + 3 * plan.ntask;
+  const int64_t* d_off = d_first + (G + 1);
+  const PointSet pts{e->ga.xs, e->ga.xl, e->ga.cat, M, Mp};
+  const int t_first = first_term(terms);
+  PhaseTimer tp(e);
+  auto work = [&]() -> int {
+    HIP_TRY(e, hipMemcpy2DAsync(e->ga.Xs, e->D * sizeof(double), Xs, ldxs * sizeof(double), e->D * sizeof(double), M, ck.in, e->stream));
+    if (weights) HIP_TRY(e, hipMemcpyAsync(e->ga.w, weights, M * sizeof(double), ck.in, e->stream));
+    else HIP_TRY(e, hipMemcpyAsync(e->ga.w, mean_w.data(), M * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->ga_idx, plan.tasks.data(), 3 * plan.ntask * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->ga_idx + 3 * plan.ntask, plan.first_task.data(), (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->ga_idx + 3 * plan.ntask + (G + 1), offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+    // A's rows G .. Gr - 1 belong to no group and stay zero; C starts as the bordered layout's padding (identity on the padding
+    // diagonal, a zero border row)
+    HIP_TRY(e, hipMemsetAsync(e->pw.dV, 0, (size_t)(Gr * e->Np) * sizeof(double), e->stream));
+    if (cov) {
+      HIP_TRY(e, hipMemsetAsync(jt.dC, 0, (size_t)(Gr * Gp) * sizeof(double), e->stream));
+      if (Gp > G) hipLaunchKernelGGL(lo_pad_diag_kernel, dim3((unsigned)((Gp - G + 127) / 128)), dim3(128), 0, e->stream, jt.dC, Gr, G, Gp);
+      HIP_TRY(e, hipGetLastError());
+    }
+    rc = walk_terms(e, terms, [&](int t) -> int {
+      const gmb_engine::Term& tr = e->terms[t];
+      const bool first = t == t_first;
+      int r;
+      if ((r = prep_points(e, e->ga.Xs, M, e->D, Mp, e->ga.xs, e->ga.xl, e->ga.cat, &tr.pa))) return r;
+      GroupCovArgs a{};
+      a.p = tr.cp;
+      a.pts = pts;
+      a.w = e->ga.w;
+      a.part = e->ga_part;
+      a.offsets = d_off;
+      GroupFinishArgs f{};
+      f.part = e->ga_part;
+      f.first_task = d_first;
+      f.accumulate = first ? 0 : 1;
+      f.offsets = d_off;
+      // A: every task against the training points -> dV (Gr x Np, group index fastest; columns >= N are zero)
+      a.cols = train_set(e);
+      a.tasks = d_tasks;
+      a.ldp = e->Np;
+      ev_begin(e, e->stream, EV_GROUP_COV, 0.0, (int)(a.ldp / GA_COLS), (int)plan.ntask, 0, 0);
+      r = launch_group_cov(e, a, plan.ntask);
+      ev_end(e);
+      if (r) return r;
+      f.ldp = e->Np;
+      f.task0 = 0;
+      f.g0 = 0;
+      f.ng = G;
+      f.ncols = e->Np;
+      f.out = e->pw.dV;
+      f.ldo = Gr;
+      hipLaunchKernelGGL(group_cov_finish_kernel, dim3((unsigned)(G * ((e->Np + 255) / 256))), dim3(256), 0, e->stream, f);
+      HIP_TRY(e, hipGetLastError());
+      // Q: the group points against themselves, a row block of 128 groups at a time -> R -> folded into C (and kss)
+      a.cols = pts;
+      a.ldp = Mp;
+      a.diag_only = cov ? 0 : 1;
+      f.ldp = Mp;
+      f.ncols = M;
+      f.out = e->ga.R;
+      f.ldo = GA_ROWS;
+      f.accumulate = 0;
+      f.diag_only = a.diag_only;
+      for (int64_t g0 = 0; g0 < G; g0 += GA_ROWS) {
+        const int64_t ng = std::min<int64_t>(GA_ROWS, G - g0);
+        const int64_t tb0 = plan.first_task[g0], nt = plan.first_task[g0 + ng] - tb0;
+        a.tasks = d_tasks + 3 * tb0;
+        ev_begin(e, e->stream, EV_GROUP_COV, 0.0, (int)(a.ldp / GA_COLS), (int)nt, 0, a.diag_only ? 2 : 1);
+        r = launch_group_cov(e, a, nt);
+        ev_end(e);
+        if (r) return r;
+        f.task0 = tb0;
+        f.g0 = g0;
+        f.ng = ng;
+        hipLaunchKernelGGL(group_cov_finish_kernel, dim3((unsigned)(ng * ((M + 255) / 256))), dim3(256), 0, e->stream, f);
+        GroupFoldArgs fo{};
+        fo.R = e->ga.R;
+        fo.w = e->ga.w;
+        fo.offsets = d_off;
+        fo.g0 = g0;
+        fo.G = G;
+        fo.C = cov ? (double*)jt.dC : nullptr;
+        fo.ldc = Gr;
+        fo.kss = e->pw.dkss;
+        fo.accumulate = first ? 0 : 1;
+        fo.diag_only = a.diag_only;
+        hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)(a.diag_only ? 1 : g0 + ng)), dim3(GA_ROWS), 0, e->stream, fo);
+        HIP_TRY(e, hipGetLastError());
+      }
+      return GMB_OK;
+    });
+    if (rc) return rc;
+    // from here on it is a prediction at Gr rows: V_A = A L^-T, mean = V_A v, var = diag Q - |V_A|^2 (not clipped)
+    if ((rc = predict_solve_v(e, Gr, gemm_form))) return rc;
+    if ((rc = predict_reduce(e, G, Gr, gemm_form))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(mean, e->pw.dmean, G * sizeof(double), ck.out, e->stream));
+    if (var) HIP_TRY(e, hipMemcpyAsync(var, e->pw.dvar, G * sizeof(double), ck.out, e->stream));
+    if (!cov) return GMB_OK;
+    // C -= V_A V_A^T as joint_covariance does it: the product form's V turned into the update's k-major layout, the columns of no
+    // training point cleared, the trailing update's launch with contraction length Np
+    if (gemm_form && (rc = launch_transpose(e, e->stream, e->pw2.dV2, e->Np, e->pw.dV, Gr, (int)e->Np, (int)Gr))) return rc;
+    if (e->Np > e->N) HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * Gr, 0, (size_t)((e->Np - e->N) * Gr) * sizeof(double), e->stream));
+    GemmArgs g{};
+    g.C = jt.dC;
+    g.ldc = Gr;
+    g.A = e->pw.dV;
+    g.lda = Gr;
+    g.B = e->pw.dV;
+    g.ldb = Gr;
+    g.mt = (int)(Gp / TILE);
+    g.nt = (int)(Gr / TILE);
+    g.k = (int)e->Np;
+    g.alpha = -1.0;
+    g.beta = 1.0;
+    g.tri = 1;
+    if ((rc = launch_gemm(e, e->stream, g, EV_PREDICT_GEMM))) return rc;
+    // both triangles from the lower one (exactly symmetric), the reduction's variance on the diagonal (cov's diagonal IS var)
+    SymArgs sa{};
+    sa.C = jt.dC;
+    sa.ldc = Gr;
+    sa.out = host ? (double*)jt.dstage : cov;
+    sa.ldo = host ? G : ldc;
+    sa.M = G;
+    const unsigned nb = (unsigned)((G + 31) / 32);
+    hipLaunchKernelGGL(joint_symmetrise_kernel, dim3(nb, nb), dim3(256), 0, e->stream, sa);
+    hipLaunchKernelGGL(group_cov_diag_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, e->stream, sa.out, sa.ldo, G, (const double*)e->pw.dvar);
+    HIP_TRY(e, hipGetLastError());
+    if (host)
+      HIP_TRY(e, hipMemcpy2DAsync(cov, ldc * sizeof(double), jt.dstage, G * sizeof(double), G * sizeof(double), G, hipMemcpyDeviceToHost, e->stream));
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, work());
+}
+
 }  // namespace
 
 extern "C" {
@@ -4180,6 +4478,26 @@ int gmb_loo(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* me
 int gmb_leave_out(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_noise, double* mean, double* var, double* cov, int64_t ldc,
                   int32_t memspace) {
   return leave_out_impl(e, idx, m, with_noise, mean, var, cov, ldc, memspace);
+}
+
+int gmb_predict_groups(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets, int64_t G, const double* weights,
+                       double* mean, double* var, double* cov, int64_t ldc, int32_t memspace) {
+  return predict_groups_sel(e, nullptr, "gmb_predict_groups", Xs, M, ldxs, offsets, G, weights, mean, var, cov, ldc, memspace);
+}
+
+int gmb_predict_groups_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets, int64_t G,
+                             const double* weights, double* mean, double* var, double* cov, int64_t ldc, int32_t memspace) {
+  return predict_groups_sel(e, &terms, "gmb_predict_groups_terms", Xs, M, ldxs, offsets, G, weights, mean, var, cov, ldc, memspace);
+}
+
+int64_t gmb_debug_group_tasks(const int64_t* offsets, int64_t G, int64_t chunk, int64_t* out, int64_t cap) {
+  if (!offsets || G < 1) return (int64_t)GMB_EINVAL;
+  if (group_check_offsets(offsets, G, offsets[G], nullptr)) return (int64_t)GMB_EINVAL;
+  std::vector<int64_t> tasks;
+  const int64_t n = group_build_tasks(offsets, G, chunk > 0 ? chunk : GROUP_CHUNK, &tasks);
+  for (int64_t i = 0; i < n && i < cap && out; ++i)
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = tasks[(size_t)(3 * i + k)];
+  return n;
 }
 
 int gmb_copy_factor(const gmb_engine* ce, int64_t r0, int64_t nr, int64_t c0, int64_t nc, double* out) {

@@ -371,6 +371,10 @@ class DistributedEngine:
         raise NotImplementedError("leave_out: leave-group-out predictions are not built for distributed GPs (they need the "
                                   "complete factor of a single-engine factorisation)")
 
+    def predict_groups(self, Xs, offsets, weights=None, cov=False, terms=None):
+        raise NotImplementedError("predict_groups: group averages of the posterior are not built for distributed GPs (they need "
+                                  "the complete factor of a single-engine factorisation)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         """Every rank passes the same ``Xs``; the points are sharded over the ranks and every rank receives
         the complete (mean, var)."""

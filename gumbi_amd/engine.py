@@ -350,6 +350,11 @@ _SIGNATURES = {
     "gmb_loo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "gmb_leave_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                 C.c_int32]),
+    "gmb_predict_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_predict_groups_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_debug_group_tasks": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
 }
 
 
@@ -395,8 +400,12 @@ def _preload_hip_runtime():
 #: appended to / cut from the resident factor -- and the split-k GEMM's test door ``gmb_blk_gemm_splitk``; added to version 16
 #: without a change of layout: the components of an additive model, ``gmb_num_terms``, the ``gmb_*_terms`` forms of the four
 #: prediction calls and ``gmb_predict_decompose``; likewise the leave-out predictions of the training rows, ``gmb_loo`` /
-#: ``gmb_leave_out``)
+#: ``gmb_leave_out``, and the averages of the posterior over groups of points, ``gmb_predict_groups`` / ``gmb_predict_groups_terms``
+#: with the host-only ``gmb_debug_group_tasks``)
 ABI_VERSION = 16
+
+#: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
+GROUP_CHUNK = 512
 
 
 def load_library():
@@ -756,6 +765,33 @@ class Engine:
                                             _ptr(full) if cov else None, max(m, 1), GMB_HOST), "gmb_leave_out")
         return (mean, var, full) if cov else (mean, var)
 
+    def predict_groups(self, Xs, offsets, weights=None, cov=False, terms=None):
+        """Weighted averages of the LATENT posterior over groups of the rows of ``Xs`` (``gmb_predict_groups``): ``(mean, var)``,
+        or ``(mean, var, cov)`` with ``cov=True`` -- ``mean_g = sum_{m in g} w_m E f(x_m)`` and ``cov = W C W^T`` with C the joint
+        posterior covariance of all the points (never formed: nothing of size M x M or M x N exists on the device).  Group g is
+        the rows ``offsets[g]:offsets[g + 1]`` (``offsets[0] == 0``, strictly increasing, ``offsets[-1] == len(Xs)``);
+        ``weights`` of any sign, ``None`` for a plain mean ``1 / |g|``.  No noise, no jitter, variances not clipped; ``cov`` is
+        exactly symmetric and its diagonal is ``var``.  ``terms`` selects terms of an additive model (:func:`terms_mask`).
+        ``ValueError`` for malformed offsets or weights that are not finite, ``MemoryError`` -- before anything is computed --
+        when the device cannot hold the request."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        offsets = np.ascontiguousarray(np.asarray(offsets).ravel(), dtype=np.int64)
+        M, G = Xs.shape[0], offsets.shape[0] - 1
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+            if weights.shape[0] != M:
+                raise ValueError(f"predict_groups: {weights.shape[0]} weights for {M} points")
+        mean = np.empty(max(G, 0), dtype=np.float64)
+        var = np.empty(max(G, 0), dtype=np.float64)
+        full = np.empty((G, G), dtype=np.float64) if cov and G > 0 else None
+        tail = (_ptr(Xs), M, Xs.shape[1] if Xs.ndim == 2 else 0, _ptr(offsets), G, _ptr(weights) if weights is not None else None,
+                _ptr(mean), _ptr(var), _ptr(full) if full is not None else None, max(G, 1), GMB_HOST)
+        if terms is not None:
+            self._check(self._lib.gmb_predict_groups_terms(self._h, terms_mask(terms), *tail), "gmb_predict_groups_terms")
+        else:
+            self._check(self._lib.gmb_predict_groups(self._h, *tail), "gmb_predict_groups")
+        return (mean, var, full) if cov else (mean, var)
+
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with
         respect to the test point, ``(M, D)`` each with the columns of :meth:`predict_grad` (``gmb_predict_with_grad``) -- one
@@ -1003,6 +1039,22 @@ def eval_task_list(nct: int, nrt: int, with_chol: bool = True, lag: int = 1, pai
     buf = (C.c_uint32 * n)()
     lib.gmb_debug_eval_tasks(int(nct), int(nrt), mode, int(lag), buf, n)
     return [(w >> 30, (w >> 15) & 0x7FFF, w & 0x7FFF) for w in buf]
+
+
+def group_tasks(offsets, chunk=None) -> list:
+    """[(group, first point, count), ...]: the tasks ``gmb_predict_groups`` runs over for these offsets (host-only), every count
+    at most ``chunk`` (``None``: :data:`GROUP_CHUNK`), in ascending group order, then ascending first point.  ``ValueError`` for
+    offsets that do not start at 0 or do not increase strictly."""
+    lib = load_library()
+    offsets = np.ascontiguousarray(np.asarray(offsets).ravel(), dtype=np.int64)
+    G = offsets.shape[0] - 1
+    chunk = 0 if chunk is None else int(chunk)
+    n = lib.gmb_debug_group_tasks(_ptr(offsets), G, chunk, None, 0) if G >= 1 else GMB_EINVAL
+    if n < 0:
+        raise ValueError("gmb_debug_group_tasks: offsets must start at 0 and increase strictly (no empty group)")
+    buf = np.empty((n, 3), dtype=np.int64)
+    lib.gmb_debug_group_tasks(_ptr(offsets), G, chunk, _ptr(buf), n)
+    return [tuple(int(v) for v in row) for row in buf]
 
 
 def chol_task_count(nct: int, nrt: int) -> int:

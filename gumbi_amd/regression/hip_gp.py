@@ -152,6 +152,7 @@ class HipGP(Regressor):
         self.gp_dict = None
         self.additive_levels = None  # {level: the engine's term selection} (build_model)
         self.component_cov = self.component_levels = None  # decompose_points: covariance between the components, and its axes
+        self.marginal_points = self.marginal_cov = self.average_labels = None  # predict_marginal's grid and joint covariance; predict_average's labels
         self.MAP = None
         self.trace = None
         self.engine = None
@@ -1109,6 +1110,180 @@ class HipGP(Regressor):
                 entry["unit"] = labels[k]
             out.append(entry)
         return out
+
+    # -- averages of the posterior over groups of points: marginal effects and contrasts ------------------------------------------
+    def predict_groups(self, points_array, offsets, weights=None, cov=False, additive_level="total"):
+        """Weighted averages of the LATENT posterior over groups of standardized points, in standardized units: ``(mean, var)``,
+        or ``(mean, var, cov)`` with ``cov=True`` -- one call into ``gmb_predict_groups`` against the factor left resident by
+        :meth:`find_MAP`.  Group g is the rows ``offsets[g]:offsets[g + 1]`` of ``points_array``; ``weights`` of any sign, ``None``
+        for the plain mean of each group.  The variance of an average is ``w^T C w`` with C the joint posterior covariance of the
+        group's points, NOT the mean of their variances; nothing of size M x M is formed to get it.
+
+        Averages are taken on the model's own standardized, transformed scale, like everything the GP computes: for a
+        log-normal output the natural-scale reading of an average is therefore a GEOMETRIC mean."""
+        terms = self._level_terms(additive_level)
+        if self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before predicting")
+        if self.distributed:
+            raise NotImplementedError("predict_groups: group averages are not built for distributed GPs (the factor is spread over ranks)")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError("predict_groups: group averages are not built for the Kronecker path (pass kronecker=False)")
+        return self.engine.predict_groups(np.asarray(points_array, dtype=np.float64), offsets, weights=weights, cov=cov, **terms)
+
+    def _one_output(self, output, what):
+        outputs = self._parse_prediction_output(output)
+        if len(outputs) != 1:
+            raise ValueError(f"{what} averages ONE output: pass output= one of {outputs}")
+        return outputs
+
+    def predict_average(self, points, groups=None, weights=None, output=None, joint=False, additive_level="total"):
+        """The posterior of the weighted mean of the latent function over groups of ``points`` (a 1-D parray): a uparray of
+        length G, one entry per distinct label of ``groups`` (an integer per point; ``None``: all points are one group) in
+        ascending label order; with ``joint=True`` ``(uparray, cov)``, ``cov`` the standardized G x G covariance between the
+        averages.  ``weights`` (one per point, any sign) default to ``1 / |g|``.  The points are sorted stably by label, so
+        points of one label keep their order.
+
+        Averages are taken on the model's standardized, transformed scale: for a log-normal output the natural-scale value
+        of the returned uparray is a geometric mean."""
+        self._level_terms(additive_level)
+        outputs = self._one_output(output, "predict_average")
+        points_array, _, _ = self._prepare_points_for_prediction(points, output=outputs)
+        M = points_array.shape[0]
+        labels = np.zeros(M, dtype=np.int64) if groups is None else np.asarray(groups).ravel()
+        if labels.shape[0] != M or not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError(f"predict_average: `groups` must hold one integer label per point ({M}), got {labels.shape[0]} of dtype {labels.dtype}")
+        order = np.argsort(labels, kind="stable")
+        uniq, counts = np.unique(labels, return_counts=True)
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64).ravel()
+            if w.shape[0] != M:
+                raise ValueError(f"predict_average: {w.shape[0]} weights for {M} points")
+            w = w[order]
+        res = self.predict_groups(points_array[order], offsets, weights=w, cov=joint, additive_level=additive_level)
+        self.average_labels = uniq
+        avg = self.uparray(outputs[0], res[0], res[1], stdzd=True)
+        return (avg, res[2]) if joint else avg
+
+    def _background_rows(self, what, over, outputs, n_background, seed, categorical_levels, overwritten):
+        """``(B, D)`` standardized model rows to average over: the fitted table's rows of the output (``over="data"``), a seeded
+        random subset of ``n_background`` of them, or the points of a parray.  ``overwritten``: dims the caller sets afterwards
+        (a parray need not carry them)."""
+        if isinstance(over, str):
+            if over != "data":
+                raise ValueError(f'{what}: `over` must be "data" or a parray of background points, got {over!r}')
+            rows = np.asarray(self.model.X, dtype=np.float64)[self._output_rows()[outputs[0]]].copy()
+            for dim, level in (categorical_levels or {}).items():
+                if dim not in self.categorical_dims or dim == self.out_col:
+                    raise ValueError(f'{what}: "{dim}" is not a categorical dimension of the model')
+                rows[:, self.dims.index(dim)] = self.stdzr.stdz(dim, float(self.categorical_coords[dim][level]))
+        else:
+            pts = np.atleast_1d(over)
+            fill = {dim: np.zeros(pts.shape) for dim in overwritten if dim not in pts.names}
+            if fill:
+                pts = pts.add_layers(stdzd=True, **fill)
+            if set(self.categorical_dims) - {self.out_col} - set(pts.names):
+                if categorical_levels is None:
+                    raise AttributeError("Must specify level for every categorical dimension")
+                pts = self.append_categorical_points(pts, {d: l for d, l in categorical_levels.items() if d not in pts.names})
+            rows, _, _ = self._prepare_points_for_prediction(pts, output=outputs)
+            rows = np.asarray(rows, dtype=np.float64)
+        if n_background is not None:
+            n_background = int(n_background)
+            if not 1 <= n_background <= len(rows):
+                raise ValueError(f"{what}: n_background must be in [1, {len(rows)}], got {n_background}")
+            rng = np.random.default_rng(self.seed if seed is None else seed)
+            rows = rows[np.sort(rng.choice(len(rows), n_background, replace=False))]
+        return rows
+
+    def marginal_design(self, dims, limits=None, resolution=50, over="data", n_background=None, seed=None, categorical_levels=None,
+                        output=None):
+        """What :meth:`predict_marginal` averages: a dict with ``"grid"`` (the parray of grid values, shaped like the grid),
+        ``"points_array"`` (G B standardized model rows: for every grid value, in the grid's row-major order, the B background
+        rows with ``dims`` overwritten), ``"offsets"`` (group g = grid value g) and ``"weights"`` (1 / B)."""
+        what = "predict_marginal"
+        dims = [dims] if isinstance(dims, str) else list(dims)
+        if not 1 <= len(dims) <= 2 or len(set(dims)) != len(dims) or any(d not in self.continuous_dims for d in dims):
+            raise ValueError(f"{what}: `dims` must be one or two of the continuous dimensions {list(self.continuous_dims)}, got {dims}")
+        outputs = self._one_output(output, what)
+        back = self._background_rows(what, over, outputs, n_background, seed, categorical_levels, dims)
+        defaults = self._default_grid_limits(set(dims))
+        if limits is None:
+            limits = defaults
+        else:
+            missing = set(dims) - set(limits.names)
+            if missing:
+                limits = limits.add_layers(**defaults[list(missing)].as_dict())
+        per_dim = self._grid_resolution(resolution)
+        order = [d for d in self.dims if d in dims]  # grid axes follow the model's dimension order
+        lz = limits.z
+        axes = [np.linspace(*lz[d + "_z"].values(), per_dim[d]) for d in order]
+        mesh = np.meshgrid(*axes, indexing="ij")
+        grid = self.parray(**{d: m for d, m in zip(order, mesh)}, stdzd=True)
+        G, B = mesh[0].size, back.shape[0]
+        points_array = np.tile(back, (G, 1))
+        for d, m in zip(order, mesh):
+            points_array[:, self.dims.index(d)] = np.repeat(m.ravel(), B)
+        return {"grid": grid, "points_array": points_array, "offsets": np.arange(G + 1, dtype=np.int64) * B,
+                "weights": np.full(G * B, 1.0 / B), "output": outputs[0]}
+
+    def predict_marginal(self, dims, limits=None, resolution=50, over="data", n_background=None, seed=None, categorical_levels=None,
+                         output=None, joint=False, additive_level="total"):
+        """The marginal effect of one or two continuous dimensions: for every value (or pair) of a regular grid over ``dims``,
+        the posterior of the latent function AVERAGED over a background of points -- the background's other coordinates with
+        ``dims`` overwritten, every background row weighing ``1 / B``.  Returns a uparray shaped like the grid.
+
+        ``over``: ``"data"`` (the fitted table's rows of the output, with their own categorical coordinates unless
+        ``categorical_levels`` pins some), or a 1-D parray of background points; ``n_background`` + ``seed`` take a seeded random
+        subset of the background.  ``limits`` (a parray with two values per dim) default to those :meth:`prepare_grid` would
+        take; ``resolution`` an int or a dict per dim.  The grid is left in :attr:`marginal_points`; with ``joint=True`` the
+        standardized G x G covariance between the grid values' averages (row-major over the grid) is left in
+        :attr:`marginal_cov`.  The variance of each average is that of the MEAN of the latent function over the background
+        (``w^T C w``), which is not the mean of the pointwise variances.
+
+        Averages are taken on the model's standardized, transformed scale: for a log-normal output the natural-scale reading
+        of a marginal effect is a geometric mean over the background."""
+        self._level_terms(additive_level)
+        design = self.marginal_design(dims, limits=limits, resolution=resolution, over=over, n_background=n_background, seed=seed,
+                                      categorical_levels=categorical_levels, output=output)
+        res = self.predict_groups(design["points_array"], design["offsets"], weights=design["weights"], cov=joint,
+                                  additive_level=additive_level)
+        shape = design["grid"].shape
+        self.marginal_points = design["grid"]
+        self.marginal_cov = res[2] if joint else None
+        return self.uparray(design["output"], res[0].reshape(shape), res[1].reshape(shape), stdzd=True)
+
+    def compare_levels(self, dim, a, b, over="data", n_background=None, seed=None, categorical_levels=None, output=None,
+                       additive_level="total"):
+        """Is level ``a`` of the categorical dimension ``dim`` different from level ``b``, averaged over a background?  ONE group
+        of 2 B points -- the background at level ``a`` with weights ``+1 / B``, at level ``b`` with ``-1 / B`` -- so the variance
+        holds the posterior covariance BETWEEN the two levels' averages.  Returns a dict, standardized: ``"mean"`` (the
+        difference a - b of the averages), ``"var"``, ``"z_score"`` ``= mean / sqrt(var)``, ``"levels"`` ``(a, b)`` and
+        ``"n_background"``.  ``over`` / ``n_background`` / ``seed`` / ``categorical_levels`` as :meth:`predict_marginal`.
+
+        The difference is taken on the model's standardized, transformed scale: for a log-normal output it is a log RATIO of
+        geometric means, in units of the output's standard deviation."""
+        what = "compare_levels"
+        self._level_terms(additive_level)
+        if dim not in self.categorical_dims or dim == self.out_col:
+            raise ValueError(f'{what}: "{dim}" is not a categorical dimension of the model')
+        for level in (a, b):
+            if level not in self.categorical_coords[dim]:
+                raise ValueError(f'{what}: "{level}" is not a level of "{dim}" ({list(self.categorical_coords[dim])})')
+        outputs = self._one_output(output, what)
+        if not isinstance(over, str) and dim not in np.atleast_1d(over).names:
+            over = np.atleast_1d(over).fill_with(**{dim: self.categorical_coords[dim][a]})
+        back = self._background_rows(what, over, outputs, n_background, seed, categorical_levels, [])
+        B, col = back.shape[0], self.dims.index(dim)
+        points_array = np.tile(back, (2, 1))
+        points_array[:B, col] = self.stdzr.stdz(dim, float(self.categorical_coords[dim][a]))
+        points_array[B:, col] = self.stdzr.stdz(dim, float(self.categorical_coords[dim][b]))
+        weights = np.concatenate([np.full(B, 1.0 / B), np.full(B, -1.0 / B)])
+        mean, var = self.predict_groups(points_array, np.array([0, 2 * B], dtype=np.int64), weights=weights, additive_level=additive_level)
+        with np.errstate(invalid="ignore", divide="ignore"):  # (a level against itself: the variance is rounding noise around 0)
+            z_score = float(mean[0] / np.sqrt(var[0]))
+        return {"mean": float(mean[0]), "var": float(var[0]), "z_score": z_score, "levels": (a, b), "n_background": B}
 
     def decompose_grid(self, output=None, categorical_levels=None):
         """:meth:`decompose_points` on the grid :meth:`prepare_grid` left behind, every level in the grid's shape."""

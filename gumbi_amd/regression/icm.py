@@ -270,6 +270,9 @@ class IcmEngine:
     def leave_out(self, idx, with_noise=True, cov=False):
         raise NotImplementedError("leave_out: leave-group-out predictions are not built for the Kronecker engine (pass kronecker=False)")
 
+    def predict_groups(self, Xs, offsets, weights=None, cov=False, terms=None):
+        raise NotImplementedError("predict_groups: group averages of the posterior are not built for the Kronecker engine (pass kronecker=False)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

@@ -432,6 +432,42 @@ int gmb_loo(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* me
 int gmb_leave_out(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_noise, double* mean, double* var,
                   double* cov, int64_t ldc, int32_t memspace);
 
+/* -- averages of the posterior over GROUPS of points: marginal effects and contrasts (added to version 16 without a change of
+ * layout) -------------------------------------------------------------------------------------------------------------------------
+ * fbar_g = sum_{m in g} w_m f(x_m), the weighted mean of the LATENT function over group g of the points (no noise, no jitter), is
+ * Gaussian; its variance is w_g^T C w_g with C the joint posterior covariance of the group's points -- not the mean of their
+ * variances.  With a_g = sum_{m in g} w_m k(x_m, X) (row g of A, G x N) and Q_gh = sum_{m in g} sum_{m' in h} w_m w_m' k(x_m, x_m'):
+ *   V_A = A L^-T        mean = V_A v        cov = Q - V_A V_A^T  (G x G)        var = diag(cov)
+ * A and Q are summed by fused kernels that write no covariance row: nothing of size M x M or M x N exists, the device holds
+ * O(M D) for the points, 128 x M doubles of one row block of Q's reduction, the task partials, and a prediction's workspace for
+ * G (not M) rows.  Beyond the reference.
+ *
+ * Xs: M x D row-major with leading dimension ldxs >= D, in `memspace`.  offsets: HOST memory always, G + 1 entries,
+ * offsets[0] == 0, strictly increasing, offsets[G] == M; group g is rows [offsets[g], offsets[g + 1]) of Xs.  weights: length M,
+ * in `memspace`, any sign (a contrast is one group with weights of both signs); NULL = 1 / |g|, a plain mean.  mean, var: length
+ * G.  cov: G x G row-major, leading dimension ldc >= G, both triangles, exactly symmetric, its diagonal equal to var; cov may be
+ * NULL (then only Q's diagonal is formed: sum |g|^2 pairs instead of M^2), var may be NULL when cov is not.  Variances are NOT
+ * clipped.  A group of one point with weight 1 is gmb_predict(with_noise = 0) at that point, to rounding.
+ *
+ * Readiness and refusals as gmb_predict_joint and the *_terms calls: a complete, unconsumed single-engine factor; GMB_EINVAL for
+ * distributed and capacity-mode engines, a consumed factor, no factorisation yet, terms == 0 or a bit at or beyond T, null
+ * required pointers, ldxs < D, ldc < G, G < 1, an empty group, offsets that do not start at 0, do not increase strictly or do not
+ * end at M, and a weight that is not finite -- the weights are checked on the host for HOST weights only; device-side weights
+ * are the caller's to vouch for -- with nothing launched and nothing written.  A request the device cannot hold returns
+ * GMB_ENOMEM with the bytes it needs in gmb_last_error before anything is launched or written.  State contract of the *_terms
+ * calls: the factor, v, both alphas, U, L^-1 and their flags and gmb_factor_valid are left as found; the joint state's second
+ * matrix is used, as gmb_leave_out uses it.  No atomics: the same bits call after call. */
+int gmb_predict_groups(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets, int64_t G,
+                       const double* weights, double* mean, double* var, double* cov, int64_t ldc, int32_t memspace);
+/* ... of the selected terms of an additive model (bit t of `terms` = term t, as the other *_terms calls) */
+int gmb_predict_groups_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets,
+                             int64_t G, const double* weights, double* mean, double* var, double* cov, int64_t ldc,
+                             int32_t memspace);
+/* Host only: the task list the kernels of gmb_predict_groups run over for these offsets -- (group, first point, count) triples,
+ * count <= chunk, ascending group, then ascending first point.  Returns the number of tasks and writes at most `cap` triples to
+ * `out` (may be NULL); chunk <= 0 = the engine's own (512).  GMB_EINVAL for malformed offsets (as above, with M = offsets[G]). */
+int64_t gmb_debug_group_tasks(const int64_t* offsets, int64_t G, int64_t chunk, int64_t* out, int64_t cap);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
