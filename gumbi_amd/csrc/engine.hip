@@ -48,6 +48,7 @@
 #include "predict_terms.hpp"
 #include "leave_out.hpp"
 #include "group_average.hpp"
+#include "predict_slope.hpp"
 
 using namespace gmb;
 
@@ -82,10 +83,12 @@ enum EvKind : int {
   // (ABI 16)
   EV_SPLITK = 16,             // the split-k product's launch pair (gemm_splitk.hpp): flags = slices
   EV_TERM_GRAM = 17,          // gmb_predict_decompose: the reduction's partial + final launches of one M-tile (k = terms)
-  EV_GROUP_COV = 18           // gmb_predict_groups: the partial launches of one reduction of one term (mt = column blocks, nt = tasks,
+  EV_GROUP_COV = 18,          // gmb_predict_groups: the partial launches of one reduction of one term (mt = column blocks, nt = tasks,
                               // flags = 0 the cross part A, 1 the prior part Q, 2 its diagonal only)
+  EV_SLOPE_COV = 19           // gmb_predict_slope: the derivative cross-covariance launch of the first selected term (mt x nt tiles
+                              // of 128 x 128 pairs, k = differentiable columns written per pair)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_GROUP_COV); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_SLOPE_COV); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -262,6 +265,29 @@ struct gmb_engine {
     }
   } ga;
   DevBuf<double> ga_part;   // [task][column] of one reduction
+  // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks: the chunked partials of an M-tile
+  // ([chunk][entry][Mt]), the prior curvature (Dc rows of Mt) and the results in the caller's layout (Mt x D twice, Mt x D x D
+  // when the covariance is asked for).  Reserved inside the call only.
+  struct SlopeWorkspace : RowGroup {
+    DevBuf<double> part, prior, mean, var, cov;
+    int64_t per_row = 0;  // chunks x entries the partials were sized for
+    bool has_cov = false;
+    int reserve(DevPool& pool, int64_t Mt, int64_t need, int D, bool with_cov) {
+      if (per_row < need || (with_cov && !has_cov)) stale();
+      return reserve_rows(Mt, [&] {
+        int rc;
+        per_row = 0;
+        has_cov = false;
+        if ((rc = part.renew(pool, need * Mt)) || (rc = prior.renew(pool, (int64_t)SLOPE_MAX_COLS * Mt)) ||
+            (rc = mean.renew(pool, Mt * (int64_t)D)) || (rc = var.renew(pool, Mt * (int64_t)D)))
+          return rc;
+        if (with_cov && (rc = cov.renew(pool, Mt * (int64_t)D * D))) return rc;
+        per_row = need;
+        has_cov = with_cov;
+        return 0;
+      });
+    }
+  } slope;
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
 
   // gradient workspace
@@ -581,7 +607,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_PREDICT_VGRAD_SOLVE:
       case EV_SPLITK:
       case EV_TERM_GRAM:
-      case EV_GROUP_COV: break;
+      case EV_GROUP_COV:
+      case EV_SLOPE_COV: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -1041,6 +1068,7 @@ void stale_sized_by_n(gmb_engine* e) {
   e->dpart.stale();
   e->pg.stale();
   e->ga.stale();
+  e->slope.stale();
   e->plan_N = -1;
 }
 
@@ -3670,6 +3698,194 @@ int decompose_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, in
   return GMB_OK;
 }
 
+// ---- the posterior of the slope (predict_slope.hpp) ---------------------------------------------------------------------------------
+
+template <int KIND, int NC>
+void launch_slope_cov_nc(gmb_engine* e, const SlopeCovArgs& a, dim3 grid, bool gen) {
+  if (gen) hipLaunchKernelGGL((slope_cross_cov_kernel<KIND, NC, true>), grid, dim3(256), 0, e->stream, a);
+  else hipLaunchKernelGGL((slope_cross_cov_kernel<KIND, NC, false>), grid, dim3(256), 0, e->stream, a);
+}
+
+template <int KIND>
+void launch_slope_cov_kind(gmb_engine* e, const SlopeCovArgs& a, dim3 grid, bool gen) {
+  switch (e->nc_pad) {
+    case 1: launch_slope_cov_nc<KIND, 1>(e, a, grid, gen); break;
+    case 2: launch_slope_cov_nc<KIND, 2>(e, a, grid, gen); break;
+    case 4: launch_slope_cov_nc<KIND, 4>(e, a, grid, gen); break;
+    case 8: launch_slope_cov_nc<KIND, 8>(e, a, grid, gen); break;
+    default: launch_slope_cov_nc<KIND, 16>(e, a, grid, gen); break;
+  }
+}
+
+// one term's derivative cross-covariance of an M-tile into the stacked dV (dispatched as launch_predict_grad, kinds 0 - 2 only:
+// gmb_predict_slope has refused the others)
+int launch_slope_cov(gmb_engine* e, const SlopeCovArgs& a) {
+  const dim3 grid((unsigned)(a.test.npad / SC_PTS), (unsigned)(e->Np / SC_PIECE));
+  const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
+  switch (a.p.kind) {
+    case GMB_EXPQUAD: launch_slope_cov_kind<0>(e, a, grid, gen); break;
+    case GMB_MATERN52: launch_slope_cov_kind<1>(e, a, grid, gen); break;
+    case GMB_MATERN32: launch_slope_cov_kind<2>(e, a, grid, gen); break;
+    default: return fail(e, GMB_EINVAL, "kernel kind %d has no derivative process", a.p.kind);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// the differentiable model columns of a selection (slope_plan.hpp): the selected terms' continuous and linear columns
+int slope_columns(gmb_engine* e, uint32_t terms, const char* what, SlopeColumns* cols) {
+  *cols = SlopeColumns{};
+  for (int t = 0; t < (int)e->terms.size(); ++t) {
+    if (!((terms >> t) & 1u)) continue;
+    const PrepArgs& pa = e->terms[t].pa;
+    for (int k = 0; k < pa.nc; k += pa.periodic ? 2 : 1)
+      for (int j = 0; j < k; j += pa.periodic ? 2 : 1)
+        if (pa.idx_cont[j] == pa.idx_cont[k])
+          return fail(e, GMB_EINVAL, "%s: column %d of X is two continuous dimensions of the kernel", what, pa.idx_cont[k]);
+    if (!slope_add_columns(*cols, pa.idx_cont, pa.nc) || !slope_add_columns(*cols, pa.idx_lin, pa.n_lin))
+      return fail(e, GMB_EINVAL, "%s: more than %d differentiable columns", what, SLOPE_MAX_COLS);
+  }
+  return GMB_OK;
+}
+
+// one M-tile of gmb_predict_slope: the Dc derivative cross-covariances stacked in dV, one solve, the reductions; results in the
+// slope workspace's mean / var / cov, in the caller's layout
+int slope_tile(gmb_engine* e, uint32_t terms, const SlopeColumns& cols, const double* Xs, int64_t mc, int64_t mpad, int64_t ldxs,
+               hipMemcpyKind in_kind, bool with_cov) {
+  int rc;
+  const int dc = cols.n;
+  const SlopeLayout lay{mpad, dc};
+  const int64_t ldz = lay.ldz();
+  HIP_TRY(e, hipMemcpy2DAsync(e->pw.dXs, e->D * sizeof(double), Xs, ldxs * sizeof(double), e->D * sizeof(double), mc, in_kind, e->stream));
+  const PointSet test{e->pw.txs, e->pw.txl, e->pw.tcat, mc, mpad};
+  const int t_first = first_term(terms);
+  rc = walk_terms(e, terms, [&](int t) -> int {
+    const gmb_engine::Term& tr = e->terms[t];
+    const PrepArgs& pa = tr.pa;
+    const bool first = t == t_first;
+    int r;
+    if ((r = prep_points(e, e->pw.dXs, mc, e->D, mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &pa))) return r;
+    SlopeCovArgs a{};
+    SlopePriorArgs pr{};
+    a.p = pr.p = tr.cp;
+    a.test = pr.test = test;
+    a.train = train_set(e);
+    a.out = e->pw.dV;
+    a.ldz = ldz;
+    a.accumulate = pr.accumulate = first ? 0 : 1;
+    a.periodic = pa.periodic;
+    a.nc = pa.nc;
+    a.dc = pr.dc = dc;
+    uint32_t covered = 0;
+    if (pa.periodic) {
+      for (int d = 0; 2 * d < pa.nc; ++d) {
+        const int c = cols.slot_of(pa.idx_cont[2 * d]);
+        const double w = M_PI * pa.two_over_T[d];  // 2 pi / T_d
+        a.slot[d] = c;
+        a.scale[d] = 2.0 * w;
+        pr.jj[c] = pa.inv_ls[2 * d] * pa.inv_ls[2 * d] * w * w;
+        covered |= 1u << c;
+      }
+    } else {
+      for (int k = 0; k < pa.nc; ++k) {
+        const int c = cols.slot_of(pa.idx_cont[k]);
+        a.slot[k] = c;
+        a.scale[k] = 2.0 * pa.inv_ls[k];
+        pr.jj[c] = pa.inv_ls[k] * pa.inv_ls[k];
+        covered |= 1u << c;
+      }
+    }
+    for (int l = 0; l < tr.cp.n_lin; ++l) {
+      const int c = cols.slot_of(pa.idx_lin[l]);
+      a.slot_lin[l] = c;
+      a.lin_over[l] = (covered >> c) & 1u;
+      pr.tl[c] = tr.cp.tau;
+    }
+    for (int l = 0; l < tr.cp.n_lin; ++l) covered |= 1u << a.slot_lin[l];
+    a.zero_slots = ~covered & ((1u << dc) - 1u);
+    if (first) ev_begin(e, e->stream, EV_SLOPE_COV, 0.0, (int)(mpad / TILE), (int)(e->Np / TILE), dc);
+    r = launch_slope_cov(e, a);
+    if (first) ev_end(e);
+    if (r) return r;
+    pr.prior = e->slope.prior;
+    hipLaunchKernelGGL(slope_prior_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, pr);
+    HIP_TRY(e, hipGetLastError());
+    return GMB_OK;
+  });
+  if (rc) return rc;
+  if ((rc = predict_solve_v(e, ldz, false))) return rc;  // all Dc blocks at once; neither dW nor U is touched
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const dim3 grid((unsigned)((mpad + 255) / 256), (unsigned)nchunk, (unsigned)slope_pair_blocks(dc, with_cov));
+  if (with_cov)
+    hipLaunchKernelGGL(slope_gram_partial_kernel<true>, grid, dim3(256), 0, e->stream, e->pw.dV, ldz, mpad, e->dv, e->N, dc, e->slope.part);
+  else
+    hipLaunchKernelGGL(slope_gram_partial_kernel<false>, grid, dim3(256), 0, e->stream, e->pw.dV, ldz, mpad, e->dv, e->N, dc, e->slope.part);
+  HIP_TRY(e, hipGetLastError());
+  // the model's other columns (categories, the output index) have slope 0 and variance 0
+  HIP_TRY(e, hipMemsetAsync(e->slope.mean, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->slope.var, 0, (size_t)(mc * e->D) * sizeof(double), e->stream));
+  if (with_cov) HIP_TRY(e, hipMemsetAsync(e->slope.cov, 0, (size_t)(mc * e->D * e->D) * sizeof(double), e->stream));
+  SlopeFinishArgs f{};
+  f.part = e->slope.part;
+  f.prior = e->slope.prior;
+  f.nchunk = nchunk;
+  f.dc = dc;
+  f.with_cov = with_cov ? 1 : 0;
+  f.D = e->D;
+  f.mpad = mpad;
+  f.mc = mc;
+  for (int c = 0; c < dc; ++c) f.col[c] = cols.col[c];
+  f.mean = e->slope.mean;
+  f.var = e->slope.var;
+  f.cov = with_cov ? (double*)e->slope.cov : nullptr;
+  hipLaunchKernelGGL(slope_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)slope_entries(dc, with_cov)), dim3(256), 0, e->stream, f);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+int predict_slope_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, double* dmean,
+                      double* dvar, int64_t ldg, double* dcov, int64_t ldc, int32_t memspace) {
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  uint32_t terms;
+  if ((rc = resolve_terms(e, sel, what, &terms))) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !dmean)) || ldxs < e->D || ldg < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/grad/ldg");
+  if (dcov && ldc < (int64_t)e->D * e->D) return fail(e, GMB_EINVAL, "%s: ldc = %lld is less than D x D = %d", what, (long long)ldc, e->D * e->D);
+  for (int t = 0; t < (int)e->terms.size(); ++t)
+    if (((terms >> t) & 1u) && e->terms[t].cp.kind != GMB_EXPQUAD && e->terms[t].cp.kind != GMB_MATERN52 && e->terms[t].cp.kind != GMB_MATERN32)
+      return fail(e, GMB_EINVAL, "%s: the process has no derivative: term %d is a %s kernel, which is not mean-square differentiable", what,
+                  t, e->terms[t].cp.kind == GMB_MATERN12 ? "Matern-1/2" : "Exponential");
+  SlopeColumns cols;
+  if ((rc = slope_columns(e, terms, what, &cols))) return rc;
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;  // the stacked V is always solved for, as in gmb_predict_decompose: neither dW nor U is touched
+  const bool with_cov = dcov != nullptr;
+  const int dc = cols.n;
+  const int64_t Mt = std::min<int64_t>(slope_tile_rows(predict_tile_rows(e, (int64_t)1 << 40), dc), round_up(M, TILE));
+  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  // every allocation before the first launch: Dc stacked blocks in the prediction's workspace, the partials, the results
+  if ((rc = predict_workspace(e, (int64_t)dc * Mt))) return rc;
+  if ((rc = e->slope.reserve(e->pool, Mt, (int64_t)nchunk * slope_entries(dc, with_cov), e->D, with_cov))) return rc;
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      if ((rc = slope_tile(e, terms, cols, Xs + m0 * ldxs, mc, round_up(mc, TILE), ldxs, ck.in, with_cov))) return rc;
+      if (hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->slope.mean, row, row, mc, ck.out, e->stream) != hipSuccess ||
+          (dvar && hipMemcpy2DAsync(dvar + m0 * ldg, ldg * sizeof(double), e->slope.var, row, row, mc, ck.out, e->stream) != hipSuccess) ||
+          (dcov && hipMemcpy2DAsync(dcov + m0 * ldc, ldc * sizeof(double), e->slope.cov, row * e->D, row * e->D, mc, ck.out, e->stream) !=
+                       hipSuccess))
+        return fail(e, GMB_EHIP, "%s: copying the results out failed", what);
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
 // ---- the selecting forms of the four prediction calls; `sel` null: every term, i.e. the calls without a selection ---------------
 
 int predict_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise,
@@ -4488,6 +4704,21 @@ int gmb_predict_groups(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs,
 int gmb_predict_groups_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets, int64_t G,
                              const double* weights, double* mean, double* var, double* cov, int64_t ldc, int32_t memspace) {
   return predict_groups_sel(e, &terms, "gmb_predict_groups_terms", Xs, M, ldxs, offsets, G, weights, mean, var, cov, ldc, memspace);
+}
+
+int gmb_predict_slope(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* dmean, double* dvar, int64_t ldg, double* dcov,
+                      int64_t ldc, int32_t memspace) {
+  return predict_slope_sel(e, nullptr, "gmb_predict_slope", Xs, M, ldxs, dmean, dvar, ldg, dcov, ldc, memspace);
+}
+
+int gmb_predict_slope_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, double* dmean, double* dvar,
+                            int64_t ldg, double* dcov, int64_t ldc, int32_t memspace) {
+  return predict_slope_sel(e, &terms, "gmb_predict_slope_terms", Xs, M, ldxs, dmean, dvar, ldg, dcov, ldc, memspace);
+}
+
+int64_t gmb_debug_slope_tile_rows(int64_t Np, int32_t Dc) {
+  if (Np < 1 || Dc < 1 || Dc > SLOPE_MAX_COLS) return GMB_EINVAL;
+  return slope_tile_rows(slope_predict_rows_max(Np), Dc);
 }
 
 int64_t gmb_debug_group_tasks(const int64_t* offsets, int64_t G, int64_t chunk, int64_t* out, int64_t cap) {

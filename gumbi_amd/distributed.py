@@ -389,6 +389,10 @@ class DistributedEngine:
         raise NotImplementedError("predict_grad: the posterior mean's gradient is not built for distributed GPs (gmb_predict_grad "
                                   "needs the complete factor of a single-engine factorisation)")
 
+    def predict_slope(self, Xs, cov=False, terms=None):
+        raise NotImplementedError("predict_slope: the slope's posterior is not built for distributed GPs (gmb_predict_slope "
+                                  "needs the complete factor of a single-engine factorisation)")
+
     def predict_with_grad(self, Xs, with_noise=True):
         raise NotImplementedError("predict_with_grad: the posterior's gradients are not built for distributed GPs "
                                   "(gmb_predict_with_grad needs the complete factor of a single-engine factorisation)")

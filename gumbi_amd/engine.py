@@ -355,6 +355,11 @@ _SIGNATURES = {
     "gmb_predict_groups_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "gmb_debug_group_tasks": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "gmb_predict_slope": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_int32]),
+    "gmb_predict_slope_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_debug_slope_tile_rows": (C.c_int64, [C.c_int64, C.c_int32]),
 }
 
 
@@ -401,7 +406,8 @@ def _preload_hip_runtime():
 #: without a change of layout: the components of an additive model, ``gmb_num_terms``, the ``gmb_*_terms`` forms of the four
 #: prediction calls and ``gmb_predict_decompose``; likewise the leave-out predictions of the training rows, ``gmb_loo`` /
 #: ``gmb_leave_out``, and the averages of the posterior over groups of points, ``gmb_predict_groups`` / ``gmb_predict_groups_terms``
-#: with the host-only ``gmb_debug_group_tasks``)
+#: with the host-only ``gmb_debug_group_tasks``, and the posterior of the slope, ``gmb_predict_slope`` / ``gmb_predict_slope_terms``
+#: with the host-only ``gmb_debug_slope_tile_rows``)
 ABI_VERSION = 16
 
 #: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
@@ -792,6 +798,27 @@ class Engine:
             self._check(self._lib.gmb_predict_groups(self._h, *tail), "gmb_predict_groups")
         return (mean, var, full) if cov else (mean, var)
 
+    def predict_slope(self, Xs, cov=False, terms=None):
+        """The posterior of the slope ``d f / d x*`` of the LATENT function at the rows of ``Xs`` (``gmb_predict_slope``):
+        ``(dmean, dvar)``, ``(M, D)`` each with the columns of :meth:`predict_grad`, or ``(dmean, dvar, dcov)`` with ``cov=True``,
+        ``dcov`` ``(M, D, D)`` the joint covariance of the partial derivatives at each point -- exactly symmetric, its diagonal
+        equal to ``dvar``.  ``dmean`` is the quantity :meth:`predict_grad` returns; ``dvar`` is the variance OF the slope, not
+        the slope of the variance (:meth:`predict_with_grad`).  Columns that carry no derivative are 0; variances are not
+        clipped.  ``terms`` selects terms of an additive model (:func:`terms_mask`).  ``ValueError`` for a Matern-1/2 or
+        Exponential kernel, whose process has no derivative.  Leaves the factor and everything a fit left beside it untouched."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M, D = Xs.shape[0], self.D
+        dmean, dvar = np.empty((M, D), dtype=np.float64), np.empty((M, D), dtype=np.float64)
+        dcov = np.empty((M, D, D), dtype=np.float64) if cov else None
+        tail = (_ptr(Xs), M, D, _ptr(dmean), _ptr(dvar), D, _ptr(dcov) if cov else None, D * D, GMB_HOST)
+        if terms is not None:
+            self._check(self._lib.gmb_predict_slope_terms(self._h, terms_mask(terms), *tail), "gmb_predict_slope_terms")
+        else:
+            self._check(self._lib.gmb_predict_slope(self._h, *tail), "gmb_predict_slope")
+        return (dmean, dvar, dcov) if cov else (dmean, dvar)
+
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with
         respect to the test point, ``(M, D)`` each with the columns of :meth:`predict_grad` (``gmb_predict_with_grad``) -- one
@@ -1055,6 +1082,15 @@ def group_tasks(offsets, chunk=None) -> list:
     buf = np.empty((n, 3), dtype=np.int64)
     lib.gmb_debug_group_tasks(_ptr(offsets), G, chunk, _ptr(buf), n)
     return [tuple(int(v) for v in row) for row in buf]
+
+
+def slope_tile_rows(Np: int, Dc: int) -> int:
+    """Test points per M-tile of ``gmb_predict_slope`` behind ``Np`` padded training points with ``Dc`` differentiable columns
+    (host-only)."""
+    n = int(load_library().gmb_debug_slope_tile_rows(int(Np), int(Dc)))
+    if n < 0:
+        raise ValueError(f"gmb_debug_slope_tile_rows: Np = {Np}, Dc = {Dc}")
+    return n
 
 
 def chol_task_count(nct: int, nrt: int) -> int:

@@ -35,6 +35,7 @@ import pandas as pd
 
 from ..aggregation import DataSet
 from ..arrays import ParameterArray as parray
+from ..arrays import UncertainArray
 from ..engine import KERNEL_KINDS, MAX_PERIODIC_DIMS, Engine, KernelSpec, resolve_kernel_name
 from . import icm
 from ..utils.gp_utils import get_ls_prior
@@ -153,6 +154,7 @@ class HipGP(Regressor):
         self.additive_levels = None  # {level: the engine's term selection} (build_model)
         self.component_cov = self.component_levels = None  # decompose_points: covariance between the components, and its axes
         self.marginal_points = self.marginal_cov = self.average_labels = None  # predict_marginal's grid and joint covariance; predict_average's labels
+        self.slope_cov = None  # predict_points_slope(joint=True): {output: (points, n_cont, n_cont)} covariance of the partial slopes
         self.MAP = None
         self.trace = None
         self.engine = None
@@ -600,6 +602,66 @@ class HipGP(Regressor):
         if self.categorical_dims:
             points = self.append_categorical_points(points, categorical_levels=categorical_levels)
         return self.predict_points_grad(points, output=output, norm=norm, additive_level=additive_level).reshape(self.grid_parray.shape)
+
+    # -- slope with uncertainty: the posterior of the derivative ----------------------------------------------------------------
+    def predict_slope(self, points_array, additive_level="total", cov=False):
+        """The posterior of the slope ``d f / d x`` of the latent function at standardized points: ``(dmean, dvar)``, ``(M, D)``
+        each with one column per model dimension in ``dims`` order (categorical columns and the output index: 0), or
+        ``(dmean, dvar, dcov)`` with ``cov=True``, ``dcov`` ``(M, D, D)`` the joint covariance of the partial derivatives at
+        each point -- one call into ``gmb_predict_slope`` against the factor left resident by :meth:`find_MAP`.  ``dmean`` is
+        :meth:`predict_grad`'s quantity; ``dvar`` is the variance OF the slope (the derivative of a GP is a GP), not the slope
+        of the variance.  Matern-1/2 and Exponential kernels have no mean-square derivative: ``ValueError``."""
+        terms = self._level_terms(additive_level)
+        if self.MAP is None or self.engine is None:
+            raise ValueError("The model must be fit (find_MAP) before predicting")
+        kind, _ = resolve_kernel_name(self.continuous_kernel)
+        if kind in ("Matern12", "Exponential"):
+            raise ValueError(f"predict_slope: a GP with the {self.continuous_kernel} kernel is not mean-square differentiable -- "
+                             "the process has no derivative (use ExpQuad, Matern52 or Matern32)")
+        return self.engine.predict_slope(np.asarray(points_array, dtype=np.float64), cov=cov, **terms)
+
+    def predict_points_slope(self, points, output=None, additive_level="total", joint=False):
+        """Slope of the fitted surface WITH its uncertainty at a 1-D parray of points: a dict with one ``UncertainArray``
+        ``δ[{y}]/δ[{x}]`` per output and continuous dimension (the layer names of :meth:`predict_points_grad`).  ``μ`` is the
+        standardized slope times ``σ_y / σ_x`` of the standardizer, ``σ2`` its standardized variance times ``(σ_y / σ_x)^2``:
+        is the effect of x different from zero here, where is the surface flat, which input matters most.  With
+        ``joint=True``, :attr:`slope_cov` is set too: ``{output: (points, n_cont, n_cont)}``, the covariance between the
+        partial slopes at each point in the same units, continuous dimensions in ``continuous_dims`` order.
+
+        As in :meth:`predict_points_grad`, everything is in the TRANSFORMED space: log (or logit) transforms of inputs or
+        outputs are NOT unwound.  The norm ``|∇|y`` gets no uncertainty here: the norm of a Gaussian vector is not Gaussian."""
+        output = self._parse_prediction_output(output)
+        points_array, tall, param_coords = self._prepare_points_for_prediction(points, output=output)
+        res = self.predict_slope(points_array, additive_level=additive_level, cov=joint)
+        task = tall[self.out_col].values().squeeze() if param_coords is not None else None
+        cols = [self.dims.index(x_var) for x_var in self.continuous_dims]
+        σx = np.array([np.sqrt(self.stdzr[x_var]["σ2"]) for x_var in self.continuous_dims])
+        slopes, covs = {}, {}
+        for i, y_var in enumerate(output):
+            rows = slice(None) if task is None else np.atleast_1d(task == param_coords[i])
+            σy = np.sqrt(self.stdzr[y_var]["σ2"])
+            for k, x_var in enumerate(self.continuous_dims):
+                name = f"δ[{y_var}]/δ[{x_var}]"
+                slopes[name] = UncertainArray(name, res[0][rows][:, cols[k]] * σy / σx[k], res[1][rows][:, cols[k]] * (σy / σx[k]) ** 2,
+                                              stdzr=self.stdzr)
+            if joint:
+                covs[y_var] = res[2][rows][:, cols][:, :, cols] * (σy**2 / np.outer(σx, σx))
+        self.slope_cov = covs if joint else None
+        return slopes
+
+    def predict_grid_slope(self, output=None, categorical_levels=None, additive_level="total", joint=False):
+        """:meth:`predict_points_slope` on the grid :meth:`prepare_grid` left behind, every array in the grid's shape
+        (:attr:`slope_cov`: the grid's shape, then ``(n_cont, n_cont)``)."""
+        if self.grid_points is None:
+            raise ValueError("Grid must first be specified with `prepare_grid`")
+        points = self.grid_points
+        if self.categorical_dims:
+            points = self.append_categorical_points(points, categorical_levels=categorical_levels)
+        slopes = self.predict_points_slope(points, output=output, additive_level=additive_level, joint=joint)
+        shape = self.grid_parray.shape
+        if joint:
+            self.slope_cov = {y: c.reshape(*shape, *c.shape[1:]) for y, c in self.slope_cov.items()}
+        return {name: ua.reshape(shape) for name, ua in slopes.items()}
 
     @staticmethod
     def _get_pgrad_norm(pgrad):

@@ -317,6 +317,33 @@ class IcmEngine:
         grad[:, :-1] *= np.sqrt(Dd[task])[:, None]
         return grad
 
+    def predict_slope(self, Xs, cov=False, terms=None):
+        """The posterior of the slope at the rows of ``Xs`` (``Engine.predict_slope``): the Kronecker posterior is the fixed
+        combination of the P independent systems' of :meth:`predict`, so the slope's mean is ``sqrt(Dd) sum_p Q_p dmean_p`` (as
+        :meth:`predict_grad`) and its covariance ``Dd sum_p Q_p^2 Cov_p``; the output column gets 0."""
+        _no_terms(terms, "predict_slope(terms=...)")
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        D = self.spec.D
+        if Xs.ndim != 2 or Xs.shape[1] != D:
+            raise ValueError(f"points_array must be (M, {D}), got {Xs.shape}")
+        st = self._decompose()
+        M = len(Xs)
+        dmean, dvar, dcov = np.zeros((M, D)), np.zeros((M, D)), np.zeros((M, D, D))
+        if M > 0:
+            task = Xs[:, -1].astype(np.int64)
+            x = np.ascontiguousarray(Xs[:, :-1])
+            Q, Dd = st["Q"], st["Dd"]
+            for p in range(self.P):
+                res = self._load(p, st).predict_slope(x, cov=cov)
+                dmean[:, :-1] += Q[task, p][:, None] * res[0]
+                dvar[:, :-1] += (Q[task, p] ** 2)[:, None] * res[1]
+                if cov:
+                    dcov[:, :-1, :-1] += (Q[task, p] ** 2)[:, None, None] * res[2]
+            dmean[:, :-1] *= np.sqrt(Dd[task])[:, None]
+            dvar[:, :-1] *= Dd[task][:, None]
+            dcov[:, :-1, :-1] *= Dd[task][:, None, None]
+        return (dmean, dvar, dcov) if cov else (dmean, dvar)
+
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs`` (``Engine.predict_with_grad``): mean and variance are the fixed
         combinations of the P systems' of :meth:`predict` -- ``sqrt(Dd) sum_p Q_p mu_p`` and ``Dd sum_p Q_p^2 v_p`` -- so their

@@ -468,6 +468,37 @@ int gmb_predict_groups_terms(gmb_engine* e, uint32_t terms, const double* Xs, in
  * `out` (may be NULL); chunk <= 0 = the engine's own (512).  GMB_EINVAL for malformed offsets (as above, with M = offsets[G]). */
 int64_t gmb_debug_group_tasks(const int64_t* offsets, int64_t G, int64_t chunk, int64_t* out, int64_t cap);
 
+/* ---- the posterior of the slope d f / d x* : mean, variance and covariance of the partial derivatives (ABI stays 16: new
+ * functions only, no change of layout) --------------------------------------------------------------------------------------------
+ * The derivative of a GP with a mean-square differentiable kernel is a GP.  Per test point x* (LATENT function: no noise, no
+ * jitter) and differentiable model column d, with b_d[n] = d k(x*, x_n) / d x*_d and V_d = b_d L^-T:
+ *   dmean_d = V_d v  (= d mu / d x*_d, the quantity gmb_predict_grad returns, by another route)
+ *   dcov_de = P_de - V_d V_e,     dvar_d = dcov_dd
+ *   P_de    = delta_de sum_t F_t(x*, x*) [ -2 eta_t^2 f'_t(0) J_d^2 + tau_t 1{d linear in t} ]
+ * J_d^2 = 1 / ls_d^2 for a stationary kernel (P = eta^2 / ls^2 for ExpQuad, 5 eta^2 / 3 ls^2 for Matern-5/2, 3 eta^2 / ls^2 for
+ * Matern-3/2) and w_d^2 (2 pi / T_d)^2 for the periodic forms.  gmb_predict_with_grad's dvar is d sigma^2 / d x*: another quantity.
+ *
+ * Xs: M x D row-major, leading dimension ldxs >= D, in `memspace`.  dmean, dvar: M x D row-major with leading dimension ldg >= D,
+ * every model column; dvar may be NULL.  dcov: NULL, or point m's D x D row-major block at dcov + m * ldc, ldc >= D * D; exactly
+ * symmetric, its diagonal equal to dvar.  Rows and columns of model columns that are not differentiable (categories, the output
+ * index) are written 0.  Variances are NOT clipped.  What lies between the rows of a strided result is left untouched.
+ *
+ * A model whose selected terms include a Matern-1/2 or Exponential kernel (<kind>+Periodic with such a kind included) is not
+ * mean-square differentiable: GMB_EINVAL, "the process has no derivative", nothing launched.  Readiness and the other refusals
+ * are gmb_predict_grad's: a complete, unconsumed single-engine factor; GMB_EINVAL for distributed and capacity-mode engines, no
+ * factorisation yet, M < 0, null Xs / dmean, ldxs < D, ldg < D, terms == 0 or a bit at or beyond T (and ldc < D * D).  V is always
+ * solved for (as gmb_predict_decompose): the factor, v, both alphas, U, L^-1, their flags and the joint state are left as found,
+ * the resident training points hold term 0's preparation on return, and a gmb_predict behind a fit keeps its form and its
+ * bits.  No atomics: the same bits call after call. */
+int gmb_predict_slope(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* dmean, double* dvar, int64_t ldg,
+                      double* dcov, int64_t ldc, int32_t memspace);
+/* ... of the selected terms of an additive model (bit t of `terms` = term t, as the other *_terms calls) */
+int gmb_predict_slope_terms(gmb_engine* e, uint32_t terms, const double* Xs, int64_t M, int64_t ldxs, double* dmean, double* dvar,
+                            int64_t ldg, double* dcov, int64_t ldc, int32_t memspace);
+/* Host only: test points per M-tile of gmb_predict_slope behind Np (padded) training points with Dc differentiable columns --
+ * max(128, mt_max / Dc / 128 * 128), mt_max a prediction's largest M-tile.  GMB_EINVAL for Np < 1 or Dc outside 1 .. 24. */
+int64_t gmb_debug_slope_tile_rows(int64_t Np, int32_t Dc);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
