@@ -21,15 +21,13 @@
 #include <stdint.h>
 
 #include "gemm_f64.hpp"
+#include "workspace_sizes.hpp"  // MAX_TABS, MAX_LIN, RED_CHUNK
 
 #ifndef GMB_KB_PROBE
 #define GMB_KB_PROBE 0  // 1 / 2: measurement probes of the interior covariance tiles (stores only / arithmetic only)
 #endif
 
 namespace gmb {
-
-constexpr int MAX_TABS = 5;     // GMB_MAX_COREG + output coregion
-constexpr int MAX_LIN = 8;      // GMB_MAX_LIN
 
 // Pre-processed coordinates of a point set (structure-of-arrays, padded length `npad`):
 //   xs[k*npad + i]  continuous dims scaled by 1/ls_k (zero for padded dims / points), k < nc_pad;
@@ -754,8 +752,6 @@ __global__ void kss_kernel(KssArgs a) {
 //   part_mu[c][m] = sum_{i in chunk c} V[m + i*ldz] * v[i],  part_s[c][m] = sum V^2
 // then  mean = sum_c part_mu,  var = kss - sum_c part_s   (deterministic two-stage sum)
 // ---------------------------------------------------------------------------------------------
-constexpr int RED_CHUNK = 256;
-
 __global__ __launch_bounds__(256) void predict_partial_kernel(const double* __restrict__ V,
                                                               int64_t ldz,
                                                               const double* __restrict__ v,

@@ -5,6 +5,8 @@
 //   DevBuf<T>    pointer + element capacity of one block of a pool; converts to T*, so use sites read as with a bare pointer
 //   ScopedBuf<T> a DevBuf that gives its block back at scope exit unless a DevBuf adopted it
 //   RowGroup     the shared row count of several buffers that are only ever sized together
+//   Budget       what a list of buffers and row groups takes, and what of it is still to be allocated: a call measures with it
+//   Reserver     ... and then allocates, walking the same list
 //
 // No engine types, and no HIP beyond the two allocator hooks below: a program that defines GMB_DEVBUF_OWN_HOOKS supplies its own
 // pair, which is how tools/device_buffers_check.cpp runs this very header on host memory under the sanitizers.
@@ -138,6 +140,36 @@ struct RowGroup {
     if (!rc) rows = need;
     return rc;
   }
+};
+
+// A call writes the list of its buffers once, as a function of a visitor, and walks it twice: with a Budget, to measure the request
+// against the device BEFORE anything is touched, then with a Reserver.  Both answer "go on?".  In double: the element
+// counts of a request that has to be refused can overflow int64_t.  A row group says what it takes through bytes(rows, args...)
+// and held(args...) (workspaces.hpp).
+struct Budget {
+  double total = 0.0;  // bytes the listed buffers take at the sizes asked for
+  double fresh = 0.0;  // bytes still to be allocated; a stale buffer or group holds nothing, so it counts in full
+  template <typename T>
+  bool buf(const DevBuf<T>& b, double need) {
+    total += sizeof(T) * need;
+    if ((double)b.cap < need) fresh += sizeof(T) * (need - (double)b.cap);
+    return true;
+  }
+  template <typename Group, typename... Args>
+  bool rows(Group& g, double need, Args... args) {
+    const double have = (double)g.held(args...);
+    total += g.bytes(need, args...);
+    if (have < need) fresh += g.bytes(need, args...) - g.bytes(have, args...);
+    return true;
+  }
+};
+struct Reserver {
+  DevPool& pool;
+  int rc = 0;  // the first failure: the walk stops there
+  template <typename T>
+  bool buf(DevBuf<T>& b, double need) { return !(rc = b.reserve(pool, (int64_t)need)); }
+  template <typename Group, typename... Args>
+  bool rows(Group& g, double need, Args... args) { return !(rc = g.reserve(pool, (int64_t)need, args...)); }
 };
 
 }  // namespace gmb

@@ -31,6 +31,7 @@
 
 #include "../../include/gumbi_hip.h"
 #include "device_buffers.hpp"
+#include "workspaces.hpp"
 #include "term_walk.hpp"
 #include "factor_state.hpp"
 #include "eval_plan.hpp"
@@ -149,17 +150,7 @@ struct gmb_engine {
   int nc_pad = 1;
   int periodic = 0;        // gmb_set_periodic: 0 off, 1 <kind>+Periodic, 2 pm.gp.cov.Periodic; the prepared columns are then 2 n_cont
   double periods[8] = {};  // T_d per continuous dimension (standardized units)
-  struct PreparedPoints : RowGroup {  // the training points as the covariance kernels read them (SoA, stride = rows)
-    DevBuf<double> xs, xl;
-    DevBuf<int32_t> cat;
-    int reserve(DevPool& pool, int64_t n) {
-      return reserve_rows(n, [&] {
-        int rc;
-        if ((rc = xs.renew(pool, (int64_t)17 * n)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * n))) return rc;
-        return cat.renew(pool, (int64_t)MAX_TABS * n);
-      });
-    }
-  } pts;
+  PreparedPoints pts;  // the training points as the covariance kernels read them (SoA, stride = rows)
   DevBuf<double> dtabs, dnoise;
   // The model's covariance terms (apply_theta; empty until gmb_set_theta): terms[0] is the global kernel -- the ONLY copy of its
   // parameters, and the preparation the resident points hold between calls -- and an additive model adds term 1 + j, the kernel
@@ -184,110 +175,25 @@ struct gmb_engine {
   int64_t notpd = -1;
   double logdet = 0.0, vnorm2 = 0.0;
 
-  // predict workspace: what an M-tile of Mt rows needs (predict_workspace)
-  struct PredictWorkspace : RowGroup {
-    DevBuf<double> dV, dXs, txs, txl;
-    DevBuf<int32_t> tcat;
-    DevBuf<double> dkss, dmean, dvar;
-    int reserve(DevPool& pool, int64_t Mt, int64_t Np, int D) {
-      return reserve_rows(Mt, [&] {
-        int rc;
-        if ((rc = dV.renew(pool, Mt * Np)) || (rc = dXs.renew(pool, Mt * (int64_t)D)) || (rc = txs.renew(pool, (int64_t)17 * Mt)) ||
-            (rc = txl.renew(pool, (int64_t)MAX_LIN * Mt)) || (rc = tcat.renew(pool, (int64_t)MAX_TABS * Mt)) ||
-            (rc = dkss.renew(pool, Mt)) || (rc = dmean.renew(pool, Mt)))
-          return rc;
-        return dvar.renew(pool, Mt);
-      });
-    }
-  } pw;
+  // the workspaces (workspaces.hpp: each writes its members once, for the allocation and for the guards' measurement alike)
+  PredictWorkspace pw;     // what an M-tile of Mt rows needs (predict_workspace)
   // GEMM-form prediction (predict_form.hpp): U = L^-T behind a tile-path gradient sits in the factor buffer's upper triangle +
   // dUdiag; the first prediction transposes it into dW's lower triangle, every one until the next factorisation is one GEMM into dV2
   int predict_form = -1;   // -1 = GEMM form whenever U is there; 0 = always the triangular solve; 1 = as -1 (explicit)
-  struct GemmFormWorkspace : RowGroup {
-    DevBuf<double> dV2;    // Np x Mt: the solved cross-covariance with the TRAINING index fastest
-    int reserve(DevPool& pool, int64_t Mt, int64_t Np) {
-      return reserve_rows(Mt, [&] { return dV2.renew(pool, Mt * Np); });
-    }
-  } pw2;
+  GemmFormWorkspace pw2;   // its second V
   JointState jt;           // the second matrix of gmb_predict_joint / gmb_draw_joint (joint_predict.hpp)
-  DevBuf<double> dpart;    // the prediction's chunked partial sums (2 x chunks x pw.rows)
+  DevBuf<double> dpart;    // the prediction's chunked partial sums (2 x chunks x the rows asked for: predict_buffers)
   // gmb_predict_grad (predict_grad.hpp): workspaces of its own -- a prediction's (Mt x Np and friends) stay as they are --
   // and alpha by back substitution for the states in which no gradient evaluation left one
-  struct PredictGradWorkspace : RowGroup {
-    DevBuf<double> Xs, xs, xl;
-    DevBuf<int32_t> cat;
-    DevBuf<double> grad;
-    int reserve(DevPool& pool, int64_t Mt, int D) {
-      return reserve_rows(Mt, [&] {
-        int rc;
-        if ((rc = Xs.renew(pool, Mt * (int64_t)D)) || (rc = xs.renew(pool, (int64_t)17 * Mt)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * Mt)) ||
-            (rc = cat.renew(pool, (int64_t)MAX_TABS * Mt)))
-          return rc;
-        return grad.renew(pool, Mt * (int64_t)D);
-      });
-    }
-  } pg;
+  PredictGradWorkspace pg;
   DevBuf<double> pg_part;
   DevBuf<double> dalpha_bs;  // Np: alpha, then Np: the running right-hand side
   // gmb_predict_with_grad: the variance gradient of an M-tile (its partials are a second set in pg_part)
   DevBuf<double> vg_grad;
-  // gmb_predict_decompose (predict_terms.hpp), beside a prediction's workspace of T stacked blocks: the chunked partials of an
-  // M-tile ([chunk][entry][Mt]) and its results (T means, T (T + 1) / 2 covariance rows, the noise: rows of Mt)
-  struct TermsWorkspace : RowGroup {
-    DevBuf<double> part, out;
-    int64_t per_row = 0;  // chunks x entries the rows were sized for
-    int reserve(DevPool& pool, int64_t Mt, int nchunk, int nt) {
-      const int64_t need = (int64_t)nchunk * tg_entries(nt);
-      if (per_row < need) stale();
-      return reserve_rows(Mt, [&] {
-        int rc;
-        per_row = 0;
-        if ((rc = part.renew(pool, need * Mt))) return rc;
-        if ((rc = out.renew(pool, (int64_t)(tg_entries(TG_MAX_TERMS) + 1) * Mt))) return rc;
-        per_row = need;
-        return 0;
-      });
-    }
-  } tg;
-  // gmb_predict_groups (group_average.hpp), sized by the call's M points and by nothing of size M x N: the raw and the prepared
-  // points, their weights and one row block of R (128 x M); beside them the task partials and the call's index arrays
-  struct GroupWorkspace : RowGroup {
-    DevBuf<double> Xs, xs, xl, w, R;
-    DevBuf<int32_t> cat;
-    int reserve(DevPool& pool, int64_t Mp, int D) {
-      return reserve_rows(Mp, [&] {
-        int rc;
-        if ((rc = Xs.renew(pool, Mp * (int64_t)D)) || (rc = xs.renew(pool, (int64_t)17 * Mp)) || (rc = xl.renew(pool, (int64_t)MAX_LIN * Mp)) ||
-            (rc = w.renew(pool, Mp)) || (rc = R.renew(pool, (int64_t)GA_ROWS * Mp)))
-          return rc;
-        return cat.renew(pool, (int64_t)MAX_TABS * Mp);
-      });
-    }
-  } ga;
+  TermsWorkspace tg;        // gmb_predict_decompose (predict_terms.hpp), beside a prediction's workspace of T stacked blocks
+  GroupWorkspace ga;        // gmb_predict_groups (group_average.hpp); beside it the task partials and the call's index arrays
   DevBuf<double> ga_part;   // [task][column] of one reduction
-  // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks: the chunked partials of an M-tile
-  // ([chunk][entry][Mt]), the prior curvature (Dc rows of Mt) and the results in the caller's layout (Mt x D twice, Mt x D x D
-  // when the covariance is asked for).  Reserved inside the call only.
-  struct SlopeWorkspace : RowGroup {
-    DevBuf<double> part, prior, mean, var, cov;
-    int64_t per_row = 0;  // chunks x entries the partials were sized for
-    bool has_cov = false;
-    int reserve(DevPool& pool, int64_t Mt, int64_t need, int D, bool with_cov) {
-      if (per_row < need || (with_cov && !has_cov)) stale();
-      return reserve_rows(Mt, [&] {
-        int rc;
-        per_row = 0;
-        has_cov = false;
-        if ((rc = part.renew(pool, need * Mt)) || (rc = prior.renew(pool, (int64_t)SLOPE_MAX_COLS * Mt)) ||
-            (rc = mean.renew(pool, Mt * (int64_t)D)) || (rc = var.renew(pool, Mt * (int64_t)D)))
-          return rc;
-        if (with_cov && (rc = cov.renew(pool, Mt * (int64_t)D * D))) return rc;
-        per_row = need;
-        has_cov = with_cov;
-        return 0;
-      });
-    }
-  } slope;
+  SlopeWorkspace slope;     // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
 
   // gradient workspace
@@ -3122,10 +3028,17 @@ int64_t predict_tile_rows(const gmb_engine* e, int64_t M) {
 // prediction: a rank that ran out of memory here would otherwise leave gmb_predict before the solve hook, i.e. without
 // issuing the pass's all-gathers, with its peers blocked inside them.
 int predict_workspace(gmb_engine* e, int64_t Mt) {
-  int rc;
-  if ((rc = e->pw.reserve(e->pool, Mt, e->Np, e->D))) return rc;
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
-  return e->dpart.reserve(e->pool, (int64_t)2 * nchunk * e->pw.rows);
+  Reserver take{e->pool};
+  predict_buffers(*e, (double)Mt, take);
+  return take.rc;
+}
+
+// what a guarded call holds its Budget against: the bytes the device has free now
+int device_free_bytes(gmb_engine* e, double* free_bytes) {
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+  *free_bytes = (double)free_b;
+  return GMB_OK;
 }
 
 // ---- the pieces of one M-tile of a prediction, shared by gmb_predict (tile by tile) and the joint posterior (all M rows at
@@ -3136,9 +3049,6 @@ int predict_workspace(gmb_engine* e, int64_t Mt) {
 bool predict_takes_gemm_form(const gmb_engine* e) {
   return !e->solve_hook && e->predict_form != 0 && e->fs.gemm_form_ready() && e->dW && e->dUdiag && e->dW.cap >= e->Np * e->Np;
 }
-
-// ... and the second Mt x Np buffer that form needs
-int predict_gemm_form_workspace(gmb_engine* e, int64_t Mt) { return e->pw2.reserve(e->pool, Mt, e->Np); }
 
 // mc test points (Xs: their first row) -> prepared points in txs / txl / tcat, the cross-covariance K(X*, X) in dV (mpad x Np,
 // test index fastest) and the prior variances (+ noise) in dkss
@@ -3240,7 +3150,7 @@ int predict_solve_v(gmb_engine* e, int64_t mpad, bool use_gemm_form) {
 
 // mean and variance of the tile's mc points into dmean / dvar
 int predict_reduce(gmb_engine* e, int64_t mc, int64_t mpad, bool gemm_form) {
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   if (gemm_form) {
     // variance from Vt, mean = K(X*, X) alpha from the cross-covariance, which the GEMM left in dV (predict_form.hpp)
     hipLaunchKernelGGL(predict_rows_kernel, dim3((unsigned)mc), dim3(256), 0, e->stream, e->pw2.dV2, e->Np, e->N, e->pw.dkss, e->pw.dvar);
@@ -3277,43 +3187,41 @@ int joint_ready(gmb_engine* e, const char* what) {
   return GMB_OK;
 }
 
-// Every buffer of a joint prediction at M points (+ `stage` doubles of device staging for host-side arguments), allocated
-// before anything is launched.  V is held whole -- the rank-N update needs every pair of its row tiles -- so a request is
-// first measured against the device: one that cannot fit is refused with the bytes it needs, and nothing has been touched.
-int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, double stage) {
+// What a joint posterior at M points (mr x mp in the bordered layout) gets AFTER its guard's check: the small fixed buffers of the
+// factorisation of C -- sub-block inverses, scalar block, zero row -- are in no budget, O(M) beside the O(M N + M^2) measured.
+int joint_fixed_buffers(gmb_engine* e, int64_t M, int64_t mr, int64_t mp) {
   JointState& jt = e->jt;
-  const double Mr = (double)round_up(M + 1, TILE), Mp = (double)round_up(M, TILE), Np = (double)e->Np;
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
-  const double per_row = 8.0 * (Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;  // predict_workspace, per row of the M-tile
-  const double v_bytes = 8.0 * Mr * Np, c_bytes = 8.0 * Mr * Mp, stage_bytes = 8.0 * stage;
-  const double total = per_row * Mr + 16.0 * nchunk * Mr + (gemm_form ? v_bytes : 0.0) + c_bytes + stage_bytes;
-  // what is still to be allocated, less what those allocations release first
-  double fresh = 0.0;
-  if ((double)e->pw.rows < Mr) fresh += per_row * (Mr - (double)e->pw.rows);
-  if ((double)e->dpart.cap < 2.0 * nchunk * Mr) fresh += 8.0 * (2.0 * nchunk * Mr - (double)e->dpart.cap);
-  if (gemm_form && (double)e->pw2.rows < Mr) fresh += 8.0 * Np * (Mr - (double)e->pw2.rows);
-  if ((double)jt.dC.cap < Mr * Mp) fresh += 8.0 * (Mr * Mp - (double)jt.dC.cap);
-  if ((double)jt.dstage.cap < stage) fresh += 8.0 * (stage - (double)jt.dstage.cap);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
-  if (fresh > (double)free_b || Mr > 1073741824.0)
-    return fail(e, GMB_ENOMEM, "%s: M = %lld behind N = %lld needs %.0f bytes on the device (V: %.0f%s, C: %.0f), %.0f more than it holds "
-                               "for the engine now; %.0f bytes are free -- nothing was computed",
-                what, (long long)M, (long long)e->N, total, v_bytes, gemm_form ? " twice" : "", c_bytes, fresh, (double)free_b);
-  const int64_t mr = round_up(M + 1, TILE), mp = round_up(M, TILE);
   int rc;
-  if ((rc = predict_workspace(e, mr))) return rc;
-  if (gemm_form && (rc = predict_gemm_form_workspace(e, mr))) return rc;
-  if ((rc = jt.dC.reserve(e->pool, mr * mp))) return rc;
   if ((rc = jt.dDinv16.reserve(e->pool, (mp / TILE) * (int64_t)8 * 256))) return rc;
   if ((rc = jt.dscal.reserve(e->pool, (int64_t)SCAL_GACC_AT))) return rc;
   if (jt.dzero.cap < mr) {
     if ((rc = jt.dzero.reserve(e->pool, mr))) return rc;
     HIP_TRY(e, hipMemsetAsync(jt.dzero, 0, (size_t)jt.dzero.cap * sizeof(double), e->stream));
   }
-  if (stage > 0.0 && (rc = jt.dstage.reserve(e->pool, (int64_t)stage))) return rc;
   jt.M = M, jt.Mp = mp, jt.Mr = mr;
   return GMB_OK;
+}
+
+// Every buffer of a joint prediction at M points (+ `stage` doubles of device staging for host-side arguments), allocated
+// before anything is launched.  V is held whole -- the rank-N update needs every pair of its row tiles -- so a request is
+// first measured against the device: one that cannot fit is refused with the bytes it needs, and nothing has been touched.
+// The buffers are joint_buffers' list (workspaces.hpp), walked by the budget and then by the allocation.
+int joint_workspace(gmb_engine* e, const char* what, int64_t M, bool gemm_form, double stage) {
+  const int64_t mr = round_up(M + 1, TILE), mp = round_up(M, TILE);
+  const double Mr = (double)mr, Mp = (double)mp;
+  Budget need;
+  joint_buffers(*e, Mr, Mp, gemm_form, stage, need);
+  double free_b;
+  int rc;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
+  if (need.fresh > free_b || Mr > 1073741824.0)  // (V's bytes: what the product form's second V takes)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld behind N = %lld needs %.0f bytes on the device (V: %.0f%s, C: %.0f), %.0f more than it holds "
+                               "for the engine now; %.0f bytes are free -- nothing was computed",
+                what, (long long)M, (long long)e->N, need.total, e->pw2.bytes(Mr, e->Np), gemm_form ? " twice" : "",
+                sizeof(double) * joint_matrix_elems(Mr, Mp), need.fresh, free_b);
+  Reserver take{e->pool};
+  joint_buffers(*e, Mr, Mp, gemm_form, stage, take);
+  return take.rc ? take.rc : joint_fixed_buffers(e, M, mr, mp);
 }
 
 // The posterior mean of all M points into dmean and the lower-triangle tiles of
@@ -3680,7 +3588,7 @@ int decompose_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, in
   });
   if (rc) return rc;
   if ((rc = predict_solve_v(e, ldz, false))) return rc;  // all T blocks at once; neither dW nor U is touched
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   const dim3 grid((unsigned)((mpad + 255) / 256), (unsigned)nchunk);
   ev_begin(e, e->stream, EV_TERM_GRAM, 0.0, (int)(mpad / TILE), nchunk, T);
   switch (T) {
@@ -3814,7 +3722,7 @@ int slope_tile(gmb_engine* e, uint32_t terms, const SlopeColumns& cols, const do
   });
   if (rc) return rc;
   if ((rc = predict_solve_v(e, ldz, false))) return rc;  // all Dc blocks at once; neither dW nor U is touched
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   const dim3 grid((unsigned)((mpad + 255) / 256), (unsigned)nchunk, (unsigned)slope_pair_blocks(dc, with_cov));
   if (with_cov)
     hipLaunchKernelGGL(slope_gram_partial_kernel<true>, grid, dim3(256), 0, e->stream, e->pw.dV, ldz, mpad, e->dv, e->N, dc, e->slope.part);
@@ -3864,7 +3772,7 @@ int predict_slope_sel(gmb_engine* e, const uint32_t* sel, const char* what, cons
   const bool with_cov = dcov != nullptr;
   const int dc = cols.n;
   const int64_t Mt = std::min<int64_t>(slope_tile_rows(predict_tile_rows(e, (int64_t)1 << 40), dc), round_up(M, TILE));
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   // every allocation before the first launch: Dc stacked blocks in the prediction's workspace, the partials, the results
   if ((rc = predict_workspace(e, (int64_t)dc * Mt))) return rc;
   if ((rc = e->slope.reserve(e->pool, Mt, (int64_t)nchunk * slope_entries(dc, with_cov), e->D, with_cov))) return rc;
@@ -3910,7 +3818,7 @@ int predict_sel(gmb_engine* e, const uint32_t* sel, const char* what, const doub
   if ((rc = predict_workspace(e, Mt))) return rc;
   // the GEMM form needs the inverse factor the tile path's gradient leaves behind, and a second Mt x Np buffer
   const bool use_gemm_form = predict_takes_gemm_form(e);
-  if (use_gemm_form && (rc = predict_gemm_form_workspace(e, Mt))) return rc;
+  if (use_gemm_form && (rc = e->pw2.reserve(e->pool, Mt, e->Np))) return rc;
   e->tm.predict_gemm_form = use_gemm_form ? 1 : 0;
 
   const CopyKinds ck = copy_kinds(memspace);
@@ -4064,17 +3972,15 @@ bool loo_takes_product_form(const gmb_engine* e) {
 // A prediction's workspace for M-tiles of Mt rows, measured against the device before anything is allocated or launched
 // (joint_workspace's rule, without the second matrix)
 int leave_out_workspace(gmb_engine* e, const char* what, int64_t Mt) {
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
-  const double per_row = 8.0 * ((double)e->Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;
-  double fresh = 0.0;
-  if (e->pw.rows < Mt) fresh += per_row * (double)(Mt - e->pw.rows);
-  if ((double)e->dpart.cap < 2.0 * nchunk * (double)Mt) fresh += 8.0 * (2.0 * nchunk * (double)Mt - (double)e->dpart.cap);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
-  if (fresh > (double)free_b)
+  Budget need;
+  predict_buffers(*e, (double)Mt, need);
+  double free_b;
+  int rc;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
+  if (need.fresh > free_b)
     return fail(e, GMB_ENOMEM, "%s: tiles of %lld rows behind N = %lld need %.0f bytes on the device, %.0f more than it holds for the engine "
                                "now; %.0f bytes are free -- nothing was computed",
-                what, (long long)Mt, (long long)e->N, per_row * (double)Mt + 16.0 * nchunk * (double)Mt, fresh, (double)free_b);
+                what, (long long)Mt, (long long)e->N, need.total, need.fresh, free_b);
   return predict_workspace(e, Mt);
 }
 
@@ -4132,7 +4038,7 @@ int loo_impl(gmb_engine* e, int64_t i0, int64_t n, int32_t with_noise, double* m
   if ((rc = leave_out_workspace(e, "gmb_loo", Mt))) return rc;
   reset_predict_timings(e);
   e->tm.predict_gemm_form = 0;
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   PhaseTimer tp(e);
   auto tiles = [&]() -> int {
     for (int64_t m0 = 0; m0 < n; m0 += Mt) {
@@ -4179,7 +4085,7 @@ int leave_out_impl(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_no
   const int64_t Mr = jt.Mr, Mp = jt.Mp;
   const LeaveOutDiag off = leave_out_diag(e, with_noise);
   const CopyKinds ck = copy_kinds(memspace);
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   // g = alpha_B and t = X^T g: two vectors in the prepared test points' block, which no launch of this call reads as points
   double* g = e->pw.txs;
   double* t = e->pw.txs + Mr;
@@ -4228,7 +4134,7 @@ int leave_out_impl(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_no
       return rc;
     if (Mp > m) HIP_TRY(e, hipMemsetAsync(e->pw.dV + m * Mr, 0, (size_t)((Mp - m) * Mr) * sizeof(double), e->stream));
     // t = X^T g, then (X t)_j = (C^-1 g)_j and |X_j|^2 = (C^-1)_jj by the prediction's reduction
-    const int nchunk_m = (int)((m + RED_CHUNK - 1) / RED_CHUNK);
+    const int nchunk_m = red_chunks(m);
     double* pmu = e->dpart;
     double* ps = e->dpart + (int64_t)nchunk_m * Mp;
     hipLaunchKernelGGL(lo_xt_g_kernel, dim3((unsigned)m), dim3(256), 0, e->stream, e->pw.dV, Mr, g, t);
@@ -4326,45 +4232,30 @@ struct GroupPlan {
 // (joint_workspace's rule): the feature's own workspace -- O(M D), one row block of R and the task partials -- a prediction's for
 // Gr = round_up(G + 1, 128) rows (NEVER for M), the product form's second V, and for a covariance the second matrix and the staging
 // of a host-side result.
+// The buffers are group_buffers' list (workspaces.hpp), walked by the budget and then by the allocation: ONE check, the joint
+// posterior's buffers in it.
 int group_workspace(gmb_engine* e, const char* what, int64_t M, int64_t G, const GroupPlan& plan, bool gemm_form, bool with_cov, double stage) {
-  JointState& jt = e->jt;
-  const int64_t mp = round_up(M, TILE), gr = round_up(G + 1, TILE), gp = round_up(G, TILE);
-  const double Mp = (double)mp, Gr = (double)gr, Gp = (double)gp, Np = (double)e->Np;
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
-  const double ga_row = 8.0 * (e->D + 17 + MAX_LIN + 1 + GA_ROWS) + 4.0 * MAX_TABS;
-  const double part = std::max((double)plan.ntask * Np, (double)plan.block_tasks * Mp);
-  const double idx = 3.0 * (double)plan.ntask + 2.0 * (double)(G + 1);
-  const double per_row = 8.0 * (Np + e->D + 17 + MAX_LIN + 3) + 4.0 * MAX_TABS;  // predict_workspace, per row
-  const double total = ga_row * Mp + 8.0 * part + 8.0 * idx + per_row * Gr + 16.0 * nchunk * Gr + (gemm_form ? 8.0 * Gr * Np : 0.0) +
-                       (with_cov ? 8.0 * Gr * Gp + 8.0 * stage : 0.0);
-  double fresh = 0.0;
-  if ((double)e->ga.rows < Mp) fresh += ga_row * (Mp - (double)e->ga.rows);
-  if ((double)e->ga_part.cap < part) fresh += 8.0 * (part - (double)e->ga_part.cap);
-  if ((double)e->ga_idx.cap < idx) fresh += 8.0 * (idx - (double)e->ga_idx.cap);
-  if ((double)e->pw.rows < Gr) fresh += per_row * (Gr - (double)e->pw.rows);
-  if ((double)e->dpart.cap < 2.0 * nchunk * Gr) fresh += 8.0 * (2.0 * nchunk * Gr - (double)e->dpart.cap);
-  if (gemm_form && (double)e->pw2.rows < Gr) fresh += 8.0 * Np * (Gr - (double)e->pw2.rows);
-  if (with_cov && (double)jt.dC.cap < Gr * Gp) fresh += 8.0 * (Gr * Gp - (double)jt.dC.cap);
-  if (with_cov && (double)jt.dstage.cap < stage) fresh += 8.0 * (stage - (double)jt.dstage.cap);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(e, hipMemGetInfo(&free_b, &total_b));
+  const int64_t gr = round_up(G + 1, TILE), gp = round_up(G, TILE);
+  const double Mp = (double)round_up(M, TILE), Gr = (double)gr, Gp = (double)gp, Np = (double)e->Np;
+  auto walk = [&](auto& v) {
+    return group_buffers(*e, Mp, (double)G, Gr, Gp, (double)plan.ntask, (double)plan.block_tasks, gemm_form, with_cov, stage, v);
+  };
+  Budget need;
+  walk(need);
+  double free_b;
+  int rc;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
   // (every grid extent and index below stays inside 31 bits with these)
-  if (fresh > (double)free_b || Mp > 1073741824.0 || Gr * ((Np > Mp ? Np : Mp) / 256.0 + 1.0) > 2147483647.0)
-    return fail(e, GMB_ENOMEM, "%s: M = %lld points in G = %lld groups behind N = %lld need %.0f bytes on the device (points and R: %.0f, "
+  if (need.fresh > free_b || Mp > 1073741824.0 || Gr * ((Np > Mp ? Np : Mp) / 256.0 + 1.0) > 2147483647.0)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld points in G = %lld groups behind N = %lld needs %.0f bytes on the device (points and R: %.0f, "
                                "task partials: %.0f, V: %.0f%s, C: %.0f), %.0f more than it holds for the engine now; %.0f bytes are free -- "
                                "nothing was computed",
-                what, (long long)M, (long long)G, (long long)e->N, total, ga_row * Mp, 8.0 * part, 8.0 * Gr * Np, gemm_form ? " twice" : "",
-                with_cov ? 8.0 * Gr * Gp : 0.0, fresh, (double)free_b);
-  int rc;
-  if (with_cov) {
-    if ((rc = joint_workspace(e, what, G, gemm_form, stage))) return rc;
-  } else {
-    if ((rc = predict_workspace(e, gr))) return rc;
-    if (gemm_form && (rc = predict_gemm_form_workspace(e, gr))) return rc;
-  }
-  if ((rc = e->ga.reserve(e->pool, mp, e->D))) return rc;
-  if ((rc = e->ga_part.reserve(e->pool, (int64_t)part))) return rc;
-  return e->ga_idx.reserve(e->pool, (int64_t)idx);
+                what, (long long)M, (long long)G, (long long)e->N, need.total, e->ga.bytes(Mp, e->D),
+                sizeof(double) * group_partial_elems((double)plan.ntask, (double)plan.block_tasks, Np, Mp), e->pw2.bytes(Gr, e->Np),
+                gemm_form ? " twice" : "", with_cov ? sizeof(double) * joint_matrix_elems(Gr, Gp) : 0.0, need.fresh, free_b);
+  Reserver take{e->pool};
+  walk(take);
+  return take.rc || !with_cov ? take.rc : joint_fixed_buffers(e, G, gr, gp);
 }
 
 int predict_groups_sel(gmb_engine* e, const uint32_t* sel, const char* what, const double* Xs, int64_t M, int64_t ldxs, const int64_t* offsets,
@@ -4662,10 +4553,10 @@ int gmb_predict_decompose(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
   reset_predict_timings(e);
   e->tm.predict_gemm_form = 0;  // the stacked V is always solved for, as in gmb_predict_with_grad: neither dW nor U is touched
   const int64_t Mt = decompose_tile_rows(e, M);
-  const int nchunk = (int)((e->N + RED_CHUNK - 1) / RED_CHUNK);
+  const int nchunk = red_chunks(e->N);
   // every allocation before the first launch: T stacked blocks in the prediction's workspace, the partials, the results
   if ((rc = predict_workspace(e, (int64_t)T * Mt))) return rc;
-  if ((rc = e->tg.reserve(e->pool, Mt, nchunk, T))) return rc;
+  if ((rc = e->tg.reserve(e->pool, Mt, (int64_t)nchunk * tg_entries(T)))) return rc;
   const CopyKinds ck = copy_kinds(memspace);
   const int np = T * (T + 1) / 2;
   PhaseTimer tp(e);

@@ -34,12 +34,12 @@
 
 #include "covariance.hpp"
 #include "group_tasks.hpp"
+#include "workspace_sizes.hpp"  // GA_ROWS
 
 namespace gmb {
 
 constexpr int GA_COLS = 64;     // column points per workgroup (a lane each)
 constexpr int GA_PIECE = 128;   // group points staged in LDS at a time
-constexpr int GA_ROWS = 128;    // groups per row block of the Q pass (the leading dimension of R)
 static_assert(GROUP_CHUNK % GA_PIECE == 0, "a task is a whole number of staged pieces at most");
 
 struct GroupCovArgs {

@@ -9,13 +9,9 @@
 // No atomics, every output written once.
 #pragma once
 #include "covariance.hpp"
+#include "workspace_sizes.hpp"  // TG_MAX_TERMS, tg_entries
 
 namespace gmb {
-
-constexpr int TG_MAX_TERMS = 5;  // 1 + GMB_MAX_COREG: 5 means + 15 products = 20 f64 accumulators per thread
-
-// entries per test point and chunk: NT means, then the packed lower triangle (row p = t (t + 1) / 2 + u, u <= t)
-__host__ __device__ constexpr int tg_entries(int nt) { return nt + nt * (nt + 1) / 2; }
 
 // part[chunk][q][m]: q < NT the chunk's share of mu_q, q = NT + p the chunk's share of <V_t, V_u>.
 // Grid (ceil(mpad / 256), nchunk), 256 threads, one test point per thread; the chunk's RED_CHUNK entries of v sit in LDS.  Every

@@ -1,0 +1,152 @@
+// workspaces.hpp -- the engine's workspaces, and what each guarded call asks of them.
+//
+// A workspace is a row group (device_buffers.hpp).  Each struct writes its members ONCE, in each(): (buffer, element count) pairs
+// for a row count and its other size arguments.  reserve() renews by walking that list, bytes() sums sizeof(T) * count over it and
+// a Budget measures with the two, so what a call is refused for and what it allocates cannot drift apart.  The counts are
+// doubles: a request that has to be refused may not fit in int64_t, and every count that IS allocated is an integer below 2^53.
+// One level up, predict_buffers / joint_buffers / group_buffers list every buffer of a call once, over a visitor (a Budget, then a
+// Reserver); they are templates over the engine, of which they use N, Np, D and the members named in them.
+//
+// No HIP and no engine types: tools/workspace_budget_check.cpp runs this very header over a host allocator.
+#pragma once
+#include "device_buffers.hpp"
+#include "slope_plan.hpp"  // SLOPE_MAX_COLS
+#include "workspace_sizes.hpp"
+
+namespace gmb {
+
+// what every workspace derives from its list: Self::each(rows, <size arguments>, f) calls f(buffer, element count) for every member
+// while f says "go on".  A workspace whose SHAPE can grow (more entries per row, a further member) hides held() and sized_for():
+// it holds no rows for a larger shape, and is renewed whole for one.
+template <class Self>
+struct Workspace : RowGroup {
+  template <typename... Args>
+  double bytes(double n, Args... args) {
+    double sum = 0.0;
+    self().each(n, args..., [&](auto& b, double count) { return sum += sizeof(*b.p) * count, true; });
+    return sum;
+  }
+  template <typename... Args>  // rows that serve a request with these size arguments
+  int64_t held(Args...) const { return rows; }
+  template <typename... Args>  // the members were renewed for these
+  void sized_for(Args...) {}
+  template <typename... Args>
+  int reserve(DevPool& pool, int64_t n, Args... args) {
+    if (!self().held(args...)) stale();
+    return reserve_rows(n, [&] {
+      int rc = 0;
+      self().each((double)n, args..., [&](auto& b, double count) { return !(rc = b.renew(pool, (int64_t)count)); });
+      if (!rc) self().sized_for(args...);
+      return rc;
+    });
+  }
+  Self& self() { return *static_cast<Self*>(this); }
+};
+
+struct PreparedPoints : Workspace<PreparedPoints> {  // the training points as the covariance kernels read them (SoA, stride = rows)
+  DevBuf<double> xs, xl;
+  DevBuf<int32_t> cat;
+  template <class F>
+  bool each(double n, F&& f) { return f(xs, XS_ROWS * n) && f(xl, MAX_LIN * n) && f(cat, MAX_TABS * n); }
+};
+
+struct PredictWorkspace : Workspace<PredictWorkspace> {  // what an M-tile of Mt rows of a prediction needs
+  DevBuf<double> dV, dXs, txs, txl;
+  DevBuf<int32_t> tcat;
+  DevBuf<double> dkss, dmean, dvar;
+  template <class F>
+  bool each(double Mt, int64_t Np, int D, F&& f) {
+    return f(dV, Mt * (double)Np) && f(dXs, Mt * D) && f(txs, XS_ROWS * Mt) && f(txl, MAX_LIN * Mt) && f(tcat, MAX_TABS * Mt) && f(dkss, Mt) &&
+           f(dmean, Mt) && f(dvar, Mt);
+  }
+};
+
+struct GemmFormWorkspace : Workspace<GemmFormWorkspace> {  // the product form's second V (predict_form.hpp)
+  DevBuf<double> dV2;  // Np x Mt: the solved cross-covariance with the TRAINING index fastest
+  template <class F>
+  bool each(double Mt, int64_t Np, F&& f) { return f(dV2, Mt * (double)Np); }
+};
+
+struct PredictGradWorkspace : Workspace<PredictGradWorkspace> {  // gmb_predict_grad's own, beside a prediction's (predict_grad.hpp)
+  DevBuf<double> Xs, xs, xl;
+  DevBuf<int32_t> cat;
+  DevBuf<double> grad;
+  template <class F>
+  bool each(double Mt, int D, F&& f) { return f(Xs, Mt * D) && f(xs, XS_ROWS * Mt) && f(xl, MAX_LIN * Mt) && f(cat, MAX_TABS * Mt) && f(grad, Mt * D); }
+};
+
+// gmb_predict_decompose (predict_terms.hpp): the chunked partials of an M-tile ([chunk][entry][Mt], `entries` = chunks x entries)
+// and its results (T means, T (T + 1) / 2 covariance rows, the noise: rows of Mt)
+struct TermsWorkspace : Workspace<TermsWorkspace> {
+  DevBuf<double> part, out;
+  int64_t per_row = 0;  // the entries the rows were sized for
+  template <class F>
+  bool each(double Mt, int64_t entries, F&& f) { return f(part, (double)entries * Mt) && f(out, (tg_entries(TG_MAX_TERMS) + 1) * Mt); }
+  int64_t held(int64_t entries) const { return per_row < entries ? 0 : rows; }
+  void sized_for(int64_t entries) { per_row = entries; }
+};
+
+// gmb_predict_groups (group_average.hpp), sized by the call's M points and by nothing of size M x N: the raw and the prepared
+// points, their weights and one row block of R (128 x M)
+struct GroupWorkspace : Workspace<GroupWorkspace> {
+  DevBuf<double> Xs, xs, xl, w, R;
+  DevBuf<int32_t> cat;
+  template <class F>
+  bool each(double Mp, int D, F&& f) {
+    return f(Xs, Mp * D) && f(xs, XS_ROWS * Mp) && f(xl, MAX_LIN * Mp) && f(w, Mp) && f(R, GA_ROWS * Mp) && f(cat, MAX_TABS * Mp);
+  }
+};
+
+// gmb_predict_slope (predict_slope.hpp): the chunked partials of an M-tile ([chunk][entry][Mt]), the prior curvature (Dc rows of
+// Mt) and the results in the caller's layout (Mt x D twice, Mt x D x D when the covariance is asked for)
+struct SlopeWorkspace : Workspace<SlopeWorkspace> {
+  DevBuf<double> part, prior, mean, var, cov;
+  int64_t per_row = 0;  // the entries the partials were sized for
+  bool has_cov = false;
+  template <class F>
+  bool each(double Mt, int64_t entries, int D, bool with_cov, F&& f) {
+    return f(part, (double)entries * Mt) && f(prior, SLOPE_MAX_COLS * Mt) && f(mean, Mt * D) && f(var, Mt * D) && (!with_cov || f(cov, Mt * D * D));
+  }
+  int64_t held(int64_t entries, int, bool with_cov) const { return per_row < entries || (with_cov && !has_cov) ? 0 : rows; }
+  void sized_for(int64_t entries, int, bool with_cov) { per_row = entries, has_cov = with_cov; }
+};
+
+// ---- what a call asks for: its buffers, listed once (`v`: a Budget or a Reserver) ---------------------------------------------------
+
+// chunks of the posterior reductions' first stage over the N training rows
+inline int red_chunks(int64_t N) { return (int)((N + RED_CHUNK - 1) / RED_CHUNK); }
+
+// a prediction's M-tiles of Mt rows: the workspace and the two chunked partial sums (mean, variance) of a tile
+template <class E, class V>
+bool predict_buffers(E& e, double Mt, V& v) {
+  return v.rows(e.pw, Mt, e.Np, e.D) && v.buf(e.dpart, 2.0 * red_chunks(e.N) * Mt);
+}
+
+// elements of the joint posterior's second matrix (bordered layout: Mr = M + 1 rounded up to a tile, Mp = M rounded up)
+inline double joint_matrix_elems(double Mr, double Mp) { return Mr * Mp; }
+
+// a joint posterior: V whole (all Mr rows in ONE tile), the product form's second V, C, and `stage` doubles of device staging
+template <class E, class V>
+bool joint_buffers(E& e, double Mr, double Mp, bool gemm_form, double stage, V& v) {
+  return predict_buffers(e, Mr, v) && (!gemm_form || v.rows(e.pw2, Mr, e.Np)) && v.buf(e.jt.dC, joint_matrix_elems(Mr, Mp)) &&
+         (stage <= 0.0 || v.buf(e.jt.dstage, stage));
+}
+
+// elements of the task partials of one reduction of gmb_predict_groups ([task][column]): all tasks against the training points, or
+// the fullest row block's against the call's own
+inline double group_partial_elems(double ntask, double block_tasks, double Np, double Mp) {
+  return ntask * Np > block_tasks * Mp ? ntask * Np : block_tasks * Mp;
+}
+
+// gmb_predict_groups: a prediction's buffers for Gr = G + 1 rounded up rows (NEVER for M) -- a joint posterior's when the covariance
+// is asked for -- then the feature's own workspace for Mp rows, the task partials and the index arrays (the task triples, then
+// first_task and offsets: G + 1 each)
+template <class E, class V>
+bool group_buffers(E& e, double Mp, double G, double Gr, double Gp, double ntask, double block_tasks, bool gemm_form, bool with_cov,
+                   double stage, V& v) {
+  return (with_cov ? joint_buffers(e, Gr, Gp, gemm_form, stage, v) : predict_buffers(e, Gr, v) && (!gemm_form || v.rows(e.pw2, Gr, e.Np))) &&
+         v.rows(e.ga, Mp, e.D) && v.buf(e.ga_part, group_partial_elems(ntask, block_tasks, (double)e.Np, Mp)) &&
+         v.buf(e.ga_idx, 3.0 * ntask + 2.0 * (G + 1.0));
+}
+
+}  // namespace gmb

@@ -345,3 +345,51 @@ def test_a_request_that_cannot_fit_is_refused_before_anything_runs(gpu):
     mean, cov = eng.predict_joint(Xs)
     assert np.max(np.abs(np.diag(cov) - var1)) <= 1e-11
     eng.close()
+
+
+def test_group_averages_that_cannot_fit_are_refused_before_anything_runs(gpu):
+    """The guard of ``gmb_predict_groups``, without and with a covariance: G = M singleton groups, M as above, so that V for the
+    G rows alone exceeds the device.  One check covers the call's own workspace and the joint posterior's buffers (``cov=True``).
+
+    The covariance case goes through the C ABI with the engine's own status check: the front end would first ask numpy for the
+    G x G result, which no host has.  The refused call writes none of its outputs, so one double stands in for it.
+
+    ``gmb_loo`` and ``gmb_leave_out`` cannot be made to exceed the device at a test-sized N -- their row count is bounded by N --
+    so their guard's arithmetic is covered on the host only (tools/workspace_budget_check.cpp, tests/test_workspace_budget_cpu.py).
+    """
+    import ctypes as C
+
+    import torch
+
+    from gumbi_amd.engine import GMB_HOST
+
+    spec, theta, X, y, Xs, _ = problem("fit_4224")
+    eng = make_engine(spec, theta, X, y)
+    eng.factorize()
+    mu0, var0 = eng.predict(Xs)
+    total = torch.cuda.get_device_properties(0).total_memory
+    Np = -(-X.shape[0] // 128) * 128
+    M = (total - eng.resident_bytes()) // (8 * Np) + 1024
+    big = np.zeros((M, X.shape[1]))  # (never touched: the call is refused before it copies anything)
+    offsets = np.arange(M + 1, dtype=np.int64)
+    mean, var, one = np.empty(M), np.empty(M), np.empty(1)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def without_cov():
+        eng.predict_groups(big, offsets)
+
+    def with_cov():
+        rc = eng._lib.gmb_predict_groups(eng._h, ptr(big), M, big.shape[1], ptr(offsets), M, None, ptr(mean), ptr(var), ptr(one), M, GMB_HOST)
+        eng._check(rc, "gmb_predict_groups")
+
+    before = eng.resident_bytes()
+    for call in (without_cov, with_cov):
+        with pytest.raises(MemoryError, match=r"needs \d+ bytes") as err:
+            call()
+        text = str(err.value)
+        print(f"{call.__name__}: {text}")
+        assert "gmb_predict_groups" in text and f"M = {M}" in text and f"G = {M}" in text
+        assert eng.resident_bytes() == before and eng.factor_is_current()
+        mu1, var1 = eng.predict(Xs)
+        assert np.array_equal(mu0, mu1) and np.array_equal(var0, var1)
+    eng.close()
