@@ -718,6 +718,13 @@ struct KssArgs {
   int32_t accumulate;  // additive models: later terms add to kss
 };
 
+// the noise variance at point m of a prepared set (the output's level is read from the noise table's category)
+__device__ __forceinline__ double kss_noise(const CovParams& p, const PointSet& pts, const int64_t m) {
+  double nz = p.sigma2;
+  if (p.noise_tab >= 0) nz *= p.noise_mult[pts.cat[(int64_t)p.noise_tab * pts.npad + m]];
+  return nz;
+}
+
 __global__ void kss_kernel(KssArgs a) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= a.pts.npad) return;
@@ -735,11 +742,7 @@ __global__ void kss_kernel(KssArgs a) {
     const int c = a.pts.cat[(int64_t)t * a.pts.npad + m];
     v *= p.tabs[p.tab_off[t] + c * p.tab_levels[t] + c];
   }
-  if (a.with_noise) {
-    double nz = p.sigma2;
-    if (p.noise_tab >= 0) nz *= p.noise_mult[a.pts.cat[(int64_t)p.noise_tab * a.pts.npad + m]];
-    v += nz;
-  }
+  if (a.with_noise) v += kss_noise(p, a.pts, m);
   if (a.accumulate) {
     if (m < a.pts.n) a.kss[m] += v;
   } else {

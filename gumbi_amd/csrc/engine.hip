@@ -50,6 +50,7 @@
 #include "leave_out.hpp"
 #include "group_average.hpp"
 #include "predict_slope.hpp"
+#include "design_batch.hpp"
 
 using namespace gmb;
 
@@ -86,10 +87,12 @@ enum EvKind : int {
   EV_TERM_GRAM = 17,          // gmb_predict_decompose: the reduction's partial + final launches of one M-tile (k = terms)
   EV_GROUP_COV = 18,          // gmb_predict_groups: the partial launches of one reduction of one term (mt = column blocks, nt = tasks,
                               // flags = 0 the cross part A, 1 the prior part Q, 2 its diagonal only)
-  EV_SLOPE_COV = 19           // gmb_predict_slope: the derivative cross-covariance launch of the first selected term (mt x nt tiles
+  EV_SLOPE_COV = 19,          // gmb_predict_slope: the derivative cross-covariance launch of the first selected term (mt x nt tiles
                               // of 128 x 128 pairs, k = differentiable columns written per pair)
+  EV_DESIGN = 20              // gmb_design_batch: a PHASE, around the launches listed above (flags = 0 the solved rows V of one point
+                              // tile, 1 its prior + rank-N update, 2 the greedy loop: mt = candidates, nt = doubles per row of D, k = picks)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_SLOPE_COV); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_DESIGN); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -195,6 +198,7 @@ struct gmb_engine {
   DevBuf<double> ga_part;   // [task][column] of one reduction
   SlopeWorkspace slope;     // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
+  DesignWorkspace dz;       // gmb_design_batch (design_batch.hpp), beside a prediction's workspace of one point tile
 
   // gradient workspace
   DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
@@ -514,7 +518,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_SPLITK:
       case EV_TERM_GRAM:
       case EV_GROUP_COV:
-      case EV_SLOPE_COV: break;
+      case EV_SLOPE_COV:
+      case EV_DESIGN: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -975,6 +980,7 @@ void stale_sized_by_n(gmb_engine* e) {
   e->pg.stale();
   e->ga.stale();
   e->slope.stale();
+  e->dz.stale();
   e->plan_N = -1;
 }
 
@@ -4439,6 +4445,260 @@ int predict_groups_sel(gmb_engine* e, const uint32_t* sel, const char* what, con
   return predict_end(e, &tp, work());
 }
 
+// ---- a batch of experiments by greedy integrated variance reduction (design_batch.hpp) ----------------------------
+
+// Every buffer of gmb_design_batch, measured against the device before anything is allocated, launched, written or -- the caller's
+// arrays included -- read (joint_workspace's rule).  The buffers are design_buffers' list (workspaces.hpp), walked by this budget
+// and then by design_reserve: a prediction's for the plan's largest point tile, the product form's second V, and the feature's
+// own workspace.
+int design_measure(gmb_engine* e, const char* what, const DesignPlan& pl, int64_t q, bool gemm_form) {
+  Budget need;
+  design_buffers(*e, pl, (double)DesignPlan::result_doubles(pl.M, q), gemm_form, need);
+  double free_b;
+  int rc;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
+  if (need.fresh > free_b)
+    return fail(e, GMB_ENOMEM, "%s: M = %lld candidates and R = %lld reference points behind N = %lld need %.0f bytes on the device (D: %.0f, "
+                               "the candidates' solved rows: %.0f, V of one point tile: %.0f%s), %.0f more than it holds for the engine now; "
+                               "%.0f bytes are free -- nothing was computed",
+                what, (long long)pl.M, (long long)pl.R, (long long)e->N, need.total, 8.0 * (double)pl.Mc * (double)pl.ld,
+                8.0 * (double)pl.Mc * (double)e->Np, e->pw2.bytes((double)pl.mt, e->Np), gemm_form ? " twice" : "", need.fresh, free_b);
+  return GMB_OK;
+}
+int design_reserve(gmb_engine* e, const DesignPlan& pl, int64_t q, bool gemm_form) {
+  Reserver take{e->pool};
+  design_buffers(*e, pl, (double)DesignPlan::result_doubles(pl.M, q), gemm_form, take);
+  return take.rc;
+}
+
+// `n` points of the caller's (host, or device: copied to the host first) must hold no NaN; 0, or the refusal
+int design_check_points(gmb_engine* e, const char* what, const char* name, const double* X, int64_t n, int64_t ldx, bool host,
+                        std::vector<double>& scratch) {
+  const int64_t D = e->D;
+  const double* src = X;
+  int64_t l = ldx;
+  if (!host) {
+    scratch.resize((size_t)(n * D));
+    HIP_TRY(e, hipMemcpy2DAsync(scratch.data(), D * sizeof(double), X, ldx * sizeof(double), D * sizeof(double), n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    src = scratch.data();
+    l = D;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t d = 0; d < D; ++d)
+      if (std::isnan(src[i * l + d])) return fail(e, GMB_EINVAL, "%s: %s[%lld, %lld] is NaN", what, name, (long long)i, (long long)d);
+  return GMB_OK;
+}
+
+int design_batch_impl(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, const double* Xr, int64_t R, int64_t ldr, const double* w,
+                      int32_t q, int32_t with_noise, int32_t allow_repeats, int64_t* picks, double* gains, double* score0, double* ivar0,
+                      int32_t memspace) {
+  const char* what = "gmb_design_batch";
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  if (M < 1 || R < 1 || q < 0)
+    return fail(e, GMB_EINVAL, "%s: M = %lld candidates, R = %lld reference points, q = %d picks (M >= 1, R >= 1 and q >= 0 are required)", what,
+                (long long)M, (long long)R, (int)q);
+  if (!Xc || !Xr || ldc < e->D || ldr < e->D || (q > 0 && (!picks || !gains)))
+    return fail(e, GMB_EINVAL, "%s: null Xc/Xr, ldc < D, ldr < D, or q > 0 without picks/gains", what);
+  HIP_TRY(e, hipSetDevice(e->device));
+  const bool host = memspace != GMB_DEVICE;
+  const CopyKinds ck = copy_kinds(memspace);
+
+  // the plan first (host arithmetic), then the bytes against the device, then the arguments' values, then the allocation: a
+  // refusal has touched nothing
+  DesignPlan pl;
+  switch (pl.make(e->Np, M, R)) {
+    case 0: break;
+    case 4:
+      return fail(e, GMB_ENOMEM, "%s: M = %lld candidates are more than one M-tile of a prediction holds behind N = %lld (%lld rows: their "
+                                 "solved rows alone would take %.0f bytes) -- nothing was computed",
+                  what, (long long)M, (long long)e->N, (long long)pl.mt_max, 8.0 * (double)M * (double)e->Np);
+    default:
+      return fail(e, GMB_ENOMEM, "%s: R = %lld reference points are more than a call takes (2^30) -- nothing was computed", what, (long long)R);
+  }
+  const bool gemm_form = predict_takes_gemm_form(e);
+  if ((rc = design_measure(e, what, pl, q, gemm_form))) return rc;
+  std::vector<double> scratch, hw;
+  if ((rc = design_check_points(e, what, "Xc", Xc, M, ldc, host, scratch))) return rc;
+  if ((rc = design_check_points(e, what, "Xr", Xr, R, ldr, host, scratch))) return rc;
+  if (w) {
+    const double* src = w;
+    if (!host) {
+      hw.resize((size_t)R);
+      HIP_TRY(e, hipMemcpyAsync(hw.data(), w, R * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(e, hipStreamSynchronize(e->stream));
+      src = hw.data();
+    }
+    for (int64_t r = 0; r < R; ++r)
+      if (!(src[r] >= 0.0) || !std::isfinite(src[r]))
+        return fail(e, GMB_EINVAL, "%s: weights[%lld] = %g is negative or not finite", what, (long long)r, src[r]);
+  } else {
+    hw.assign((size_t)R, 1.0 / (double)R);
+  }
+  if ((rc = design_reserve(e, pl, q, gemm_form))) return rc;
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = gemm_form ? 1 : 0;
+
+  DesignWorkspace& z = e->dz;
+  const int64_t Mc = pl.Mc, ld = pl.ld;
+  const int64_t nres = DesignPlan::result_doubles(M, q);
+  double* d_gains = z.res;
+  double* d_score = z.res + q;
+  double* d_ivar = d_score + M;
+  int64_t* d_picks = reinterpret_cast<int64_t*>(d_ivar + 1);
+  const uint32_t terms = all_terms_mask(e);
+  const int nterms = (int)e->terms.size();
+  const int t_first = first_term(terms);
+  const PointSet cand{z.xs, z.xl, z.cat, M, Mc};
+  std::vector<double> hres(host ? (size_t)nres : 0);
+  PhaseTimer tp(e);
+  // (while profiling: the call's phases as trace lines of their own, around the launches' -- kind 20)
+  auto phase_open = [&](int which, int k) -> size_t {
+    if (!e->profiling) return (size_t)-1;
+    ev_begin(e, e->stream, EV_DESIGN, 0.0, (int)M, (int)ld, k, which);
+    return e->evs.size() - 1;
+  };
+  auto phase_close = [&](size_t at) {
+    if (at != (size_t)-1) (void)hipEventRecord(e->evs[at].b, e->evs[at].s);
+  };
+  auto work = [&]() -> int {
+    HIP_TRY(e, hipMemsetAsync(z.w, 0, (size_t)ld * sizeof(double), e->stream));
+    HIP_TRY(e, hipMemsetAsync(z.var, 0, (size_t)ld * sizeof(double), e->stream));
+    HIP_TRY(e, hipMemsetAsync(z.dpiv, 0, (size_t)ld * sizeof(double), e->stream));
+    HIP_TRY(e, hipMemsetAsync(z.ctl, 0, (size_t)DesignPlan::DESIGN_CTL_DOUBLES * sizeof(double), e->stream));
+    HIP_TRY(e, hipMemsetAsync(z.mask, 0, (size_t)Mc * sizeof(int32_t), e->stream));
+    HIP_TRY(e, hipMemsetAsync(z.res, 0, (size_t)nres * sizeof(double), e->stream));
+    if (w) HIP_TRY(e, hipMemcpyAsync(z.w + Mc, w, R * sizeof(double), ck.in, e->stream));
+    else HIP_TRY(e, hipMemcpyAsync(z.w + Mc, hw.data(), R * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpy2DAsync(z.Xs, e->D * sizeof(double), Xc, ldc * sizeof(double), e->D * sizeof(double), M, ck.in, e->stream));
+    // the candidates as the first term reads them: the noise a prediction would add, by kss_kernel's own term
+    int r;
+    if ((r = prep_points(e, z.Xs, M, e->D, Mc, z.xs, z.xl, z.cat, &e->terms[t_first].pa))) return r;
+    DesignNoiseArgs na{};
+    na.p = first_pass_params(e, t_first);
+    na.pts = cand;
+    na.with_noise = with_noise;
+    na.noise = z.noise;
+    hipLaunchKernelGGL(design_noise_kernel, dim3((unsigned)((Mc + 255) / 256)), dim3(256), 0, e->stream, na);
+    HIP_TRY(e, hipGetLastError());
+
+    for (int64_t ti = 0; ti < pl.ntile; ++ti) {
+      const DesignTile tl = pl.tile(ti);
+      const double* X = ti == 0 ? Xc : Xr + (tl.first - M) * ldr;
+      // 1. V = L^-1 K(X, P_tile) in the form a prediction would take, and the latent variances by its own reduction
+      size_t ph = phase_open(0, 0);
+      if ((r = predict_cross_cov(e, terms, X, tl.count, tl.mpad, ti == 0 ? ldc : ldr, 0, ck.in))) return r;
+      if ((r = predict_solve_v(e, tl.mpad, gemm_form))) return r;
+      if ((r = predict_reduce(e, tl.count, tl.mpad, gemm_form))) return r;
+      if (ti > 0) HIP_TRY(e, hipMemcpyAsync(z.var + tl.col0, e->pw.dvar, tl.count * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      // (as joint_covariance: the product form's V into the update's k-major layout, the columns of no training point cleared)
+      if (gemm_form && (r = launch_transpose(e, e->stream, e->pw2.dV2, e->Np, e->pw.dV, tl.mpad, (int)e->Np, (int)tl.mpad))) return r;
+      if (e->Np > e->N)
+        HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * tl.mpad, 0, (size_t)((e->Np - e->N) * tl.mpad) * sizeof(double), e->stream));
+      if (ti == 0) HIP_TRY(e, hipMemcpyAsync(z.dVc, e->pw.dV, (size_t)(Mc * e->Np) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      phase_close(ph);
+      ph = phase_open(1, 0);
+      // 2. the prior K(Xc, P_tile) into D's columns of the tile, term by term; both point sets are workspace copies (a model of
+      // one term builds on the preparations as they stand)
+      const PointSet tile_pts{e->pw.txs, e->pw.txl, e->pw.tcat, tl.count, tl.mpad};
+      bool first = true;
+      for (int t = 0; t < nterms; ++t) {
+        if (!((terms >> t) & 1u)) continue;
+        if (nterms > 1) {
+          if ((r = prep_points(e, e->pw.dXs, tl.count, e->D, tl.mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &e->terms[t].pa))) return r;
+          if ((r = prep_points(e, z.Xs, M, e->D, Mc, z.xs, z.xl, z.cat, &e->terms[t].pa))) return r;
+        }
+        CovTileArgs a{};
+        a.p = e->terms[t].cp;
+        a.rows = tile_pts;
+        a.cols = cand;
+        a.out = z.dD + tl.col0;
+        a.ldo = ld;
+        a.ti = (int)(tl.mpad / TILE);
+        a.tj = (int)(Mc / TILE);
+        a.mode = COV_CROSS;
+        a.accumulate = first ? 0 : 1;
+        if ((r = launch_cov(e, a))) return r;
+        first = false;
+      }
+      // 3. D[:, tile] -= Vc V_tile^T: the joint posterior's update with contraction length Np
+      GemmArgs g{};
+      g.C = z.dD + tl.col0;
+      g.ldc = ld;
+      g.A = z.dVc;
+      g.lda = Mc;
+      g.B = e->pw.dV;
+      g.ldb = tl.mpad;
+      g.mt = (int)(Mc / TILE);
+      g.nt = (int)(tl.mpad / TILE);
+      g.k = (int)e->Np;
+      g.alpha = -1.0;
+      g.beta = 1.0;
+      if ((r = launch_gemm(e, e->stream, g, EV_PREDICT_GEMM))) return r;
+      phase_close(ph);
+    }
+    hipLaunchKernelGGL(design_ivar_kernel, dim3(1), dim3(DESIGN_PICK_THREADS), 0, e->stream, (const double*)z.w, (const double*)z.var, ld, d_ivar);
+    HIP_TRY(e, hipGetLastError());
+
+    // 4. the greedy loop: step (the downdate of the last pick, the sums of the new score) and pick, back to back
+    if (q > 0 || score0) {
+      DesignStepArgs sa{};
+      sa.D = z.dD;
+      sa.ld = ld;
+      sa.M = M;
+      sa.Mc = Mc;
+      sa.piv = z.dpiv;
+      sa.w = z.w;
+      sa.ctl = z.ctl;
+      sa.part = z.part;
+      DesignPickArgs pa{};
+      pa.D = z.dD;
+      pa.ld = ld;
+      pa.M = M;
+      pa.Mc = Mc;
+      pa.nchunk = pl.nchunk;
+      pa.part = z.part;
+      pa.noise = z.noise;
+      pa.mask = z.mask;
+      pa.ctl = z.ctl;
+      pa.piv = z.dpiv;
+      pa.gains = d_gains;
+      pa.picks = d_picks;
+      pa.score0 = d_score;
+      pa.allow_repeats = allow_repeats;
+      pa.score_only = q == 0 ? 1 : 0;
+      const dim3 sgrid((unsigned)pl.nchunk, (unsigned)((M + DESIGN_ROWS - 1) / DESIGN_ROWS));
+      const size_t ph = phase_open(2, (int)q);
+      for (int32_t t = 0; t < (q > 0 ? q : 1); ++t) {
+        hipLaunchKernelGGL(design_step_kernel, sgrid, dim3(DESIGN_THREADS), 0, e->stream, sa);
+        pa.t = t;
+        hipLaunchKernelGGL(design_pick_kernel, dim3(1), dim3(DESIGN_PICK_THREADS), 0, e->stream, pa);
+      }
+      phase_close(ph);
+      HIP_TRY(e, hipGetLastError());
+    }
+    // 5. the results
+    if (host) {
+      HIP_TRY(e, hipMemcpyAsync(hres.data(), z.res, (size_t)nres * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    } else {
+      if (q > 0) HIP_TRY(e, hipMemcpyAsync(gains, d_gains, q * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (q > 0) HIP_TRY(e, hipMemcpyAsync(picks, d_picks, q * sizeof(int64_t), hipMemcpyDeviceToDevice, e->stream));
+      if (score0) HIP_TRY(e, hipMemcpyAsync(score0, d_score, M * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (ivar0) HIP_TRY(e, hipMemcpyAsync(ivar0, d_ivar, sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    }
+    return GMB_OK;
+  };
+  if ((rc = predict_end(e, &tp, work()))) return rc;
+  if (host) {
+    if (q > 0) std::memcpy(gains, hres.data(), (size_t)q * sizeof(double));
+    if (q > 0) std::memcpy(picks, hres.data() + q + M + 1, (size_t)q * sizeof(int64_t));
+    if (score0) std::memcpy(score0, hres.data() + q, (size_t)M * sizeof(double));
+    if (ivar0) *ivar0 = hres[(size_t)(q + M)];
+  }
+  return GMB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4611,6 +4871,14 @@ int64_t gmb_debug_slope_tile_rows(int64_t Np, int32_t Dc) {
   if (Np < 1 || Dc < 1 || Dc > SLOPE_MAX_COLS) return GMB_EINVAL;
   return slope_tile_rows(slope_predict_rows_max(Np), Dc);
 }
+
+int gmb_design_batch(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, const double* Xr, int64_t R, int64_t ldr, const double* w,
+                     int32_t q, int32_t with_noise, int32_t allow_repeats, int64_t* picks, double* gains, double* score0, double* ivar0,
+                     int32_t memspace) {
+  return design_batch_impl(e, Xc, M, ldc, Xr, R, ldr, w, q, with_noise, allow_repeats, picks, gains, score0, ivar0, memspace);
+}
+
+int64_t gmb_debug_design_plan(int64_t Np, int64_t M, int64_t R, int64_t* out, int64_t cap) { return design_plan_dump(Np, M, R, out, cap); }
 
 int64_t gmb_debug_group_tasks(const int64_t* offsets, int64_t G, int64_t chunk, int64_t* out, int64_t cap) {
   if (!offsets || G < 1) return (int64_t)GMB_EINVAL;

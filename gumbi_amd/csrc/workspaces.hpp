@@ -4,11 +4,12 @@
 // for a row count and its other size arguments.  reserve() renews by walking that list, bytes() sums sizeof(T) * count over it and
 // a Budget measures with the two, so what a call is refused for and what it allocates cannot drift apart.  The counts are
 // doubles: a request that has to be refused may not fit in int64_t, and every count that IS allocated is an integer below 2^53.
-// One level up, predict_buffers / joint_buffers / group_buffers list every buffer of a call once, over a visitor (a Budget, then a
-// Reserver); they are templates over the engine, of which they use N, Np, D and the members named in them.
+// One level up, predict_buffers / joint_buffers / group_buffers / design_buffers list every buffer of a call once, over a visitor
+// (a Budget, then a Reserver); they are templates over the engine, of which they use N, Np, D and the members named in them.
 //
 // No HIP and no engine types: tools/workspace_budget_check.cpp runs this very header over a host allocator.
 #pragma once
+#include "design_plan.hpp"
 #include "device_buffers.hpp"
 #include "slope_plan.hpp"  // SLOPE_MAX_COLS
 #include "workspace_sizes.hpp"
@@ -111,6 +112,28 @@ struct SlopeWorkspace : Workspace<SlopeWorkspace> {
   void sized_for(int64_t entries, int, bool with_cov) { per_row = entries, has_cov = with_cov; }
 };
 
+// gmb_design_batch (design_batch.hpp), by the Mc padded candidates of a DesignPlan: the candidates raw and prepared, their solved
+// rows dVc (Mc x Np), D (Mc rows of ld), the pick's row, the weights and latent variances by column of D, the step kernel's
+// partial sums ([chunk][Mc]), noise and mask by candidate, the control block and the results' staging (`res` doubles)
+struct DesignWorkspace : Workspace<DesignWorkspace> {
+  DevBuf<double> Xs, xs, xl, dVc, dD, dpiv, w, var, part, noise, ctl, res;
+  DevBuf<int32_t> cat, mask;
+  int64_t for_np = 0, for_ld = 0, for_chunks = 0, for_res = 0;
+  int for_d = 0;
+  template <class F>
+  bool each(double Mc, int64_t Np, int64_t ld, int64_t nchunk, int64_t nres, int D, F&& f) {
+    return f(Xs, Mc * D) && f(xs, XS_ROWS * Mc) && f(xl, MAX_LIN * Mc) && f(cat, MAX_TABS * Mc) && f(dVc, Mc * (double)Np) &&
+           f(dD, Mc * (double)ld) && f(dpiv, (double)ld) && f(w, (double)ld) && f(var, (double)ld) && f(part, (double)nchunk * Mc) &&
+           f(noise, Mc) && f(mask, Mc) && f(ctl, (double)DesignPlan::DESIGN_CTL_DOUBLES) && f(res, (double)nres);
+  }
+  int64_t held(int64_t Np, int64_t ld, int64_t nchunk, int64_t nres, int D) const {
+    return for_np < Np || for_ld < ld || for_chunks < nchunk || for_res < nres || for_d < D ? 0 : rows;
+  }
+  void sized_for(int64_t Np, int64_t ld, int64_t nchunk, int64_t nres, int D) {
+    for_np = Np, for_ld = ld, for_chunks = nchunk, for_res = nres, for_d = D;
+  }
+};
+
 // ---- what a call asks for: its buffers, listed once (`v`: a Budget or a Reserver) ---------------------------------------------------
 
 // chunks of the posterior reductions' first stage over the N training rows
@@ -147,6 +170,14 @@ bool group_buffers(E& e, double Mp, double G, double Gr, double Gp, double ntask
   return (with_cov ? joint_buffers(e, Gr, Gp, gemm_form, stage, v) : predict_buffers(e, Gr, v) && (!gemm_form || v.rows(e.pw2, Gr, e.Np))) &&
          v.rows(e.ga, Mp, e.D) && v.buf(e.ga_part, group_partial_elems(ntask, block_tasks, (double)e.Np, Mp)) &&
          v.buf(e.ga_idx, 3.0 * ntask + 2.0 * (G + 1.0));
+}
+
+// gmb_design_batch: a prediction's buffers for the plan's largest point tile (`mt` rows, NEVER all M + R), the product form's
+// second V, then the feature's own workspace (`nres`: doubles of the results' staging)
+template <class E, class V>
+bool design_buffers(E& e, const DesignPlan& pl, double nres, bool gemm_form, V& v) {
+  return predict_buffers(e, (double)pl.mt, v) && (!gemm_form || v.rows(e.pw2, (double)pl.mt, e.Np)) &&
+         v.rows(e.dz, (double)pl.Mc, e.Np, pl.ld, pl.nchunk, (int64_t)nres, (int)e.D);
 }
 
 }  // namespace gmb

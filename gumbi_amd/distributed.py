@@ -393,6 +393,11 @@ class DistributedEngine:
         raise NotImplementedError("predict_slope: the slope's posterior is not built for distributed GPs (gmb_predict_slope "
                                   "needs the complete factor of a single-engine factorisation)")
 
+    def design_batch(self, Xc, Xr, q, weights=None, with_noise=True, allow_repeats=True):
+        raise NotImplementedError("design_batch: the rectangular posterior covariance of the candidates and the reference points is "
+                                  "built on the single-device engine only (gmb_design_batch needs the complete factor of a "
+                                  "single-engine factorisation)")
+
     def predict_with_grad(self, Xs, with_noise=True):
         raise NotImplementedError("predict_with_grad: the posterior's gradients are not built for distributed GPs "
                                   "(gmb_predict_with_grad needs the complete factor of a single-engine factorisation)")

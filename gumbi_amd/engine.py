@@ -360,6 +360,9 @@ _SIGNATURES = {
     "gmb_predict_slope_terms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_int64, C.c_int32]),
     "gmb_debug_slope_tile_rows": (C.c_int64, [C.c_int64, C.c_int32]),
+    "gmb_design_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "gmb_debug_design_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
 }
 
 
@@ -407,7 +410,8 @@ def _preload_hip_runtime():
 #: prediction calls and ``gmb_predict_decompose``; likewise the leave-out predictions of the training rows, ``gmb_loo`` /
 #: ``gmb_leave_out``, and the averages of the posterior over groups of points, ``gmb_predict_groups`` / ``gmb_predict_groups_terms``
 #: with the host-only ``gmb_debug_group_tasks``, and the posterior of the slope, ``gmb_predict_slope`` / ``gmb_predict_slope_terms``
-#: with the host-only ``gmb_debug_slope_tile_rows``)
+#: with the host-only ``gmb_debug_slope_tile_rows``, and the batch design by integrated variance reduction, ``gmb_design_batch`` with
+#: the host-only ``gmb_debug_design_plan``)
 ABI_VERSION = 16
 
 #: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
@@ -819,6 +823,36 @@ class Engine:
             self._check(self._lib.gmb_predict_slope(self._h, *tail), "gmb_predict_slope")
         return (dmean, dvar, dcov) if cov else (dmean, dvar)
 
+    def design_batch(self, Xc, Xr, q, weights=None, with_noise=True, allow_repeats=True):
+        """A batch of ``q`` experiments by greedy integrated variance reduction (``gmb_design_batch``): which rows of the
+        candidates ``Xc`` (M x D), measured next, lower the LATENT posterior variance summed over the reference points ``Xr``
+        (R x D, ``weights`` >= 0, ``None`` = ``1 / R`` each) the most.  Returns ``(picks, gains, score0, ivar0)``: the picked
+        candidate indices in pick order (-1 once no candidate has a positive gain), the variance each pick removes, the step-0
+        score of every candidate and ``sum_r w_r var f(x_r)`` before any pick.  ``with_noise``: a measurement carries the
+        model's noise; then ``allow_repeats`` lets a candidate be picked again -- a replicate.  ``q = 0`` computes the scores
+        alone.  No ``y`` is fantasised: a GP's posterior covariance does not depend on it.  ``ValueError`` for a negative or
+        non-finite weight or a NaN coordinate, ``MemoryError`` -- before anything is computed -- when the device cannot hold the
+        request.  Leaves the factor and everything a fit left beside it untouched."""
+        Xc = np.ascontiguousarray(Xc, dtype=np.float64)
+        Xr = np.ascontiguousarray(Xr, dtype=np.float64)
+        for name, X in (("Xc", Xc), ("Xr", Xr)):
+            if X.ndim != 2 or X.shape[1] != self.D:
+                raise ValueError(f"design_batch: {name} must be (n, {self.D}), got {X.shape}")
+        M, R, q = Xc.shape[0], Xr.shape[0], int(q)
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+            if weights.shape[0] != R:
+                raise ValueError(f"design_batch: {weights.shape[0]} weights for {R} reference points")
+        picks = np.full(max(q, 0), -1, dtype=np.int64)
+        gains = np.zeros(max(q, 0), dtype=np.float64)
+        score0 = np.zeros(M, dtype=np.float64)
+        ivar0 = np.zeros(1, dtype=np.float64)
+        self._check(self._lib.gmb_design_batch(self._h, _ptr(Xc), M, self.D, _ptr(Xr), R, self.D,
+                                               _ptr(weights) if weights is not None else None, q, int(bool(with_noise)),
+                                               int(bool(allow_repeats)), _ptr(picks), _ptr(gains), _ptr(score0), _ptr(ivar0), GMB_HOST),
+                    "gmb_design_batch")
+        return picks, gains, score0, float(ivar0[0])
+
     def predict_with_grad(self, Xs, with_noise=True):
         """``(mean, var, dmean, dvar)`` at the rows of ``Xs``: ``predict``'s mean and variance (M each) and their gradients with
         respect to the test point, ``(M, D)`` each with the columns of :meth:`predict_grad` (``gmb_predict_with_grad``) -- one
@@ -1091,6 +1125,24 @@ def slope_tile_rows(Np: int, Dc: int) -> int:
     if n < 0:
         raise ValueError(f"gmb_debug_slope_tile_rows: Np = {Np}, Dc = {Dc}")
     return n
+
+
+def design_plan(Np: int, M: int, R: int) -> dict:
+    """The plan of ``gmb_design_batch`` behind ``Np`` padded training points (host-only): the sizes, the point tiles
+    ``(first stacked index, count, padded count, first column of D)`` and the step kernel's column chunks ``(first, end)``.
+    ``ValueError`` for a request the call refuses."""
+    lib = load_library()
+    n = int(lib.gmb_debug_design_plan(int(Np), int(M), int(R), None, 0))
+    if n < 0:
+        raise ValueError(f"gmb_debug_design_plan: Np = {Np}, M = {M}, R = {R} is refused (code {-n})")
+    buf = np.empty(n, dtype=np.int64)
+    lib.gmb_debug_design_plan(int(Np), int(M), int(R), _ptr(buf), n)
+    keys = ("Mc", "ld", "mt_max", "mt", "ntile", "nchunk", "chunk", "rows", "own_bytes")
+    plan = {k: int(v) for k, v in zip(keys, buf)}
+    h, nt = len(keys), int(buf[4])
+    plan["tiles"] = [tuple(int(v) for v in buf[h + 4 * t:h + 4 * t + 4]) for t in range(nt)]
+    plan["chunks"] = [tuple(int(v) for v in buf[h + 4 * nt + 2 * c:h + 4 * nt + 2 * c + 2]) for c in range(plan["nchunk"])]
+    return plan
 
 
 def chol_task_count(nct: int, nrt: int) -> int:

@@ -1347,6 +1347,96 @@ class HipGP(Regressor):
             z_score = float(mean[0] / np.sqrt(var[0]))
         return {"mean": float(mean[0]), "var": float(var[0]), "z_score": z_score, "levels": (a, b), "n_background": B}
 
+    # -- a batch of experiments by integrated variance reduction ---------------------------------------------------------------
+    def _design_points(self, what, candidates, reference, n_candidates, n_reference, bounds, categorical_levels, output, seed):
+        """The standardized continuous coordinates of the candidates and the reference points of :meth:`design_batch`
+        (``(M, n_cont)``, ``(R, n_cont)``; each given as a parray or such an array, or drawn: seeded quasi-random points inside
+        ``bounds``, default the data's limits), the continuous dims, and ``full(Z)``, which completes them to model points."""
+        if self.distributed:
+            raise NotImplementedError(f"{what}: the rectangular posterior covariance is built on the single-device engine only "
+                                      "(the factor of a distributed GP is spread over ranks)")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError(f"{what}: the rectangular posterior covariance is built on the single-device engine only, "
+                                      "not for the Kronecker path (pass kronecker=False)")
+        _, cont, cols, full = self._acquisition_problem(output, "UCB", True, categorical_levels, None)
+        if bounds is None:
+            Xd = np.asarray(self.model.X, float)[:, cols]
+            lo, hi = Xd.min(axis=0), Xd.max(axis=0)
+        else:
+            both = np.array([np.asarray(bounds.z[d + "_z"].values(), float).ravel() for d in cont])
+            if both.shape != (len(cont), 2):
+                raise ValueError("bounds must hold two entries (lower, upper) per continuous dimension")
+            lo, hi = both.min(axis=1), both.max(axis=1)
+        seed = self.seed if seed is None else seed
+
+        def drawn(n, stream):
+            try:
+                from scipy.stats import qmc
+
+                with warnings.catch_warnings():  # (a Sobol' sample whose size is no power of two: still a fine design)
+                    warnings.simplefilter("ignore", UserWarning)
+                    u = qmc.Sobol(len(cont), seed=np.random.default_rng([seed, stream])).random(int(n))
+            except ImportError:
+                u = np.random.default_rng([seed, stream]).uniform(size=(int(n), len(cont)))
+            return lo + (hi - lo) * u
+
+        def given(points, name):
+            if hasattr(points, "z"):
+                Z = np.column_stack([np.asarray(points.z[d + "_z"].values(), float).ravel() for d in cont])
+            else:
+                Z = np.asarray(points, float).reshape(-1, len(cont))
+            if len(Z) < 1:
+                raise ValueError(f"{what}: {name} holds no point")
+            return Z
+
+        Zc = drawn(n_candidates, 0) if candidates is None else given(candidates, "candidates")
+        Zr = drawn(n_reference, 1) if reference is None else given(reference, "reference")
+        return Zc, Zr, cont, full
+
+    def design_batch(self, q, candidates=None, reference=None, n_candidates=1024, n_reference=4096, bounds=None,
+                     categorical_levels=None, output=None, weights=None, allow_repeats=True, with_noise=True, seed=None):
+        """Which ``q`` conditions to run next to learn the surface as a whole: a greedy batch by integrated variance reduction
+        (IVR, also called ALC), one call into ``gmb_design_batch`` against the factor :meth:`find_MAP` left resident.
+
+        Measuring at a candidate c lowers the latent variance at every point r by ``cov(c, r)^2 / (var f(c) + noise(c))`` -- in
+        closed form, whatever will be observed, so no value is fantasised (unlike ``propose_continuous(sequential=True)``,
+        which optimises an acquisition of the mean).  The score of a candidate is that reduction summed over the ``reference``
+        points with ``weights`` (default ``1 / R`` each), which stand for the region of interest; each pick conditions the
+        posterior before the next.  ``candidates`` and ``reference``: parrays, or ``(n, n_cont)`` arrays of standardized
+        continuous coordinates in ``continuous_dims`` order; default ``n_candidates`` / ``n_reference`` seeded quasi-random
+        points inside ``bounds`` (a parray with two entries per continuous dimension; default the data's limits).
+        Categorical coordinates are fixed through ``categorical_levels`` and ``output`` names the output, as in
+        :meth:`propose_continuous`.  With ``with_noise`` (a measurement carries the model's noise) and ``allow_repeats`` a
+        candidate may be picked again: a replicate, where it teaches more than a new condition.
+
+        Returns the picked points as a parray in pick order, repeats included (fewer than ``q`` once no candidate lowers the
+        variance any further), and sets :attr:`design_picks` (candidate indices), :attr:`design_gains` (the variance each pick
+        removes), :attr:`design_ivar0` (the weighted variance over the reference points before any pick: ``gains / ivar0`` are
+        fractions), :attr:`design_scores` (the step-0 score of every candidate) and :attr:`design_candidates` (the candidates,
+        a parray).  Covers one-term and additive models as a whole; not the Kronecker or distributed paths."""
+        q = int(q)
+        if q < 0:
+            raise ValueError(f"q must be >= 0, got {q}")
+        Zc, Zr, cont, full = self._design_points("design_batch", candidates, reference, n_candidates, n_reference, bounds,
+                                                 categorical_levels, output, seed)
+        picks, gains, scores, ivar0 = self.engine.design_batch(full(Zc), full(Zr), q, weights=weights, with_noise=with_noise,
+                                                               allow_repeats=allow_repeats)
+        picks = np.asarray(picks, dtype=np.int64)
+        self.design_picks, self.design_gains, self.design_ivar0, self.design_scores = picks, np.asarray(gains, float), float(ivar0), scores
+        self.design_candidates = self.parray(**{d: Zc[:, k] for k, d in enumerate(cont)}, stdzd=True)
+        chosen = Zc[picks[picks >= 0]]
+        return self.parray(**{d: chosen[:, k] for k, d in enumerate(cont)}, stdzd=True)
+
+    def variance_reduction(self, candidates, reference, bounds=None, categorical_levels=None, output=None, weights=None,
+                           with_noise=True):
+        """The integrated variance reduction of every candidate on its own -- :meth:`design_batch`'s step-0 score, its ``q = 0``
+        form: how much one measurement there would lower the weighted latent variance over ``reference``.  Returns the scores
+        (one per candidate) and sets :attr:`design_ivar0`."""
+        Zc, Zr, _, full = self._design_points("variance_reduction", candidates, reference, 0, 0, bounds, categorical_levels, output, None)
+        _, _, scores, ivar0 = self.engine.design_batch(full(Zc), full(Zr), 0, weights=weights, with_noise=with_noise, allow_repeats=True)
+        self.design_ivar0 = float(ivar0)
+        return scores
+
     def decompose_grid(self, output=None, categorical_levels=None):
         """:meth:`decompose_points` on the grid :meth:`prepare_grid` left behind, every level in the grid's shape."""
         if self.grid_points is None:

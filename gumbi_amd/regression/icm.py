@@ -273,6 +273,10 @@ class IcmEngine:
     def predict_groups(self, Xs, offsets, weights=None, cov=False, terms=None):
         raise NotImplementedError("predict_groups: group averages of the posterior are not built for the Kronecker engine (pass kronecker=False)")
 
+    def design_batch(self, Xc, Xr, q, weights=None, with_noise=True, allow_repeats=True):
+        raise NotImplementedError("design_batch: the rectangular posterior covariance of the candidates and the reference points is "
+                                  "built on the single-device engine only, not for the Kronecker engine (pass kronecker=False)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

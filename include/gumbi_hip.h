@@ -499,6 +499,38 @@ int gmb_predict_slope_terms(gmb_engine* e, uint32_t terms, const double* Xs, int
  * max(128, mt_max / Dc / 128 * 128), mt_max a prediction's largest M-tile.  GMB_EINVAL for Np < 1 or Dc outside 1 .. 24. */
 int64_t gmb_debug_slope_tile_rows(int64_t Np, int32_t Dc);
 
+/* ---- a batch of experiments: greedy integrated variance reduction (ABI stays 16: new functions only, no change of layout) ------
+ * Which q of the M candidates Xc, measured next, teach most about the surface over the R reference points Xr?  A GP's posterior
+ * covariance does not depend on y: measuring at c lowers the variance at r by cov(c, r)^2 / (var f(c) + noise(c)).  With
+ * P = [Xc; Xr] and D = C(Xc, P), the M x (M + R) LATENT posterior covariance, step t = 0 .. q - 1 is
+ *   s_a    = D[a, a] + noise_a                       (noise_a: what gmb_predict(with_noise = 1) adds at candidate a; 0 without)
+ *   gain_a = sum_r w_r D[a, M + r]^2 / s_a           (candidates with s_a <= 0 or not finite, or masked: excluded)
+ *   picks[t] = argmax gain_a (ties: lowest index), gains[t] = its gain
+ *   D[a, p] -= (D[c, a] * D[c, p]) * (1 / s_c)       for all a, p, c = picks[t]
+ * allow_repeats = 0 masks a picked candidate; with allow_repeats = 1 and noise it may be picked again (a replicate).  When no
+ * candidate has a positive finite gain the loop stops: the remaining picks are -1, their gains 0.
+ *
+ * Xc: M x D and Xr: R x D row-major with leading dimensions ldc, ldr >= D; w: R weights >= 0, NULL = 1 / R each; picks, gains: q
+ * values; score0 (M values, may be NULL): the step-0 gain of every candidate (0 for an excluded one) -- q = 0 computes only
+ * these; ivar0 (may be NULL): sum_r w_r var f(r) before any pick, by the prediction's own variance reduction.  All in `memspace`.
+ *
+ * Readiness is gmb_predict_joint's: a complete, unconsumed single-engine factor.  GMB_EINVAL with a text for M < 1, R < 1, q < 0,
+ * null Xc / Xr (picks / gains with q > 0), ldc < D, ldr < D, a negative or non-finite weight and a NaN coordinate (device-side
+ * arguments are copied to the host for these checks).  The candidates must fit one M-tile of a prediction (V within 8 GiB, at
+ * most 32768 rows); that, and a request the device cannot hold, return GMB_ENOMEM with the bytes in gmb_last_error before
+ * anything is launched or written.  The factor, v, both alphas, U, L^-1, their flags and the joint state are left as found.  No
+ * atomics, fixed-order sums: the same bits call after call. */
+int gmb_design_batch(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, const double* Xr, int64_t R, int64_t ldr,
+                     const double* w, int32_t q, int32_t with_noise, int32_t allow_repeats, int64_t* picks, double* gains,
+                     double* score0, double* ivar0, int32_t memspace);
+/* Host only: the plan of gmb_design_batch behind Np (padded) training points.  Writes at most `cap` values to `out` (may be
+ * NULL) and returns how many there are: Mc (padded candidates), ld (doubles per row of D), mt_max, mt (rows of the prediction
+ * workspace), ntile, nchunk, the step kernel's chunk (columns) and rows per workgroup, the bytes of the call's own buffers for
+ * D = 1, q = 0; then per point tile (first stacked index, count, padded count, first column of D); then per column chunk
+ * (first column, end).  A refusal returns -(code): 1 M < 1, 2 R < 1, 3 Np no positive multiple of 128, 4 the candidates exceed
+ * one M-tile, 5 R > 2^30. */
+int64_t gmb_debug_design_plan(int64_t Np, int64_t M, int64_t R, int64_t* out, int64_t cap);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
