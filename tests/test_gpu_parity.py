@@ -598,6 +598,21 @@ def test_additive_model_matches_oracle(gpu, two_outputs, lin, hetero, n):
 # ----------------------------------------------------------------------------------------------
 # device tests of the composite gradient and of the pairwise-distance reduction (restored: ADVICE r02)
 # ----------------------------------------------------------------------------------------------
+def assert_gradient_blocks_match_the_oracle(spec, theta, X, y, grads):
+    """The per-component comparison beside the max-norm one: every entry of each gradient within
+    composite_reference.float64_bar of the float64 oracle's (direct distances) -- 2 (4 + cond(Sigma)) eps A_p, A_p the size of
+    the sum that component is the remainder of -- reported as the worst entry of every parameter block.  (The max-norm bar
+    sees the largest component only: a table partial a hundred times smaller may be all wrong under it.)"""
+    import composite_reference as CR
+
+    g_r = O.nlml_and_grad(spec, theta, X, y, dist_mode="direct")[1]
+    bar, _ = CR.float64_bar(spec, theta, X, CR.oracle_m(spec, theta, X, y))
+    for g in grads:
+        worst = CR.worst_by_block(spec, np.abs(g - g_r) / bar)
+        print("BLOCKS " + "  ".join(f"{b} {r:.3g}" for b, r in worst.items()))
+        assert all(r <= 1.0 for r in worst.values()), worst
+
+
 def test_composite_model_gradient_and_prediction(gpu):
     """Linear x coregion x two outputs x heteroskedastic noise on ONE GPU: every accumulator class of the fused
     trace reductions (lengthscales, eta, tau, c, coregion tables, sigma, noise table) against the golden gradient."""
@@ -610,6 +625,7 @@ def test_composite_model_gradient_and_prediction(gpu):
     assert np.isclose(val, float(GOLD[f"{case}/nlml"]), rtol=1e-10)
     g_r = GOLD[f"{case}/grad"]
     assert np.max(np.abs(g - g_r)) < 1e-8 * max(1.0, np.max(np.abs(g_r)))
+    assert_gradient_blocks_match_the_oracle(spec, theta, X, y, [g])
     mu, var = eng.predict(Xs, with_noise=True)  # the factor survives the gradient
     mu_r, var_r = O.predict(spec, theta, X, y, Xs, with_noise=True, dist_mode="direct")
     assert rel(mu, mu_r) < 1e-8 and np.max(np.abs(var - var_r)) < 1e-9
@@ -1010,11 +1026,14 @@ def test_composite_model_gradient_through_the_fused_launch(gpu):
     theta = GOLD["composite_N140/theta"]
     val_r, grad_r = O.nlml_and_grad(spec, theta, X, y)
     eng = make_engine(spec, theta, X, y)
+    grads = []
     for scheme in (eng.GRAD_LAUNCH_TREE, eng.GRAD_FUSED):
         eng.set_grad_scheme(scheme)
         val, g = eng.evaluate(theta)
         assert abs(val - val_r) < 1e-10 * max(1.0, abs(val_r)) and rel(g, grad_r) < 1e-8
+        grads.append(g)
     eng.close()
+    assert_gradient_blocks_match_the_oracle(spec, theta, X, y, grads)
 
 
 @pytest.mark.parametrize("N", [300, 3000])
