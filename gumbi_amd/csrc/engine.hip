@@ -51,6 +51,7 @@
 #include "group_average.hpp"
 #include "predict_slope.hpp"
 #include "design_batch.hpp"
+#include "fitc.hpp"
 
 using namespace gmb;
 
@@ -89,10 +90,13 @@ enum EvKind : int {
                               // flags = 0 the cross part A, 1 the prior part Q, 2 its diagonal only)
   EV_SLOPE_COV = 19,          // gmb_predict_slope: the derivative cross-covariance launch of the first selected term (mt x nt tiles
                               // of 128 x 128 pairs, k = differentiable columns written per pair)
-  EV_DESIGN = 20              // gmb_design_batch: a PHASE, around the launches listed above (flags = 0 the solved rows V of one point
+  EV_DESIGN = 20,             // gmb_design_batch: a PHASE, around the launches listed above (flags = 0 the solved rows V of one point
                               // tile, 1 its prior + rank-N update, 2 the greedy loop: mt = candidates, nt = doubles per row of D, k = picks)
+  EV_FITC = 21                // the sparse path's own launches (mt x nt tiles of the block): flags = 0 a cross-covariance against Z, 1 a
+                              // pass V L^-1, 2 a column / row / adjoint / transpose pass over a block, 3 a derivative reduction or the
+                              // prediction's reduction
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_DESIGN); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_FITC); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -199,6 +203,7 @@ struct gmb_engine {
   SlopeWorkspace slope;     // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
   DesignWorkspace dz;       // gmb_design_batch (design_batch.hpp), beside a prediction's workspace of one point tile
+  FitcState fitc;           // the sparse (FITC) path: everything it keeps (workspaces.hpp), nothing of it shared with the exact path
 
   // gradient workspace
   DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
@@ -519,7 +524,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_TERM_GRAM:
       case EV_GROUP_COV:
       case EV_SLOPE_COV:
-      case EV_DESIGN: break;
+      case EV_DESIGN:
+      case EV_FITC: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -2468,6 +2474,7 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   e->fs.feature_map_changed();  // (no factorisation of THIS data has been attempted: gmb_debug_assume_factored must refuse)
   e->have_theta = false;
   e->N = 0;
+  e->fitc.drop_inducing();
   stale_sized_by_n(e);
   // (here only: new data gets prepared points of exactly its own size.  resize_n keeps a block that is large enough -- after
   // a truncation it is larger than Nr asks for, and renewing it there would move gmb_resident_bytes.)
@@ -2504,6 +2511,7 @@ int gmb_set_y(gmb_engine* e, const double* y, int32_t memspace) {
   HIP_TRY(e, hipSetDevice(e->device));
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   e->fs.inputs_changed();  // the y row of the factor (v = L^-1 y) belongs to the old observations
+  e->fitc.resident = false;
   HIP_TRY(e, hipMemcpyAsync(e->dy, y, e->N * sizeof(double), kind, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller may reuse its buffer
   return GMB_OK;
@@ -2517,6 +2525,7 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->have_spec = true;
   e->have_theta = false;
   e->fs.inputs_changed();
+  e->fitc.drop_inducing();
   e->nc_pad = pick_nc(spec->n_cont);
   e->periodic = 0;
   e->pts.stale();
@@ -2545,6 +2554,7 @@ int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t
   // the prepared coordinates and everything factored from them belong to the previous feature map
   e->have_theta = false;
   e->fs.feature_map_changed();
+  e->fitc.drop_inducing();
   return GMB_OK;
 }
 
@@ -2561,6 +2571,7 @@ static int set_theta(gmb_engine* e, const double* theta, int32_t n, const EvalPl
   HIP_TRY(e, hipSetDevice(e->device));
   e->theta.assign(theta, theta + n);
   e->fs.inputs_changed();
+  e->fitc.resident = false;  // (Lu, L_B, c belong to the previous theta)
   int rc = apply_theta(e);
   if (rc) return rc;
   if ((rc = e->pts.reserve(e->pool, e->Nr))) return rc;
@@ -2963,6 +2974,7 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
     if ((rc = newA.reserve(e->pool, ld_new * Np_new))) return rc;
   }
   e->fs.resized(live);
+  e->fitc.resident = false;
   auto bail = [&](int code) {  // a failure half-way: no factor; the data may be of either size, so nothing is ready
     e->fs.resize_failed();
     e->have_theta = false;
@@ -4699,9 +4711,471 @@ int design_batch_impl(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, c
   return GMB_OK;
 }
 
+// ---- the sparse (FITC) path: fitc.hpp, fitc_plan.hpp, DESIGN 3.17 ------------------------------------------------------------------
+// The inducing points stand where the training set stands in a prediction: K(X-tile, Z) is the cross-covariance launch, A^T the
+// triangular solve against Lu, the two m x m factors go through chol_factor as matrices of their own (as the joint posterior's C
+// does).  Nothing of the exact path is touched: the factor buffer, dW, the prediction workspaces stay as they are (and unallocated
+// if they were); theta is set as gmb_set_theta sets it, so a resident exact factor is stale afterwards by FactorState's own rules.
+
+FactorRef fitc_factor_u(FitcState& s) { return FactorRef{s.dKuu, s.mr, s.m, s.mp, s.mr, s.dDinvU, s.dscalU, &s.dctU}; }
+FactorRef fitc_factor_b(FitcState& s) { return FactorRef{s.dB, s.mr, s.m, s.mp, s.mr, s.dDinvB, s.dscalB, &s.dctB}; }
+PointSet fitc_z_set(const FitcState& s) { return PointSet{s.zpts.xs, s.zpts.xl, s.zpts.cat, s.m, s.mr}; }
+
+// the models the sparse path is built for
+int fitc_scope(gmb_engine* e, const char* what) {
+  const gmb_kernel_spec& sp = e->spec;
+  if (sp.n_coreg != 0 || sp.out_col >= 0)
+    return fail(e, GMB_EINVAL, "%s: the sparse approximation supports one output and no categorical dimensions (n_coreg = %d, out_col = %d)",
+                what, sp.n_coreg, sp.out_col);
+  if (sp.additive) return fail(e, GMB_EINVAL, "%s: the sparse approximation does not support additive models", what);
+  if (sp.n_lin != 0) return fail(e, GMB_EINVAL, "%s: the sparse approximation does not support linear dimensions (n_lin = %d)", what, sp.n_lin);
+  if (e->periodic != 0) return fail(e, GMB_EINVAL, "%s: the sparse approximation does not support periodic kernels", what);
+  if (e->solve_hook || e->dist_mode != 0)
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode)", what);
+  return GMB_OK;
+}
+
+int fitc_plan_for(gmb_engine* e, const char* what, int64_t m, FitcPlan* pl) {
+  switch (pl->make(e->N, m)) {
+    case 0: return GMB_OK;
+    case 2: return fail(e, GMB_EINVAL, "%s: m = %lld inducing points (at least 1)", what, (long long)m);
+    case 3: return fail(e, GMB_EINVAL, "%s: m = %lld inducing points exceed the limit of %lld", what, (long long)m, (long long)FITC_MAX_M);
+    default: return fail(e, GMB_EINVAL, "%s: N = %lld is out of range", what, (long long)e->N);
+  }
+}
+
+// measure a list of buffers against the device, then allocate it (`list(v)`: one of workspaces.hpp's fitc_*_buffers over a visitor)
+template <typename List>
+int fitc_reserve(gmb_engine* e, const char* what, const FitcPlan& pl, List&& list) {
+  Budget need;
+  list(need);
+  double free_b;
+  int rc;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
+  if (need.fresh > free_b)
+    return fail(e, GMB_ENOMEM, "%s: N = %lld with m = %lld inducing points needs %.0f bytes on the device (m x m: %.0f each, an m x tile block of "
+                               "%lld columns: %.0f), %.0f more than the engine holds now; %.0f bytes are free -- nothing was computed",
+                what, (long long)pl.N, (long long)pl.m, need.total, 8.0 * (double)pl.mr * (double)pl.mp, (long long)pl.tmax,
+                8.0 * (double)pl.mr * (double)pl.tmax, need.fresh, free_b);
+  Reserver take{e->pool};
+  list(take);
+  return take.rc;
+}
+
+int fitc_set_inducing_impl(gmb_engine* e, const double* Z, int64_t m, int64_t ldz, int32_t memspace) {
+  const char* what = "gmb_fitc_set_inducing";
+  if (!e) return GMB_EINVAL;
+  FitcState& s = e->fitc;
+  s.drop_inducing();
+  if (e->N <= 0) return fail(e, GMB_EINVAL, "gmb_set_data must precede %s", what);
+  if (!e->have_spec) return fail(e, GMB_EINVAL, "gmb_set_kernel must precede %s", what);
+  int rc = fitc_scope(e, what);
+  if (rc) return rc;
+  if (!Z || ldz < e->D) return fail(e, GMB_EINVAL, "%s: bad Z/ldz", what);
+  FitcPlan pl;
+  if ((rc = fitc_plan_for(e, what, m, &pl))) return rc;
+  if (memspace != GMB_DEVICE)
+    for (int64_t i = 0; i < m; ++i)
+      for (int c = 0; c < e->D; ++c)
+        if (!std::isfinite(Z[i * ldz + c])) return fail(e, GMB_EINVAL, "%s: Z[%lld, %d] is not finite", what, (long long)i, c);
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int D = e->D;
+  if ((rc = fitc_reserve(e, what, pl, [&](auto& v) { return fitc_fixed_buffers(s, pl, D, v); }))) return rc;
+  const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIP_TRY(e, hipMemcpy2DAsync(s.dZ, D * sizeof(double), Z, ldz * sizeof(double), D * sizeof(double), m, kind, e->stream));
+  HIP_TRY(e, hipMemsetAsync(s.dzero, 0, (size_t)pl.mr * sizeof(double), e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  s.m = pl.m, s.mp = pl.mp, s.mr = pl.mr;
+  s.have_z = true;
+  return GMB_OK;
+}
+
+// K(P, Z) for the prepared points P (padded to `pad` rows) into V (pad x mp, P's index fastest)
+int fitc_cross_cov(gmb_engine* e, const PointSet& rows, int64_t pad, double* V) {
+  const FitcState& s = e->fitc;
+  CovTileArgs a{};
+  a.p = e->terms[0].cp;
+  a.rows = rows;
+  a.cols = fitc_z_set(s);
+  a.out = V;
+  a.ldo = pad;
+  a.ti = (int)(pad / TILE);
+  a.tj = (int)(s.mp / TILE);
+  a.mode = COV_CROSS;
+  ev_begin(e, e->stream, EV_FITC, 0.0, a.ti, a.tj, 0, 0);
+  const int rc = launch_cov(e, a);
+  ev_end(e);
+  return rc;
+}
+
+// V <- V L^-T (pad rows): the blocked solve of a prediction.  The columns m .. mp - 1 belong to no inducing point and the border
+// row of the factor reaches them: cleared, as the joint posterior clears them.
+int fitc_solve_lt(gmb_engine* e, const FactorRef& f, double* V, int64_t pad) {
+  int rc = trsm_cols(e, e->stream, f, V, pad, (int)(pad / TILE), 0, (int)(f.Np / TILE), EV_CHOL_SOLVE_GEMM, EV_SOLVE_STRIP);
+  if (rc) return rc;
+  if (f.Np > f.N) HIP_TRY(e, hipMemsetAsync(V + f.N * pad, 0, (size_t)((f.Np - f.N) * pad) * sizeof(double), e->stream));
+  return GMB_OK;
+}
+
+// V <- V L^-1 (pad rows): the second triangular pass of gmb_predict_with_grad, on this factor
+int fitc_solve_l(gmb_engine* e, const FactorRef& f, double* V, int64_t pad) {
+  const TriOperand L{f.A, f.ld, f.A, f.ld, (int64_t)TILE * (f.ld + 1)};
+  const int nb = (int)(f.Np / TILE);
+  ev_begin(e, e->stream, EV_FITC, (double)pad * (double)f.N * (double)f.N, (int)(pad / TILE), nb, 0, 1);
+  for (int b = nb - 1; b >= 0; --b) {
+    hipLaunchKernelGGL(vsolve_diag_kernel, dim3((unsigned)(pad / VS_ROWS)), dim3(VS_ROWS), 0, e->stream, L, (int64_t)b, f.N, V, pad);
+    if (b > 0)
+      hipLaunchKernelGGL(vsolve_update_kernel, dim3((unsigned)(pad / VS_PTS), (unsigned)b), dim3(256), 0, e->stream, L, (int64_t)b, f.N, V, pad);
+  }
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// one of the two m x m factorisations, by the schedule chol_factor gives a matrix of its size; synchronises and looks at the result
+int fitc_factor(gmb_engine* e, const FactorRef& f, const char* which) {
+  HIP_TRY(e, hipMemsetAsync(f.scal, 0, (size_t)SCAL_GACC_AT * sizeof(double), e->stream));
+  CholResult res;
+  int rc = chol_factor(e, f, CholOpts{}, &res);
+  if (rc) return rc;
+  int32_t info = 0;
+  uint32_t ab = 0;
+  HIP_TRY(e, hipMemcpyAsync(&info, f.info(), sizeof info, hipMemcpyDeviceToHost, e->stream));
+  if (res.tiles) HIP_TRY(e, hipMemcpyAsync(&ab, *f.ct + 1, sizeof ab, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (ab != 0) return fail(e, GMB_EHIP, "gmb_fitc_evaluate: the tile Cholesky of %s waited longer than its time-out for a tile (launch abandoned)", which);
+  if (info != 0) {
+    e->notpd = (int64_t)info - 1;
+    return fail(e, GMB_ENOTPD, "gmb_fitc_evaluate: %s is not positive definite at row %lld", which, (long long)e->notpd);
+  }
+  return GMB_OK;
+}
+
+// the columns [first, first + count) of the training points as a point set of their own (the prepared arrays' stride stays Nr)
+PointSet fitc_x_tile(const gmb_engine* e, const FitcTile& tl) {
+  return PointSet{e->pts.xs + tl.first, e->pts.xl + tl.first, e->pts.cat + tl.first, tl.count, e->Nr};
+}
+
+template <int KIND>
+void launch_fitc_deriv_nc(gmb_engine* e, const FitcDerivArgs& a, dim3 grid) {
+  switch (e->nc_pad) {
+    case 1: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 1>), grid, dim3(256), 0, e->stream, a); break;
+    case 2: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 2>), grid, dim3(256), 0, e->stream, a); break;
+    case 4: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 4>), grid, dim3(256), 0, e->stream, a); break;
+    case 8: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 8>), grid, dim3(256), 0, e->stream, a); break;
+    default: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 16>), grid, dim3(256), 0, e->stream, a); break;
+  }
+}
+
+// sum G o dk(rows, cols) / dtheta over `pad_rows` x `pad_cols` padded pairs, added to acc[0 .. FITC_DERIV_SUMS)
+int fitc_deriv(gmb_engine* e, const PointSet& rows, int64_t pad_rows, const PointSet& cols, int64_t pad_cols, const double* G, int64_t ldg,
+               double* acc) {
+  FitcState& s = e->fitc;
+  FitcDerivArgs a{};
+  a.p = e->terms[0].cp;
+  a.rows = rows;
+  a.cols = cols;
+  a.G = G;
+  a.ldg = ldg;
+  a.ti = (int)(pad_rows / TILE);
+  a.tj = (int)(pad_cols / TILE);
+  a.part = s.dredpart;
+  const int64_t nblk = (int64_t)a.ti * a.tj;
+  const dim3 grid((unsigned)nblk);
+  ev_begin(e, e->stream, EV_FITC, 0.0, a.ti, a.tj, 0, 3);
+  switch (a.p.kind) {
+    case GMB_EXPQUAD: launch_fitc_deriv_nc<0>(e, a, grid); break;
+    case GMB_MATERN52: launch_fitc_deriv_nc<1>(e, a, grid); break;
+    case GMB_MATERN32: launch_fitc_deriv_nc<2>(e, a, grid); break;
+    case GMB_MATERN12: launch_fitc_deriv_nc<3>(e, a, grid); break;
+    default: launch_fitc_deriv_nc<4>(e, a, grid); break;
+  }
+  hipLaunchKernelGGL(fitc_fold_kernel, dim3(1), dim3(256), 0, e->stream, s.dredpart, nblk, FITC_DERIV_SUMS, 0, FITC_DERIV_SUMS, acc, 1);
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// A^T of tile `tl` into V1: the cross-covariance against Z and the solve against Lu (both passes form it; DESIGN 3.17 says why)
+int fitc_tile_a(gmb_engine* e, const FitcTile& tl) {
+  FitcState& s = e->fitc;
+  int rc = fitc_cross_cov(e, fitc_x_tile(e, tl), tl.tpad, s.sw.V1);
+  if (rc) return rc;
+  return fitc_solve_lt(e, fitc_factor_u(s), s.sw.V1, tl.tpad);
+}
+
+// pass 1: Lu, lambda, B = L_B L_B^T, c, w and the NLML
+int fitc_pass1(gmb_engine* e, const FitcPlan& pl, double* nlml) {
+  FitcState& s = e->fitc;
+  const CovParams& cp = e->terms[0].cp;
+  int rc;
+  if ((rc = prep_points(e, s.dZ, s.m, e->D, s.mr, s.zpts.xs, s.zpts.xl, s.zpts.cat))) return rc;
+  HIP_TRY(e, hipMemsetAsync(s.dacc, 0, (size_t)FITC_ACC_DOUBLES * sizeof(double), e->stream));
+  {  // Kuu = k(Z, Z) + jitter I: the training build's launch on Z, a zero border row where y would sit
+    CovTileArgs a{};
+    a.p = cp;
+    a.p.sigma2 = 0.0;
+    a.rows = a.cols = fitc_z_set(s);
+    a.out = s.dKuu;
+    a.ldo = s.mr;
+    a.ti = (int)(s.mr / TILE);
+    a.tj = (int)(s.mp / TILE);
+    a.mode = COV_TRAIN;
+    a.lower_only = 1;
+    a.tri_grid = 1;
+    a.y = s.dzero;
+    if ((rc = launch_cov(e, a))) return rc;
+  }
+  if ((rc = fitc_factor(e, fitc_factor_u(s), "k(Z, Z) + jitter I"))) return rc;
+  hipLaunchKernelGGL(fitc_init_b_kernel, dim3((unsigned)((s.mr + 255) / 256), (unsigned)s.mp), dim3(256), 0, e->stream, s.dB.p, s.mr, s.mp);
+  for (int64_t t = 0; t < pl.ntile; ++t) {
+    const FitcTile tl = pl.tile(t);
+    if ((rc = fitc_tile_a(e, tl))) return rc;
+    FitcColArgs c{};
+    c.At = s.sw.V1;
+    c.ldt = tl.tpad;
+    c.tc = tl.count;
+    c.m = (int32_t)s.m;
+    c.mr = s.mr;
+    c.y = e->dy + tl.first;
+    c.kdiag = cp.eta2;
+    c.sigma2 = cp.sigma2;
+    c.lam = s.dlam + tl.first;
+    c.S = s.gw.S1;
+    c.part = s.dcolpart + (tl.first / FITC_COL_BLOCK) * FITC_COL_SUMS;
+    ev_begin(e, e->stream, EV_FITC, 0.0, (int)(tl.tpad / TILE), (int)(s.mp / TILE), 0, 2);
+    hipLaunchKernelGGL(fitc_column_kernel, dim3((unsigned)(tl.tpad / FITC_COL_BLOCK)), dim3(256), 0, e->stream, c);
+    ev_end(e);
+    HIP_TRY(e, hipGetLastError());
+    GemmArgs g{};  // B += S S^T on the lower tiles of the bordered layout, the tiles in ascending order
+    g.C = s.dB;
+    g.ldc = s.mr;
+    g.A = s.gw.S1;
+    g.lda = s.mr;
+    g.B = s.gw.S1;
+    g.ldb = s.mr;
+    g.mt = (int)(s.mp / TILE);
+    g.nt = (int)(s.mr / TILE);
+    g.k = (int)tl.tpad;
+    g.alpha = 1.0;
+    g.beta = 1.0;
+    g.tri = 1;
+    if ((rc = launch_gemm(e, e->stream, g, EV_GRAD_GEMM))) return rc;
+  }
+  if (s.mp > s.m)
+    hipLaunchKernelGGL(fitc_fix_b_kernel, dim3((unsigned)((s.mr + 255) / 256), (unsigned)(s.mp - s.m)), dim3(256), 0, e->stream, s.dB.p, s.mr, s.m);
+  HIP_TRY(e, hipGetLastError());
+  if ((rc = fitc_factor(e, fitc_factor_b(s), "B = I + A Lambda^-1 A^T"))) return rc;
+  // c = row m of the factored bordered matrix, c^T c; the column sums; w = L_B^-T c by blocked back substitution
+  double* c = s.dcw;
+  double* w = s.dcw + s.mp;
+  double* rhs = s.dcw + 2 * s.mp;
+  HIP_TRY(e, hipMemsetAsync(s.dcw, 0, (size_t)(3 * s.mp) * sizeof(double), e->stream));
+  hipLaunchKernelGGL(extract_v_kernel, dim3(EXTRACT_V_BLOCKS), dim3(TILE), 0, e->stream, s.dB.p, s.mr, s.m, c, s.dscalB + 1);
+  hipLaunchKernelGGL(fitc_fold_kernel, dim3(1), dim3(256), 0, e->stream, s.dcolpart.p, pl.col_blocks(), FITC_COL_SUMS, 0, 2, s.dacc.p, 0);
+  HIP_TRY(e, hipMemcpyAsync(rhs, c, (size_t)s.m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  const TriOperand L{s.dB, s.mr, s.dB, s.mr, (int64_t)TILE * (s.mr + 1)};
+  for (int b = (int)(s.mp / TILE) - 1; b >= 0; --b) {
+    hipLaunchKernelGGL(backsub_diag_kernel, dim3(1), dim3(256), 0, e->stream, L, (int64_t)b, s.m, rhs, w);
+    if (b > 0) hipLaunchKernelGGL(backsub_update_kernel, dim3((unsigned)(32 * b)), dim3(256), 0, e->stream, L, (int64_t)b, s.m, w, rhs);
+  }
+  HIP_TRY(e, hipGetLastError());
+  double hb[2] = {0.0, 0.0}, ha[2] = {0.0, 0.0};
+  HIP_TRY(e, hipMemcpyAsync(hb, s.dscalB, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(ha, s.dacc, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *nlml = 0.5 * ha[0] + hb[0] + 0.5 * (ha[1] - hb[1]) + 0.5 * (double)e->N * std::log(2.0 * M_PI);
+  if (!std::isfinite(*nlml)) {
+    e->notpd = 0;
+    return fail(e, GMB_ENOTPD, "gmb_fitc_evaluate: the factorisation produced non-finite values");
+  }
+  return GMB_OK;
+}
+
+// pass 2: the gradient by reverse mode, tile by tile (fitc.hpp; the formulas are DESIGN 3.17's)
+int fitc_pass2(gmb_engine* e, const FitcPlan& pl, double* grad) {
+  FitcState& s = e->fitc;
+  const FactorRef fu = fitc_factor_u(s), fb = fitc_factor_b(s);
+  const double* w = s.dcw + s.mp;
+  int rc;
+  HIP_TRY(e, hipMemsetAsync(s.dP, 0, (size_t)(s.mp * s.mp) * sizeof(double), e->stream));
+  for (int64_t t = 0; t < pl.ntile; ++t) {
+    const FitcTile tl = pl.tile(t);
+    const int64_t tp = tl.tpad;
+    double* V1 = s.sw.V1;
+    double* V2 = s.sw.V2;
+    if ((rc = fitc_tile_a(e, tl))) return rc;  // A^T
+    HIP_TRY(e, hipMemcpyAsync(V2, V1, (size_t)(tp * s.mp) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    if ((rc = fitc_solve_lt(e, fb, V2, tp))) return rc;  // C^T = A^T L_B^-T
+    FitcRowArgs r{};
+    r.At = V1;
+    r.Ct = V2;
+    r.ldt = tp;
+    r.tc = tl.count;
+    r.m = (int32_t)s.m;
+    r.w = w;
+    r.y = e->dy + tl.first;
+    r.lam = s.dlam + tl.first;
+    r.alpha = s.dalpha + tl.first;
+    r.d = s.dd + tl.first;
+    r.part = s.dcolpart + (tl.first / FITC_COL_BLOCK) * FITC_COL_SUMS;
+    ev_begin(e, e->stream, EV_FITC, 0.0, (int)(tp / TILE), (int)(s.mp / TILE), 0, 2);
+    hipLaunchKernelGGL(fitc_row_kernel, dim3((unsigned)(tp / FITC_COL_BLOCK)), dim3(256), 0, e->stream, r);
+    ev_end(e);
+    HIP_TRY(e, hipGetLastError());
+    if ((rc = fitc_solve_l(e, fb, V2, tp))) return rc;  // H^T = Lambda^-1 C^T L_B^-1
+    ev_begin(e, e->stream, EV_FITC, 0.0, (int)(tp / TILE), (int)(s.mp / TILE), 0, 2);
+    hipLaunchKernelGGL(fitc_adjoint_kernel, dim3((unsigned)((tp + 255) / 256), (unsigned)s.mp), dim3(256), 0, e->stream, V2, V1, tp, tl.count,
+                       (int32_t)s.m, r.alpha, r.d, w);
+    ev_end(e);
+    HIP_TRY(e, hipGetLastError());
+    if ((rc = fitc_solve_l(e, fu, V2, tp))) return rc;  // G_uf^T = T^T Lu^-1
+    if ((rc = fitc_deriv(e, fitc_x_tile(e, tl), tp, fitc_z_set(s), s.mp, V2, tp, s.dacc + 8))) return rc;
+    // P += G_uf A^T: both blocks into the GEMM's operand layout (inducing index fastest), the tiles in ascending order
+    ev_begin(e, e->stream, EV_FITC, 0.0, (int)(tp / TILE), (int)(s.mp / TILE), 0, 2);
+    if ((rc = launch_transpose(e, e->stream, V1, tp, s.gw.S1, s.mr, (int)tp, (int)s.mp))) return rc;
+    if ((rc = launch_transpose(e, e->stream, V2, tp, s.gw.S2, s.mr, (int)tp, (int)s.mp))) return rc;
+    ev_end(e);
+    GemmArgs g{};
+    g.C = s.dP;
+    g.ldc = s.mp;
+    g.A = s.gw.S1;
+    g.lda = s.mr;
+    g.B = s.gw.S2;
+    g.ldb = s.mr;
+    g.mt = g.nt = (int)(s.mp / TILE);
+    g.k = (int)tp;
+    g.alpha = 1.0;
+    g.beta = 1.0;
+    if ((rc = launch_gemm(e, e->stream, g, EV_GRAD_GEMM))) return rc;
+  }
+  // G_uu = -1/2 P Lu^-1 (the factor -1/2 is the host's), reduced against dk(Z, Z)
+  if ((rc = fitc_solve_l(e, fu, s.dP, s.mp))) return rc;
+  if ((rc = fitc_deriv(e, fitc_z_set(s), s.mp, fitc_z_set(s), s.mp, s.dP, s.mp, s.dacc + 32))) return rc;
+  hipLaunchKernelGGL(fitc_fold_kernel, dim3(1), dim3(256), 0, e->stream, s.dcolpart.p, pl.col_blocks(), FITC_COL_SUMS, 2, 1, s.dacc + 2, 0);
+  HIP_TRY(e, hipGetLastError());
+  double h[FITC_ACC_DOUBLES];
+  HIP_TRY(e, hipMemcpyAsync(h, s.dacc, sizeof h, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  // chain rule (fitc.hpp: fitc_deriv_kernel): theta = [ls | eta | sigma]
+  const gmb_kernel_spec& sp = e->spec;
+  const gmb_engine::Term& tr = e->terms[0];
+  const double* uf = h + 8;
+  const double* uu = h + 32;
+  const double sum_d = h[2], eta = tr.eta;
+  const int n_ls = sp.ard ? sp.n_cont : 1;
+  for (int i = 0; i < n_ls; ++i) grad[i] = 0.0;
+  for (int c = 0; c < sp.n_cont; ++c) grad[sp.ard ? c : 0] += -2.0 * tr.pa.inv_ls[c] * (uf[c] - 0.5 * uu[c]);
+  grad[n_ls] = (2.0 / eta) * (uf[FITC_DERIV_SUMS - 1] - 0.5 * uu[FITC_DERIV_SUMS - 1]) + eta * sum_d;
+  grad[n_ls + 1] = e->theta[n_ls + 1] * sum_d;
+  for (int i = 0; i < n_ls + 2; ++i)
+    if (!std::isfinite(grad[i])) return fail(e, GMB_ENOTPD, "gmb_fitc_evaluate: the gradient is not finite");
+  return GMB_OK;
+}
+
+int fitc_evaluate_impl(gmb_engine* e, const double* theta, int32_t n, double* nlml, double* grad) {
+  const char* what = "gmb_fitc_evaluate";
+  if (!e || !theta || !nlml) return GMB_EINVAL;
+  FitcState& s = e->fitc;
+  if (!s.have_z) return fail(e, GMB_EINVAL, "%s: gmb_fitc_set_inducing has not been called for this data and kernel", what);
+  int rc = set_theta(e, theta, n, nullptr);  // (clears s.resident)
+  if (rc) return rc;
+  if ((rc = fitc_scope(e, what))) return rc;
+  e->notpd = -1;
+  FitcPlan pl;
+  if ((rc = fitc_plan_for(e, what, s.m, &pl))) return rc;
+  const int D = e->D;
+  if ((rc = fitc_reserve(e, what, pl, [&](auto& v) { return fitc_evaluate_buffers(s, pl, D, v); }))) return rc;
+  rc = fitc_pass1(e, pl, nlml);
+  if (!rc) {
+    s.resident = true;
+    if (grad) rc = fitc_pass2(e, pl, grad);
+  }
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  ev_collect(e);
+  if (rc) return rc;
+  HIP_TRY(e, sync);
+  return GMB_OK;
+}
+
+int fitc_predict_impl(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
+                      int32_t memspace) {
+  const char* what = "gmb_fitc_predict";
+  if (!e) return GMB_EINVAL;
+  FitcState& s = e->fitc;
+  if (!s.have_z) return fail(e, GMB_EINVAL, "%s: gmb_fitc_set_inducing has not been called for this data and kernel", what);
+  if (!s.resident || !e->have_theta)
+    return fail(e, GMB_EINVAL, "%s: no sparse state is resident for the current theta, data and inducing points: call gmb_fitc_evaluate first", what);
+  if (M < 0 || (M > 0 && (!Xs || !mean || !var)) || ldxs < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  FitcPlan pl;
+  int rc = fitc_plan_for(e, what, s.m, &pl);
+  if (rc) return rc;
+  const int64_t Mt = pl.predict_rows(M);
+  const int D = e->D;
+  if ((rc = fitc_reserve(e, what, pl, [&](auto& v) { return fitc_predict_buffers(s, pl, (double)Mt, D, v); }))) return rc;
+  const CopyKinds ck = copy_kinds(memspace);
+  const FactorRef fu = fitc_factor_u(s), fb = fitc_factor_b(s);
+  const double* w = s.dcw + s.mp;
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      HIP_TRY(e, hipMemcpy2DAsync(s.tp.Xs, D * sizeof(double), Xs + m0 * ldxs, ldxs * sizeof(double), D * sizeof(double), mc, ck.in, e->stream));
+      if ((rc = prep_points(e, s.tp.Xs, mc, D, mpad, s.tp.xs, s.tp.xl, s.tp.cat))) return rc;
+      const PointSet test{s.tp.xs, s.tp.xl, s.tp.cat, mc, mpad};
+      if ((rc = fitc_cross_cov(e, test, mpad, s.sw.V1))) return rc;
+      KssArgs k{};
+      k.p = e->terms[0].cp;
+      k.pts = test;
+      k.with_noise = with_noise;
+      k.kss = s.tp.kss;
+      hipLaunchKernelGGL(kss_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, e->stream, k);
+      if ((rc = fitc_solve_lt(e, fu, s.sw.V1, mpad))) return rc;  // As^T
+      HIP_TRY(e, hipMemcpyAsync(s.sw.V2, s.sw.V1, (size_t)(mpad * s.mp) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if ((rc = fitc_solve_lt(e, fb, s.sw.V2, mpad))) return rc;  // C*^T
+      ev_begin(e, e->stream, EV_FITC, 0.0, (int)(mpad / TILE), (int)(s.mp / TILE), 0, 3);
+      hipLaunchKernelGGL(fitc_predict_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, s.sw.V1.p, s.sw.V2.p, mpad, mc,
+                         (int32_t)s.m, w, s.tp.kss.p, s.tp.mean.p, s.tp.var.p);
+      ev_end(e);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, s.tp.mean, mc * sizeof(double), ck.out, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(var + m0, s.tp.var, mc * sizeof(double), ck.out, e->stream));
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, nullptr, tiles());
+}
+
 }  // namespace
 
 extern "C" {
+
+int gmb_fitc_set_inducing(gmb_engine* e, const double* Z, int64_t m, int64_t ldz, int32_t memspace) {
+  return fitc_set_inducing_impl(e, Z, m, ldz, memspace);
+}
+
+int gmb_fitc_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlml, double* grad) {
+  return fitc_evaluate_impl(e, theta, n, nlml, grad);
+}
+
+int gmb_fitc_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
+                     int32_t memspace) {
+  return fitc_predict_impl(e, Xs, M, ldxs, with_noise, mean, var, memspace);
+}
+
+int64_t gmb_debug_fitc_plan(int64_t N, int64_t m, int64_t* out, int64_t cap) {
+  FitcPlan pl;
+  const int bad = pl.make(N, m);
+  if (bad) return -(int64_t)bad;
+  FitcState st;  // (nothing allocated: a Budget only reads what the buffers hold)
+  Budget fixed, blocks, columns;
+  fitc_fixed_buffers(st, pl, 1, fixed);
+  fitc_block_buffers(st, pl, (double)pl.tmax, true, blocks);
+  fitc_column_buffers(st, pl, columns);
+  return fitc_plan_dump(pl, fixed.total, blocks.total, columns.total, out, cap);
+}
 
 int gmb_nlml(gmb_engine* e, double* nlml, double* grad) {
   int rc = require_ready(e, true);

@@ -11,6 +11,7 @@
 #pragma once
 #include "design_plan.hpp"
 #include "device_buffers.hpp"
+#include "fitc_plan.hpp"
 #include "slope_plan.hpp"  // SLOPE_MAX_COLS
 #include "workspace_sizes.hpp"
 
@@ -134,7 +135,90 @@ struct DesignWorkspace : Workspace<DesignWorkspace> {
   }
 };
 
+// The sparse (FITC) path (fitc.hpp).  Two m x tile blocks with the tile's columns fastest (what the cross-covariance
+// launch writes and the triangular solves work on) ...
+struct FitcSolveWorkspace : Workspace<FitcSolveWorkspace> {
+  DevBuf<double> V1, V2;
+  int64_t for_mp = 0;
+  template <class F>
+  bool each(double rows, int64_t mp, F&& f) { return f(V1, rows * (double)mp) && f(V2, rows * (double)mp); }
+  int64_t held(int64_t mp) const { return for_mp < mp ? 0 : rows; }
+  void sized_for(int64_t mp) { for_mp = mp; }
+};
+// ... two with the inducing index fastest (the GEMMs' operands: leading dimension mr, the border row included) ...
+struct FitcGemmWorkspace : Workspace<FitcGemmWorkspace> {
+  DevBuf<double> S1, S2;
+  int64_t for_mr = 0;
+  template <class F>
+  bool each(double rows, int64_t mr, F&& f) { return f(S1, rows * (double)mr) && f(S2, rows * (double)mr); }
+  int64_t held(int64_t mr) const { return for_mr < mr ? 0 : rows; }
+  void sized_for(int64_t mr) { for_mr = mr; }
+};
+// ... and the test points of one M-tile of gmb_fitc_predict, raw and prepared, with their results
+struct FitcTestPoints : Workspace<FitcTestPoints> {
+  DevBuf<double> Xs, xs, xl;
+  DevBuf<int32_t> cat;
+  DevBuf<double> kss, mean, var;
+  template <class F>
+  bool each(double Mt, int D, F&& f) {
+    return f(Xs, Mt * D) && f(xs, XS_ROWS * Mt) && f(xl, MAX_LIN * Mt) && f(cat, MAX_TABS * Mt) && f(kss, Mt) && f(mean, Mt) && f(var, Mt);
+  }
+};
+
+// Everything the sparse path keeps on the device.  Nothing here has N x N elements, and none of the exact path's buffers is used.
+struct FitcState {
+  int64_t m = 0, mp = 0, mr = 0;  // inducing points; padded; rows of the bordered layout
+  bool have_z = false;            // gmb_fitc_set_inducing succeeded for the current data and kernel
+  bool resident = false;          // Lu, L_B, c and w belong to the current (data, Z, theta): gmb_fitc_predict may run
+  DevBuf<double> dZ;              // m x D, row-major: the inducing points as handed in
+  PreparedPoints zpts;            // ... as the covariance kernels read them (stride mr)
+  DevBuf<double> dKuu, dB;        // mr x mp, bordered layout: Kuu then Lu; B then L_B with c = L_B^-1 A Lambda^-1 y in row m
+  DevBuf<double> dP;              // mp x mp: sum over the tiles of G_uf A^T, then G_uu (without its -1/2)
+  DevBuf<double> dDinvU, dDinvB;  // sub-block inverses of the two factors' diagonal blocks
+  DevBuf<double> dscalU, dscalB;  // their scalar blocks: [0] log-det, the info word at SCAL_INFO_AT
+  DevBuf<uint32_t> dctU, dctB;    // control blocks of the persistent tile kernel
+  DevBuf<double> dzero;           // mr zeros: Kuu's border row
+  DevBuf<double> dcw;             // 3 mp: c | w = L_B^-T c | the back substitution's running right-hand side
+  DevBuf<double> dlam, dalpha, dd;  // Np each: lambda, alpha, d
+  DevBuf<double> dcolpart;        // [block of 32 columns][FITC_COL_SUMS]
+  DevBuf<double> dredpart;        // [workgroup][FITC_DERIV_SUMS] of one derivative reduction
+  DevBuf<double> dacc;            // FITC_ACC_DOUBLES: the folded sums (fitc.hpp)
+  FitcSolveWorkspace sw;
+  FitcGemmWorkspace gw;
+  FitcTestPoints tp;
+  void drop_inducing() { have_z = resident = false, m = mp = mr = 0; }
+};
+constexpr int FITC_ACC_DOUBLES = 64;  // [0] sum log lambda [1] sum y^2 / lambda [2] sum d | [8, 25) G_uf's sums | [32, 49) G_uu's
+
 // ---- what a call asks for: its buffers, listed once (`v`: a Budget or a Reserver) ---------------------------------------------------
+
+// the sparse path, in three lists: what depends on m alone (gmb_fitc_set_inducing allocates it) ...
+template <class V>
+bool fitc_fixed_buffers(FitcState& s, const FitcPlan& pl, int D, V& v) {
+  const double mp = (double)pl.mp, mr = (double)pl.mr, nb = mp / FITC_TILE;
+  return v.buf(s.dZ, (double)pl.m * D) && v.rows(s.zpts, mr) && v.buf(s.dKuu, mr * mp) && v.buf(s.dB, mr * mp) && v.buf(s.dP, mp * mp) &&
+         v.buf(s.dDinvU, nb * 8 * 256) && v.buf(s.dDinvB, nb * 8 * 256) && v.buf(s.dscalU, 72.0) && v.buf(s.dscalB, 72.0) && v.buf(s.dzero, mr) &&
+         v.buf(s.dcw, 3.0 * mp) && v.buf(s.dacc, (double)FITC_ACC_DOUBLES);
+}
+// ... the m x tile blocks of `rows` columns (an evaluation: the widest tile of X; a prediction: its M-tile, without the GEMM operands) ...
+template <class V>
+bool fitc_block_buffers(FitcState& s, const FitcPlan& pl, double rows, bool gemm_operands, V& v) {
+  return v.rows(s.sw, rows, pl.mp) && (!gemm_operands || (v.rows(s.gw, rows, pl.mr) && v.buf(s.dredpart, (double)pl.deriv_blocks() * FITC_DERIV_SUMS)));
+}
+// ... and the per-column vectors of an evaluation: O(N)
+template <class V>
+bool fitc_column_buffers(FitcState& s, const FitcPlan& pl, V& v) {
+  return v.buf(s.dlam, (double)pl.Np) && v.buf(s.dalpha, (double)pl.Np) && v.buf(s.dd, (double)pl.Np) &&
+         v.buf(s.dcolpart, (double)pl.col_blocks() * FITC_COL_SUMS);
+}
+template <class V>
+bool fitc_evaluate_buffers(FitcState& s, const FitcPlan& pl, int D, V& v) {
+  return fitc_fixed_buffers(s, pl, D, v) && fitc_block_buffers(s, pl, (double)pl.tmax, true, v) && fitc_column_buffers(s, pl, v);
+}
+template <class V>
+bool fitc_predict_buffers(FitcState& s, const FitcPlan& pl, double Mt, int D, V& v) {
+  return fitc_block_buffers(s, pl, Mt, false, v) && v.rows(s.tp, Mt, D);
+}
 
 // chunks of the posterior reductions' first stage over the N training rows
 inline int red_chunks(int64_t N) { return (int)((N + RED_CHUNK - 1) / RED_CHUNK); }

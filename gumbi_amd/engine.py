@@ -363,6 +363,10 @@ _SIGNATURES = {
     "gmb_design_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "gmb_debug_design_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "gmb_fitc_set_inducing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
+    "gmb_fitc_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
+    "gmb_fitc_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "gmb_debug_fitc_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
 }
 
 
@@ -868,6 +872,45 @@ class Engine:
                                                     _ptr(dmean), _ptr(dvar), self.D, GMB_HOST), "gmb_predict_with_grad")
         return mean, var, dmean, dvar
 
+    # -- sparse GPs: FITC on inducing points (csrc/fitc.hpp) ---------------------------------------------------------
+    def set_inducing(self, Z):
+        """The inducing points of the sparse approximation (``gmb_fitc_set_inducing``): ``Z`` is ``(m, D)``, columns as ``X``.
+        Needs ``set_data`` and ``set_kernel``; a later ``set_data`` / ``set_kernel`` drops them.  ``ValueError`` for a model
+        outside the sparse path's scope (several outputs, categorical or linear dimensions, additive, periodic)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != self.D:
+            raise ValueError(f"Z must be (m, {self.D}), got {Z.shape}")
+        self._check(self._lib.gmb_fitc_set_inducing(self._h, _ptr(Z), Z.shape[0], Z.shape[1], GMB_HOST), "gmb_fitc_set_inducing")
+        self.n_inducing = Z.shape[0]
+
+    def fitc_evaluate(self, theta, grad: bool = True):
+        """The FITC negative log marginal likelihood at ``theta`` -- ``(nlml, gradient)`` or ``nlml`` -- in O(N m^2)
+        (``gmb_fitc_evaluate``).  Sets theta as ``set_theta`` does (an exact factor on this engine is stale afterwards) and
+        leaves the state ``fitc_predict`` needs.  ``LinAlgError`` when one of the two m x m matrices is not positive definite."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        val = C.c_double()
+        g = np.empty(self.spec.theta_size(), dtype=np.float64) if grad else None
+        self._check(self._lib.gmb_fitc_evaluate(self._h, _dptr(theta), theta.size, C.byref(val), _dptr(g) if grad else None),
+                    "gmb_fitc_evaluate")
+        return (val.value, g) if grad else val.value
+
+    def fitc_predict(self, Xs, with_noise=True):
+        """Mean and variance of the FITC posterior at the rows of ``Xs`` against the state the last ``fitc_evaluate`` left
+        (``gmb_fitc_predict``); ``ValueError`` when theta, the data or the inducing points changed since."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        mean, var = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.float64)
+        self._check(self._lib.gmb_fitc_predict(self._h, _ptr(Xs), M, Xs.shape[1], int(bool(with_noise)), _ptr(mean), _ptr(var), GMB_HOST),
+                    "gmb_fitc_predict")
+        return mean, var
+
+    @staticmethod
+    def fitc_plan(N: int, m: int) -> dict:
+        """:func:`fitc_plan` (host-only: no device needed)."""
+        return fitc_plan(N, m)
+
     def predict_device(self, xs_ptr: int, M: int, ldxs: int, mean_ptr: int, var_ptr: int, with_noise=True):
         self._check(
             self._lib.gmb_predict(self._h, C.c_void_p(xs_ptr), M, ldxs, int(bool(with_noise)), C.c_void_p(mean_ptr),
@@ -1142,6 +1185,24 @@ def design_plan(Np: int, M: int, R: int) -> dict:
     h, nt = len(keys), int(buf[4])
     plan["tiles"] = [tuple(int(v) for v in buf[h + 4 * t:h + 4 * t + 4]) for t in range(nt)]
     plan["chunks"] = [tuple(int(v) for v in buf[h + 4 * nt + 2 * c:h + 4 * nt + 2 * c + 2]) for c in range(plan["nchunk"])]
+    return plan
+
+
+def fitc_plan(N: int, m: int) -> dict:
+    """The plan of ``gmb_fitc_evaluate`` for ``N`` observations and ``m`` inducing points (host-only): the padded sizes, the
+    column tiles of X ``(first column, count, padded count)`` and the bytes of the call's buffer list for one input column, in
+    three parts -- ``bytes_fixed`` (a function of m alone), ``bytes_blocks`` (the m x tile blocks) and ``bytes_columns`` (the
+    per-column vectors, O(N)).  ``ValueError`` for a request the call refuses."""
+    lib = load_library()
+    n = int(lib.gmb_debug_fitc_plan(int(N), int(m), None, 0))
+    if n < 0:
+        raise ValueError(f"gmb_debug_fitc_plan: N = {N}, m = {m} is refused (code {-n})")
+    buf = np.empty(n, dtype=np.int64)
+    lib.gmb_debug_fitc_plan(int(N), int(m), _ptr(buf), n)
+    keys = ("Np", "mp", "mr", "tile_rows", "tmax", "ntile", "col_blocks", "bytes_fixed", "bytes_blocks", "bytes_columns")
+    plan = {k: int(v) for k, v in zip(keys, buf)}
+    h = len(keys)
+    plan["tiles"] = [tuple(int(v) for v in buf[h + 3 * t:h + 3 * t + 3]) for t in range(plan["ntile"])]
     return plan
 
 

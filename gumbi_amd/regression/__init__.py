@@ -1,5 +1,7 @@
 from .base import Regressor
 from .hip_gp import HipGP
 from .hip_gp import HipGP as GP
+from .sparse_gp import HipSparseGP
+from .sparse_gp import HipSparseGP as SparseGP
 
-__all__ = ["Regressor", "GP", "HipGP"]
+__all__ = ["Regressor", "GP", "HipGP", "SparseGP", "HipSparseGP"]

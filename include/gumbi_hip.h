@@ -531,6 +531,48 @@ int gmb_design_batch(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, co
  * one M-tile, 5 R > 2^30. */
 int64_t gmb_debug_design_plan(int64_t Np, int64_t M, int64_t R, int64_t* out, int64_t cap);
 
+/* ---- sparse GPs: the FITC approximation on m inducing points (ABI stays 16: new functions only, no change of layout) -----------------
+ * PyMC's MarginalSparse(approx="FITC") (gumbi/regression/pymc/GP.py:571-591, fit(sparse=True, n_u=...)), csrc/fitc.hpp.  With Z the
+ * m inducing points and k the model's covariance without noise:
+ *   Kuu = k(Z, Z) + jitter I = Lu Lu^T      A = Lu^-1 k(Z, X)      lambda_i = max(k(x_i, x_i) - sum_k A_ki^2, 0) + sigma^2
+ *   B = I + A Lambda^-1 A^T = L_B L_B^T     c = L_B^-1 A Lambda^-1 y
+ *   NLML = 1/2 sum log lambda_i + sum log diag(L_B) + 1/2 (y^T Lambda^-1 y - c^T c) + N/2 log 2 pi
+ *   predict: As = Lu^-1 k(Z, X*), C* = L_B^-1 As:  mean = As^T L_B^-T c,  var = k** - colsum(As^2) + colsum(C*^2) (+ sigma^2)
+ * An evaluation costs O(N m^2) and holds O(m^2 + m * tile + N) on the device: X is walked in column tiles (gmb_debug_fitc_plan),
+ * nothing of N x N elements exists and none of the exact path's buffers is allocated or touched.  Fixed-order sums, no atomics: the
+ * same bits call after call.
+ *
+ * Models: one output, no categorical dimensions (n_coreg == 0, out_col == -1), not additive, no linear dimensions, not periodic;
+ * every stationary kind, ARD or a shared lengthscale, scalar noise.  Everything else, and distributed or capacity-mode engines:
+ * GMB_EINVAL with a text that names the limit. */
+
+/* The inducing points: Z is m x D row-major (D of gmb_set_data) with leading dimension ldz >= D, in `memspace`; copied in and prepared
+ * by the path of the data and the test points.  1 <= m <= 16384.  Needs gmb_set_data and gmb_set_kernel; a later gmb_set_data,
+ * gmb_set_kernel or gmb_set_periodic drops the points.  Allocates the O(m^2) state (GMB_ENOMEM with the bytes when the device cannot
+ * hold it). */
+int gmb_fitc_set_inducing(gmb_engine* e, const double* Z, int64_t m, int64_t ldz, int32_t memspace);
+
+/* One objective (+ gradient) evaluation of the FITC marginal likelihood at `theta` (length gmb_theta_size: [ls | eta | sigma]); grad
+ * may be NULL.  Sets theta exactly as gmb_set_theta does: an exact factor resident on the same engine is stale afterwards
+ * (gmb_factor_valid == 0) and is neither used nor overwritten.  GMB_ENOTPD with gmb_notpd_index (a row of the m x m matrix) when
+ * Kuu or B is not positive definite.  Leaves Lu, L_B, c and L_B^-T c resident for gmb_fitc_predict.  The gradient is hand-written
+ * reverse mode over the same tiles; each tile's block A is formed again in that pass instead of being kept (O(m * tile) memory). */
+int gmb_fitc_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlml, double* grad);
+
+/* Mean and variance of the FITC posterior at M points against the state the last gmb_fitc_evaluate left resident; arguments as
+ * gmb_predict.  GMB_EINVAL when there is none: before any evaluation, or when theta (gmb_set_theta, gmb_evaluate), the data
+ * (gmb_set_data, gmb_set_y, gmb_append, gmb_truncate) or the inducing points changed since.  M is tiled as the columns of X are; a
+ * point's result does not depend on where in the call it stands.  M == 0 is GMB_OK. */
+int gmb_fitc_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double* mean, double* var,
+                     int32_t memspace);
+
+/* Host only: the plan of gmb_fitc_evaluate for N observations and m inducing points.  Writes at most `cap` values to `out` (may be
+ * NULL) and returns how many there are: Np, mp, mr (N, m, m + 1 padded to 128), columns of X per tile, columns of the widest tile,
+ * tiles, partial-sum blocks of the column kernels; the bytes of the buffer list for D = 1 in three parts -- what depends on m alone,
+ * the m x tile blocks, the per-column vectors; then per tile (first column, count, padded count).  A refusal returns -(code):
+ * 1 N < 1, 2 m < 1, 3 m > 16384, 4 N > 2^40. */
+int64_t gmb_debug_fitc_plan(int64_t N, int64_t m, int64_t* out, int64_t cap);
+
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
  * maximum Euclidean distance over all N(N-1)/2 pairs; lower[g] = -1 if every pair coincides.
