@@ -15,7 +15,7 @@ from .arrays import (
     UncertainArray,
     UncertainParameterArray,
 )
-from .regression import GP, HipGP, HipSparseGP, Regressor, SparseGP
+from .regression import GP, GPC, HipGP, HipGPC, HipSparseGP, Regressor, SparseGP
 
 __version__ = "0.1.0"
 
@@ -27,6 +27,6 @@ mvuparray = MVUncertainParameterArray
 
 __all__ = [
     "DataSet", "Standardizer", "TidyData", "WideData", "LayeredArray", "ParameterArray", "UncertainArray",
-    "UncertainParameterArray", "MVUncertainParameterArray", "GP", "HipGP", "SparseGP", "HipSparseGP", "Regressor", "parray", "uarray",
+    "UncertainParameterArray", "MVUncertainParameterArray", "GP", "HipGP", "SparseGP", "HipSparseGP", "GPC", "HipGPC", "Regressor", "parray", "uarray",
     "uparray", "mvuparray", "make_deltas_parray",
 ]

@@ -52,6 +52,7 @@
 #include "predict_slope.hpp"
 #include "design_batch.hpp"
 #include "fitc.hpp"
+#include "laplace.hpp"
 
 using namespace gmb;
 
@@ -92,11 +93,14 @@ enum EvKind : int {
                               // of 128 x 128 pairs, k = differentiable columns written per pair)
   EV_DESIGN = 20,             // gmb_design_batch: a PHASE, around the launches listed above (flags = 0 the solved rows V of one point
                               // tile, 1 its prior + rank-N update, 2 the greedy loop: mt = candidates, nt = doubles per row of D, k = picks)
-  EV_FITC = 21                // the sparse path's own launches (mt x nt tiles of the block): flags = 0 a cross-covariance against Z, 1 a
+  EV_FITC = 21,               // the sparse path's own launches (mt x nt tiles of the block): flags = 0 a cross-covariance against Z, 1 a
                               // pass V L^-1, 2 a column / row / adjoint / transpose pass over a block, 3 a derivative reduction or the
                               // prediction's reduction
+  EV_LAPLACE = 22             // gmb_laplace_evaluate: a PHASE, around the launches listed above (mt = block rows, k = Newton iteration;
+                              // flags = 0 the build of Sigma, 1 a build of B or Z', 2 a Cholesky with its two vector solves, 3 a symmetric
+                              // matrix-vector product, 4 elementwise and likelihood work, 5 the inverse, 6 the trace pass)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_FITC); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_LAPLACE); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -204,6 +208,7 @@ struct gmb_engine {
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
   DesignWorkspace dz;       // gmb_design_batch (design_batch.hpp), beside a prediction's workspace of one point tile
   FitcState fitc;           // the sparse (FITC) path: everything it keeps (workspaces.hpp), nothing of it shared with the exact path
+  LaplaceState lap;         // GP classification (laplace.hpp): Sigma and the vectors; B's factor sits in the factor buffer, FactorState "not factored"
 
   // gradient workspace
   DevBuf<double> dW;     // Np x Np column-major: L^-1 then Sigma^-1
@@ -525,7 +530,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_GROUP_COV:
       case EV_SLOPE_COV:
       case EV_DESIGN:
-      case EV_FITC: break;
+      case EV_FITC:
+      case EV_LAPLACE: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -2038,6 +2044,50 @@ bool grad_by_tiles(const gmb_engine* e) {
   return nt >= e->tiles_min_blocks && nt <= e->tiles_max_blocks;
 }
 
+// The launch tree's two halves around whatever reads W = L^-1 in between, on the matrix factored in the factor buffer (the
+// training factor; B's of the Laplace path).  tri_inverse_pair: W = L^-1 into dW (lower) and U = L^-T into the factor buffer (upper
+// triangle + the diagonal blocks, whose L waits in dDiagSave).  `waits_pending`: the factorisation's cross-stream waits may still be
+// pending on pooled events (gmb_evaluate enqueues the gradient behind a factorisation the host has not looked at).
+int tri_inverse_pair(gmb_engine* e, bool waits_pending) {
+  const int nt = (int)(e->Np / TILE);
+  int rc;
+  if ((rc = e->dDiagSave.reserve(e->pool, (int64_t)nt * TILE * TILE))) return rc;
+  // the diagonal blocks of L are put back at the end: U takes their place in between
+  hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 1);
+  // inverses of all diagonal factor blocks, one workgroup each (kept off the Cholesky's chain)
+  {
+    InvArgs ia;
+    ia.L = e->dA;
+    ia.lda = e->ld;
+    ia.blk_stride = (int64_t)TILE * (e->ld + 1);
+    ia.dinv16 = e->dDinv16;
+    ia.invL = nullptr;
+    ia.n = e->N;
+    ia.W = e->dW;
+    ia.ldw = e->Np;
+    ia.U = e->dA;
+    ia.ldu = e->ld;
+    hipLaunchKernelGGL(leaf_invert_kernel, dim3(nt), dim3(256), 0, e->stream, ia);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (!waits_pending) e->sync_next = 0;
+  return e->par_inverse ? winv_levels(e, nt) : winv_cols(e, e->stream, 0, nt);
+}
+
+// ... and inverse_from_pair: (L L^T)^-1 = U U^T (lower triangle) into dW -- the last reader of U: the factor's diagonal blocks go back
+int inverse_from_pair(gmb_engine* e) {
+  const int nt = (int)(e->Np / TILE);
+  int rc;
+  if (e->Np > e->N)
+    hipLaunchKernelGGL(reset_pad_cols_kernel, dim3((unsigned)((e->Np + 255) / 256)), dim3(256), 0, e->stream,
+                       e->dA, e->ld, e->N, e->Np);
+  HIP_TRY(e, hipGetLastError());
+  if ((rc = grad_sigma_inv_rows(e, e->stream, 0, 1, e->dW, e->Np, false))) return rc;
+  hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 0);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
 // Single-GPU gradient: W = L^-1 and U = L^-T by recursive block inversion, alpha = W^T v, Sigma^-1 = U U^T
 // into dW, reductions.  The factor is consumed.  `job`: the factorisation this gradient is enqueued behind before the host has
 // looked at it (gmb_evaluate), or null behind a factor that is final (gmb_nlml, gmb_evaluate's retry).
@@ -2089,32 +2139,9 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h, FactorJob* job) {
   if ((rc = e->dDiagSave.reserve(e->pool, (int64_t)nt * TILE * TILE))) return rc;
   e->fs.inverse_rewrites_u();
   PhaseTimer tg(e);
-  // the diagonal blocks of L are put back at the end: U takes their place in between
-  hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 1);
-  // 0. inverses of all diagonal factor blocks, one workgroup each (kept off the Cholesky's chain)
-  {
-    InvArgs ia;
-    ia.L = e->dA;
-    ia.lda = e->ld;
-    ia.blk_stride = (int64_t)TILE * (e->ld + 1);
-    ia.dinv16 = e->dDinv16;
-    ia.invL = nullptr;
-    ia.n = e->N;
-    ia.W = e->dW;
-    ia.ldw = e->Np;
-    ia.U = e->dA;
-    ia.ldu = e->ld;
-    hipLaunchKernelGGL(leaf_invert_kernel, dim3(nt), dim3(256), 0, e->stream, ia);
-    HIP_TRY(e, hipGetLastError());
-  }
-  // 1. W = L^-1 (dW, lower) and U = L^-T (factor buffer, upper); the factor is consumed from here on
+  // 0. + 1. W = L^-1 (dW, lower) and U = L^-T (factor buffer, upper); the factor is consumed from here on
   e->fs.consume();
-  if (!(job && job->in_flight)) e->sync_next = 0;  // (gmb_evaluate: the factorisation's cross-stream waits may still be pending on pooled events)
-  if (e->par_inverse) {
-    if ((rc = winv_levels(e, nt))) return rc;
-  } else if ((rc = winv_cols(e, e->stream, 0, nt))) {
-    return rc;
-  }
+  if ((rc = tri_inverse_pair(e, job && job->in_flight))) return rc;
   // 2. alpha = W^T v = Sigma^-1 y   (before Sigma^-1 overwrites W)
   hipLaunchKernelGGL(wt_v_kernel, dim3((unsigned)((e->N + 3) / 4)), dim3(256), 0, e->stream, e->dW, e->Np,
                      e->dv, e->N, e->dalpha);
@@ -2122,14 +2149,8 @@ int grad_accumulate(gmb_engine* e, std::vector<double>& h, FactorJob* job) {
     const TriOperand L{e->dA, e->ld, e->dDiagSave, TILE, (int64_t)TILE * TILE};
     if ((rc = refine_alpha(e, L, nullptr, e->dW, e->Np))) return rc;
   }
-  if (e->Np > e->N)
-    hipLaunchKernelGGL(reset_pad_cols_kernel, dim3((unsigned)((e->Np + 255) / 256)), dim3(256), 0, e->stream,
-                       e->dA, e->ld, e->N, e->Np);
-  HIP_TRY(e, hipGetLastError());
   // 3. Sigma^-1 = U U^T (lower triangle) into dW -- the last reader of U: the factor's diagonal blocks go back
-  if ((rc = grad_sigma_inv_rows(e, e->stream, 0, 1, e->dW, e->Np, false))) return rc;
-  hipLaunchKernelGGL(diag_blocks_copy_kernel, dim3(nt), dim3(256), 0, e->stream, e->dA, e->ld, e->dDiagSave, 0);
-  HIP_TRY(e, hipGetLastError());
+  if ((rc = inverse_from_pair(e))) return rc;
   // 4. fused trace reductions
   if ((rc = grad_reduce(e, 0, 1, e->dW, e->Np, false, h, GradLanding{}))) return rc;
   tg.stop();
@@ -2475,6 +2496,7 @@ int gmb_set_data(gmb_engine* e, const double* X, int64_t N, int32_t D, int64_t l
   e->have_theta = false;
   e->N = 0;
   e->fitc.drop_inducing();
+  e->lap.drop("gmb_set_data changed the data");
   stale_sized_by_n(e);
   // (here only: new data gets prepared points of exactly its own size.  resize_n keeps a block that is large enough -- after
   // a truncation it is larger than Nr asks for, and renewing it there would move gmb_resident_bytes.)
@@ -2512,6 +2534,7 @@ int gmb_set_y(gmb_engine* e, const double* y, int32_t memspace) {
   const hipMemcpyKind kind = memspace == GMB_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   e->fs.inputs_changed();  // the y row of the factor (v = L^-1 y) belongs to the old observations
   e->fitc.resident = false;
+  e->lap.drop("gmb_set_y changed the labels");
   HIP_TRY(e, hipMemcpyAsync(e->dy, y, e->N * sizeof(double), kind, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller may reuse its buffer
   return GMB_OK;
@@ -2526,6 +2549,7 @@ int gmb_set_kernel(gmb_engine* e, const gmb_kernel_spec* spec) {
   e->have_theta = false;
   e->fs.inputs_changed();
   e->fitc.drop_inducing();
+  e->lap.drop("gmb_set_kernel changed the kernel");
   e->nc_pad = pick_nc(spec->n_cont);
   e->periodic = 0;
   e->pts.stale();
@@ -2555,6 +2579,7 @@ int gmb_set_periodic(gmb_engine* e, int32_t mode, const double* periods, int32_t
   e->have_theta = false;
   e->fs.feature_map_changed();
   e->fitc.drop_inducing();
+  e->lap.drop("gmb_set_periodic changed the kernel");
   return GMB_OK;
 }
 
@@ -2572,6 +2597,7 @@ static int set_theta(gmb_engine* e, const double* theta, int32_t n, const EvalPl
   e->theta.assign(theta, theta + n);
   e->fs.inputs_changed();
   e->fitc.resident = false;  // (Lu, L_B, c belong to the previous theta)
+  e->lap.drop("theta was set again (gmb_set_theta, gmb_evaluate, gmb_fitc_evaluate)");
   int rc = apply_theta(e);
   if (rc) return rc;
   if ((rc = e->pts.reserve(e->pool, e->Nr))) return rc;
@@ -2629,6 +2655,7 @@ namespace {
 // behind gmb_append / gmb_truncate: nothing of the previous one stays valid, no failure index, the phase timings start from zero.
 void begin_factorisation(gmb_engine* e, FactorState::Kind kind, bool tail = false) {
   tail ? e->fs.begin_tail() : e->fs.begin(kind);
+  e->lap.drop("a factorisation of Sigma (gmb_factorize, gmb_evaluate, gmb_dist_*) took the factor buffer");  // (B's factor sat there)
   e->notpd = -1;
   gmb_timings& tm = e->tm;
   tm.kbuild_ms = tm.chol_ms = tm.chol_gemm_ms = tm.chol_gemm_flops = tm.chol_leaf_ms = tm.chol_trsm_ms = 0.0;
@@ -2975,6 +3002,7 @@ int resize_n(gmb_engine* e, int64_t N_new, const double* Xnew, int64_t K, int64_
   }
   e->fs.resized(live);
   e->fitc.resident = false;
+  e->lap.drop("gmb_append / gmb_truncate changed the data");
   auto bail = [&](int code) {  // a failure half-way: no factor; the data may be of either size, so nothing is ready
     e->fs.resize_failed();
     e->have_theta = false;
@@ -5148,6 +5176,343 @@ int fitc_predict_impl(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, 
   return predict_end(e, nullptr, tiles());
 }
 
+// ---- GP classification by the Laplace approximation: laplace.hpp, laplace_plan.hpp, DESIGN 3.18 ------------------------------------
+// Sigma is built once per evaluation into the Laplace state's own buffer; B = I + (s s^T) o Sigma of every Newton step is written
+// into the factor buffer and factored there by chol_factor, its right-hand side in the border row (the factorisation turns it into
+// L^-1 rhs, as it turns y into v).  FactorState is "not factored" from set_theta on and stays so: the factor buffer holds B's
+// factor, which no reader of Sigma's may see; what these calls keep valid is LaplaceState::resident.
+
+int laplace_scope(gmb_engine* e, const char* what) {
+  const gmb_kernel_spec& sp = e->spec;
+  if (sp.additive) return fail(e, GMB_EINVAL, "%s: additive models are not supported by the Laplace path", what);
+  if (sp.out_col >= 0 || sp.n_out > 1)
+    return fail(e, GMB_EINVAL, "%s: one output only, so no output table and no heteroskedastic noise (out_col = %d, n_out = %d)", what,
+                sp.out_col, sp.n_out);
+  if (e->periodic != 0) return fail(e, GMB_EINVAL, "%s: periodic kernels are not supported by the Laplace path", what);
+  if (e->solve_hook || e->dist_mode != 0)
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode)", what);
+  return GMB_OK;
+}
+
+double* lap_vec(gmb_engine* e, int which) { return e->lap.dvec + (int64_t)which * e->Np; }
+
+// a phase of the call as a trace line of its own while profiling (kind 22), around the launches' lines
+struct LapPhase {
+  gmb_engine* e;
+  size_t at = (size_t)-1;
+  LapPhase(gmb_engine* e_, int which, int iter) : e(e_) {
+    if (!e->profiling) return;
+    ev_begin(e, e->stream, EV_LAPLACE, 0.0, (int)(e->Np / TILE), 0, iter, which);
+    at = e->evs.size() - 1;
+  }
+  ~LapPhase() {
+    if (at != (size_t)-1) (void)hipEventRecord(e->evs[at].b, e->evs[at].s);
+  }
+};
+
+// out = A v from the lower triangle of the n x n matrix A (laplace.hpp: the tiles' parts, then their sum in the plan's order)
+int lap_symv(gmb_engine* e, const double* A, int64_t ld, const double* v, double* out, int iter) {
+  const unsigned nt = (unsigned)(e->Np / TILE);
+  LapPhase ph(e, 3, iter);
+  hipLaunchKernelGGL(symv_lower_kernel, dim3(nt, nt), dim3(256), 0, e->stream, A, ld, e->N, v, e->lap.dsymv.p);
+  hipLaunchKernelGGL(symv_sum_kernel, dim3(nt), dim3(LAP_TILE), 0, e->stream, e->lap.dsymv.p, (int64_t)nt, e->N, out);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// pi, W, s, g, b at `fnew`, and the folded sums in dsums
+int lap_likelihood(gmb_engine* e, const double* fnew, const double* fold, const double* a, int iter) {
+  LaplaceState& s = e->lap;
+  LaplaceLikArgs k{};
+  k.fnew = fnew, k.fold = fold, k.a = a, k.y = e->dy;
+  k.n = e->N, k.np = e->Np;
+  k.pi = lap_vec(e, LV_PI), k.W = lap_vec(e, LV_W), k.s = lap_vec(e, LV_S), k.g = lap_vec(e, LV_G), k.b = lap_vec(e, LV_B);
+  k.part = s.dlikpart;
+  const int64_t nblk = (e->Np + LAP_LIK_BLOCK - 1) / LAP_LIK_BLOCK;
+  LapPhase ph(e, 4, iter);
+  hipLaunchKernelGGL(laplace_lik_kernel, dim3((unsigned)nblk), dim3(LAP_LIK_BLOCK), 0, e->stream, k);
+  hipLaunchKernelGGL(laplace_fold_kernel, dim3(1), dim3(256), 0, e->stream, s.dlikpart.p, nblk, s.dsums.p);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// B = I + (s s^T) o Sigma into the factor buffer with `rhs` (or 0) in the border row, its Cholesky, and L^-1 rhs into dv.  Nothing is
+// synchronised: lap_factor_look reads the failure index and the abort word.
+int lap_factor_enqueue(gmb_engine* e, const double* rhs, CholResult* res, int iter) {
+  LaplaceState& s = e->lap;
+  {
+    LaplaceScaleArgs k{};
+    k.src = s.dS, k.lds = e->ld, k.out = e->dA, k.ldo = e->ld;
+    k.n = e->N, k.rows = e->Nr;
+    k.s = lap_vec(e, LV_S), k.u = nullptr, k.rhs = rhs, k.mode = 0;
+    LapPhase ph(e, 1, iter);
+    hipLaunchKernelGGL(laplace_scale_kernel, dim3((unsigned)e->Np, (unsigned)((e->Nr + 255) / 256)), dim3(256), 0, e->stream, k);
+    HIP_TRY(e, hipGetLastError());
+  }
+  LapPhase ph(e, 2, iter);
+  HIP_TRY(e, hipMemsetAsync(e->dscal, 0, (size_t)SCAL_GACC_AT * sizeof(double), e->stream));
+  *res = CholResult{};
+  int rc = chol_factor(e, train_factor(e), CholOpts{}, res);
+  if (rc) return rc;
+  hipLaunchKernelGGL(extract_v_kernel, dim3(EXTRACT_V_BLOCKS), dim3(TILE), 0, e->stream, e->dA, e->ld, e->N, e->dv, e->dscal + 1);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// out = L^-T v by blocked back substitution against B's factor (`run`: the running right-hand side, Np doubles)
+int lap_backsub(gmb_engine* e, const double* v, double* run, double* out, int iter) {
+  LapPhase ph(e, 2, iter);
+  HIP_TRY(e, hipMemsetAsync(out, 0, (size_t)e->Np * sizeof(double), e->stream));
+  HIP_TRY(e, hipMemsetAsync(run, 0, (size_t)e->Np * sizeof(double), e->stream));
+  HIP_TRY(e, hipMemcpyAsync(run, v, (size_t)e->N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  const TriOperand L{e->dA, e->ld, e->dA, e->ld, (int64_t)TILE * (e->ld + 1)};
+  for (int b = (int)(e->Np / TILE) - 1; b >= 0; --b) {
+    hipLaunchKernelGGL(backsub_diag_kernel, dim3(1), dim3(256), 0, e->stream, L, (int64_t)b, e->N, run, out);
+    if (b > 0) hipLaunchKernelGGL(backsub_update_kernel, dim3((unsigned)(32 * b)), dim3(256), 0, e->stream, L, (int64_t)b, e->N, out, run);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// the host's look at what has been enqueued: the folded sums, and (`res` given) the last factorisation's failure index, abort word
+// and log-determinant
+int lap_look(gmb_engine* e, const char* what, double* sums, const CholResult* res, double* logdet) {
+  int32_t info = 0;
+  uint32_t ab = 0;
+  double ld = 0.0;
+  if (sums) HIP_TRY(e, hipMemcpyAsync(sums, e->lap.dsums, LAP_LIK_SUMS * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (res) {
+    HIP_TRY(e, hipMemcpyAsync(&info, e->dinfo, sizeof info, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(&ld, e->dscal, sizeof ld, hipMemcpyDeviceToHost, e->stream));
+    if (res->tiles) HIP_TRY(e, hipMemcpyAsync(&ab, e->dct + 1, sizeof ab, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (ab != 0) return fail(e, GMB_EHIP, "%s: the tile Cholesky of B waited longer than its time-out for a tile (launch abandoned)", what);
+  if (info != 0) {
+    e->notpd = (int64_t)info - 1;
+    return fail(e, GMB_ENOTPD, "%s: B = I + sqrt(W) Sigma sqrt(W) is not positive definite at row %lld", what, (long long)e->notpd);
+  }
+  if (logdet) *logdet = ld;
+  return GMB_OK;
+}
+
+int laplace_mode_and_objective(gmb_engine* e, const char* what, double* nlq) {
+  LaplaceState& s = e->lap;
+  const int64_t Np = e->Np;
+  const unsigned vgrid = (unsigned)((Np + 255) / 256);
+  int rc;
+  {
+    LapPhase ph(e, 0, 0);
+    if ((rc = build_sigma(e, s.dS, e->ld))) return rc;
+  }
+  // a = f = 0 in every evaluation: the result does not depend on what was evaluated before
+  HIP_TRY(e, hipMemsetAsync(s.dvec, 0, (size_t)(LAP_VECTORS * Np) * sizeof(double), e->stream));
+  double* f = lap_vec(e, LV_F0);
+  double* fc = lap_vec(e, LV_F1);
+  double* a = lap_vec(e, LV_A);
+  double* ac = lap_vec(e, LV_AC);
+  double* ah = lap_vec(e, LV_AH);
+  double *t1 = lap_vec(e, LV_T1), *t2 = lap_vec(e, LV_T2), *t3 = lap_vec(e, LV_T3);
+  double sums[LAP_LIK_SUMS];
+  s.iterations = s.halvings = 0;
+  s.step = 0.0;
+  if ((rc = lap_likelihood(e, f, f, a, 0))) return rc;
+  if ((rc = lap_look(e, what, sums, nullptr, nullptr))) return rc;
+  if (sums[4] != 0.0)
+    return fail(e, GMB_EINVAL, "%s: the labels (gmb_set_data / gmb_set_y) must be exactly 0 or 1; %.0f of %lld are not", what, sums[4], (long long)e->N);
+  double psi = sums[0] - 0.5 * sums[1];
+  s.psi = psi;
+  bool converged = false;
+  for (int it = 1; it <= s.max_iter && !converged; ++it) {
+    // a^ = b - s o B^-1 (s o (Sigma b))
+    if ((rc = lap_symv(e, s.dS, e->ld, lap_vec(e, LV_B), t1, it))) return rc;
+    hipLaunchKernelGGL(laplace_mul_kernel, dim3(vgrid), dim3(256), 0, e->stream, lap_vec(e, LV_S), t1, e->N, Np, t2);
+    CholResult res;
+    if ((rc = lap_factor_enqueue(e, t2, &res, it))) return rc;
+    if ((rc = lap_backsub(e, e->dv, t1, t3, it))) return rc;
+    hipLaunchKernelGGL(laplace_ahat_kernel, dim3(vgrid), dim3(256), 0, e->stream, lap_vec(e, LV_B), lap_vec(e, LV_S), t3, a, 1.0, e->N, Np, ah, ac);
+    HIP_TRY(e, hipGetLastError());
+    // the step: t = 1, halved while Psi falls
+    double t = 1.0, psi_c = psi;
+    bool accepted = false;
+    for (int h = 0; h <= 20; ++h) {
+      if (h > 0) hipLaunchKernelGGL(laplace_step_kernel, dim3(vgrid), dim3(256), 0, e->stream, a, ah, t, e->N, Np, ac);
+      if ((rc = lap_symv(e, s.dS, e->ld, ac, fc, it))) return rc;
+      if ((rc = lap_likelihood(e, fc, f, ac, it))) return rc;
+      if ((rc = lap_look(e, what, sums, h == 0 ? &res : nullptr, nullptr))) return rc;
+      psi_c = sums[0] - 0.5 * sums[1];
+      if (sums[5] != 0.0 || !std::isfinite(psi_c)) {
+        e->notpd = 0;
+        return fail(e, GMB_ENOTPD, "%s: the Newton step of iteration %d produced non-finite values", what, it);
+      }
+      if (psi_c >= psi - 1e-14 * std::fabs(psi)) {
+        accepted = true;
+        break;
+      }
+      t *= 0.5;
+      if (h < 20) ++s.halvings;
+    }
+    s.iterations = it;
+    if (!accepted)
+      return fail(e, GMB_ENOCONV, "%s: Psi still falls after 20 halvings of the step of iteration %d (Psi = %.17g)", what, it, psi);
+    std::swap(f, fc);
+    std::swap(a, ac);
+    psi = psi_c;
+    s.psi = psi;
+    s.step = sums[2];
+    converged = sums[2] <= s.tol * std::max(1.0, sums[3]);
+  }
+  // the vectors the mode ended in: `a` may be either of the two (the readers ask lap_mode_vectors)
+  s.f_swapped = f != lap_vec(e, LV_F0);
+  if (!converged)
+    return fail(e, GMB_ENOCONV, "%s: no convergence in %d Newton iterations (last step %.3g, tol %.3g)", what, s.max_iter, s.step, s.tol);
+  // W at the mode itself: B's factor for the log-determinant, the gradient and the predictions
+  CholResult res;
+  if ((rc = lap_factor_enqueue(e, nullptr, &res, s.iterations + 1))) return rc;
+  double logdet = 0.0;
+  if ((rc = lap_look(e, what, nullptr, &res, &logdet))) return rc;
+  *nlq = -psi + logdet;
+  if (!std::isfinite(*nlq)) {
+    e->notpd = 0;
+    return fail(e, GMB_ENOTPD, "%s: the factorisation produced non-finite values", what);
+  }
+  return GMB_OK;
+}
+
+// where the mode lies: the two f vectors and the two a vectors change roles with every accepted step, together
+void lap_mode_vectors(gmb_engine* e, double** f, double** a) {
+  *f = lap_vec(e, e->lap.f_swapped ? LV_F1 : LV_F0);
+  *a = lap_vec(e, e->lap.f_swapped ? LV_AC : LV_A);
+}
+
+// Alg. 5.1 folded into the exact path's trace pass: Z' = R + u u^T in the inverse's buffer, a' = a^ + u in the gradient's alpha
+int laplace_gradient(gmb_engine* e, double* grad) {
+  LaplaceState& s = e->lap;
+  const int64_t Np = e->Np;
+  const unsigned vgrid = (unsigned)((Np + 255) / 256);
+  const int it = s.iterations + 1;
+  int rc;
+  double *f, *a;
+  lap_mode_vectors(e, &f, &a);
+  double *t1 = lap_vec(e, LV_T1), *t2 = lap_vec(e, LV_T2), *t3 = lap_vec(e, LV_T3), *s2 = lap_vec(e, LV_S2), *u = lap_vec(e, LV_U);
+  {
+    LapPhase ph(e, 5, it);
+    if ((rc = tri_inverse_pair(e, false))) return rc;
+    if ((rc = inverse_from_pair(e))) return rc;  // B^-1, lower triangle of dW; L is back in the factor buffer
+  }
+  hipLaunchKernelGGL(laplace_s2_kernel, dim3(vgrid), dim3(256), 0, e->stream, e->dW.p, Np, lap_vec(e, LV_PI), e->N, Np, s2);
+  if ((rc = lap_symv(e, s.dS, e->ld, s2, t1, it))) return rc;
+  hipLaunchKernelGGL(laplace_mul_kernel, dim3(vgrid), dim3(256), 0, e->stream, lap_vec(e, LV_S), t1, e->N, Np, t2);
+  if ((rc = lap_symv(e, e->dW, Np, t2, t3, it))) return rc;
+  hipLaunchKernelGGL(laplace_u_kernel, dim3(vgrid), dim3(256), 0, e->stream, s2, lap_vec(e, LV_S), t3, a, e->N, Np, u, e->dalpha.p);
+  {
+    LaplaceScaleArgs k{};
+    k.src = nullptr, k.lds = 0, k.out = e->dW, k.ldo = Np;
+    k.n = e->N, k.rows = Np;
+    k.s = lap_vec(e, LV_S), k.u = u, k.rhs = nullptr, k.mode = 1;
+    LapPhase ph(e, 1, it);
+    hipLaunchKernelGGL(laplace_scale_kernel, dim3((unsigned)Np, (unsigned)((Np + 255) / 256)), dim3(256), 0, e->stream, k);
+    HIP_TRY(e, hipGetLastError());
+  }
+  std::vector<double> h;
+  {
+    LapPhase ph(e, 6, it);
+    if ((rc = grad_reduce(e, 0, 1, e->dW, Np, false, h, GradLanding{}))) return rc;
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if ((rc = grad_chain_rule(e, h, grad))) return rc;
+  for (size_t i = 0; i < e->theta.size(); ++i)
+    if (!std::isfinite(grad[i])) return fail(e, GMB_ENOTPD, "gmb_laplace_evaluate: the gradient is not finite");
+  return GMB_OK;
+}
+
+int laplace_evaluate_impl(gmb_engine* e, const double* theta, int32_t n, double* nlq, double* grad) {
+  const char* what = "gmb_laplace_evaluate";
+  if (!e || !theta || !nlq) return GMB_EINVAL;
+  if (!e->have_spec) return fail(e, GMB_EINVAL, "gmb_set_kernel must precede %s", what);
+  if (e->N <= 0) return fail(e, GMB_EINVAL, "gmb_set_data must precede %s", what);
+  int rc = laplace_scope(e, what);
+  if (rc) return rc;
+  LaplaceState& s = e->lap;
+  if ((rc = set_theta(e, theta, n, nullptr))) return rc;  // (FactorState: not factored, whatever was there; the Laplace state dropped)
+  s.dropped_by = "the last gmb_laplace_evaluate failed";
+  e->notpd = -1;
+  LaplacePlan pl;
+  if (pl.make(e->N)) return fail(e, GMB_EINVAL, "%s: N = %lld is out of range (at most %lld)", what, (long long)e->N, (long long)LAP_MAX_N);
+  {
+    auto list = [&](auto& v) {
+      return laplace_evaluate_buffers(s, pl, v) && v.buf(e->dA, (double)e->ld * (double)e->Np) &&
+             (!grad || (v.buf(e->dW, (double)e->Np * (double)e->Np) && v.buf(e->dalpha, 3.0 * (double)e->Np)));
+    };
+    Budget need;
+    list(need);
+    double free_b;
+    if ((rc = device_free_bytes(e, &free_b))) return rc;
+    if (need.fresh > free_b)
+      return fail(e, GMB_ENOMEM, "%s: N = %lld needs %.0f bytes on the device (Sigma, the factor buffer%s: %.0f each), %.0f more than the engine "
+                                 "holds now; %.0f bytes are free -- nothing was computed",
+                  what, (long long)e->N, need.total, grad ? " and the inverse's" : "", 8.0 * pl.sigma_doubles(), need.fresh, free_b);
+    Reserver take{e->pool};
+    list(take);
+    if (take.rc) return take.rc;
+  }
+  rc = laplace_mode_and_objective(e, what, nlq);
+  if (!rc && grad) rc = laplace_gradient(e, grad);
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  ev_collect(e);
+  if (rc) return rc;
+  HIP_TRY(e, sync);
+  s.resident = true;
+  return GMB_OK;
+}
+
+int laplace_require_resident(gmb_engine* e, const char* what) {
+  if (!e) return GMB_EINVAL;
+  if (!e->lap.resident || !e->have_theta)
+    return fail(e, GMB_EINVAL, "%s: no Laplace state is resident for the current data, labels, kernel and theta: %s -- call gmb_laplace_evaluate first",
+                what, e->lap.dropped_by);
+  return GMB_OK;
+}
+
+// Alg. 3.2 on the prediction's own pieces: the cross-covariance launch, the mean k*^T g by the reduction a product-form prediction
+// takes its mean with, the columns scaled by s, the strip solve against B's factor, the variance reduction
+int laplace_predict_impl(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* mean, double* var, int32_t memspace) {
+  const char* what = "gmb_laplace_predict";
+  int rc = laplace_require_resident(e, what);
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !mean || !var)) || ldxs < e->D) return fail(e, GMB_EINVAL, "bad Xs/M/ldxs/mean/var");
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  reset_predict_timings(e);
+  const int64_t Mt = predict_tile_rows(e, M);
+  if ((rc = predict_workspace(e, Mt))) return rc;
+  const int nchunk = red_chunks(e->N);
+  e->tm.predict_gemm_form = 0;
+  const CopyKinds ck = copy_kinds(memspace);
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t m0 = 0; m0 < M; m0 += Mt) {
+      const int64_t mc = std::min<int64_t>(Mt, M - m0);
+      const int64_t mpad = round_up(mc, TILE);
+      if ((rc = predict_cross_cov(e, 1u, Xs + m0 * ldxs, mc, mpad, ldxs, 0, ck.in))) return rc;
+      const unsigned mblocks = (unsigned)(mpad / 256 + (mpad % 256 ? 1 : 0));
+      hipLaunchKernelGGL(predict_mean_partial_kernel, dim3(mblocks, nchunk), dim3(256), 0, e->stream, e->pw.dV, mpad, lap_vec(e, LV_G), e->N, e->dpart,
+                         mpad);
+      hipLaunchKernelGGL(predict_mean_final_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, e->stream, e->dpart, nchunk, mpad, mc,
+                         e->pw.dmean);
+      HIP_TRY(e, hipMemcpyAsync(mean + m0, e->pw.dmean, mc * sizeof(double), ck.out, e->stream));
+      hipLaunchKernelGGL(laplace_colscale_kernel, dim3(mblocks, (unsigned)((e->N + LAP_SCALE_COLS - 1) / LAP_SCALE_COLS)), dim3(256), 0, e->stream,
+                         e->pw.dV.p, mpad, e->N, lap_vec(e, LV_S));
+      HIP_TRY(e, hipGetLastError());
+      if ((rc = predict_solve_v(e, mpad, false))) return rc;
+      if ((rc = predict_reduce(e, mc, mpad, false))) return rc;  // (its mean, against the border row's v, is not the latent mean)
+      HIP_TRY(e, hipMemcpyAsync(var + m0, e->pw.dvar, mc * sizeof(double), ck.out, e->stream));
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
 }  // namespace
 
 extern "C" {
@@ -5175,6 +5540,68 @@ int64_t gmb_debug_fitc_plan(int64_t N, int64_t m, int64_t* out, int64_t cap) {
   fitc_block_buffers(st, pl, (double)pl.tmax, true, blocks);
   fitc_column_buffers(st, pl, columns);
   return fitc_plan_dump(pl, fixed.total, blocks.total, columns.total, out, cap);
+}
+
+int gmb_laplace_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlq, double* grad) {
+  return laplace_evaluate_impl(e, theta, n, nlq, grad);
+}
+
+int gmb_laplace_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* mean, double* var, int32_t memspace) {
+  return laplace_predict_impl(e, Xs, M, ldxs, mean, var, memspace);
+}
+
+int gmb_laplace_info(const gmb_engine* e, gmb_laplace_stats* out) {
+  if (!e || !out) return GMB_EINVAL;
+  out->iterations = e->lap.iterations;
+  out->halvings = e->lap.halvings;
+  out->psi = e->lap.psi;
+  out->step = e->lap.step;
+  return GMB_OK;
+}
+
+int gmb_laplace_copy_mode(const gmb_engine* ce, double* f, double* a) {
+  gmb_engine* e = const_cast<gmb_engine*>(ce);
+  int rc = laplace_require_resident(e, "gmb_laplace_copy_mode");
+  if (rc) return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  double *df, *da;
+  lap_mode_vectors(e, &df, &da);
+  if (f) HIP_TRY(e, hipMemcpy(f, df, (size_t)e->Np * sizeof(double), hipMemcpyDeviceToHost));
+  if (a) HIP_TRY(e, hipMemcpy(a, da, (size_t)e->Np * sizeof(double), hipMemcpyDeviceToHost));
+  return GMB_OK;
+}
+
+int gmb_laplace_set_options(gmb_engine* e, double tol, int32_t max_iter) {
+  if (!e) return GMB_EINVAL;
+  if (!(tol > 0.0) || !std::isfinite(tol)) return fail(e, GMB_EINVAL, "gmb_laplace_set_options: tol must be a positive number");
+  if (max_iter < 1 || max_iter > 40) return fail(e, GMB_EINVAL, "gmb_laplace_set_options: max_iter = %d (1 .. 40)", max_iter);
+  e->lap.tol = tol;
+  e->lap.max_iter = max_iter;
+  return GMB_OK;
+}
+
+int64_t gmb_debug_laplace_plan(int64_t N, int64_t* out, int64_t cap) {
+  LaplacePlan pl;
+  const int bad = pl.make(N);
+  if (bad) return -(int64_t)bad;
+  LaplaceState st;  // (nothing allocated: a Budget only reads what the buffers hold)
+  Budget need;
+  laplace_evaluate_buffers(st, pl, need);
+  return laplace_plan_dump(pl, need.total, out, cap);
+}
+
+int gmb_debug_laplace_symv(gmb_engine* e, const double* v, double* out) {
+  int rc = laplace_require_resident(e, "gmb_debug_laplace_symv");
+  if (rc) return rc;
+  if (!v || !out) return fail(e, GMB_EINVAL, "gmb_debug_laplace_symv: null v / out");
+  HIP_TRY(e, hipSetDevice(e->device));
+  double *t1 = lap_vec(e, LV_T1), *t2 = lap_vec(e, LV_T2);
+  HIP_TRY(e, hipMemcpyAsync(t1, v, (size_t)e->Np * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if ((rc = lap_symv(e, e->lap.dS, e->ld, t1, t2, 0))) return rc;
+  HIP_TRY(e, hipMemcpyAsync(out, t2, (size_t)e->Np * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  ev_collect(e);
+  return GMB_OK;
 }
 
 int gmb_nlml(gmb_engine* e, double* nlml, double* grad) {

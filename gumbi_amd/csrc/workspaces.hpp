@@ -12,6 +12,7 @@
 #include "design_plan.hpp"
 #include "device_buffers.hpp"
 #include "fitc_plan.hpp"
+#include "laplace_plan.hpp"
 #include "slope_plan.hpp"  // SLOPE_MAX_COLS
 #include "workspace_sizes.hpp"
 
@@ -190,6 +191,32 @@ struct FitcState {
 };
 constexpr int FITC_ACC_DOUBLES = 64;  // [0] sum log lambda [1] sum y^2 / lambda [2] sum d | [8, 25) G_uf's sums | [32, 49) G_uu's
 
+// GP classification by the Laplace approximation (laplace.hpp): what it keeps beside the exact path's factor buffer
+// (B, then its factor) and inverse buffer (B^-1, then Z').  dS is the one N x N matrix of its own, allocated only by these calls.
+struct LaplaceState {
+  bool resident = false;   // the mode, s, g and B's factor in the factor buffer belong to the current (data, labels, kernel, theta)
+  const char* dropped_by = "no gmb_laplace_evaluate has succeeded";  // ... or what took them away
+  double tol = 1e-9;       // gmb_laplace_set_options
+  int32_t max_iter = 40;
+  int32_t iterations = 0, halvings = 0;  // of the last evaluation (gmb_laplace_info)
+  double psi = 0.0, step = 0.0;
+  bool f_swapped = false;  // which of the two f vectors holds the mode (they change roles when a step is accepted)
+  DevBuf<double> dS;       // Sigma: Nr x Np, the bordered layout of the factor buffer (the covariance build writes it)
+  DevBuf<double> dvec;     // LAP_VECTORS vectors of Np
+  DevBuf<double> dsymv;    // the slots of symv_lower_kernel
+  DevBuf<double> dlikpart; // the partial sets of laplace_lik_kernel
+  DevBuf<double> dsums;    // LAP_LIK_SUMS: their fold
+  void drop(const char* why) {
+    if (resident) dropped_by = why;
+    resident = false;
+  }
+};
+// the vectors of dvec
+enum LapVec : int {
+  LV_F0 = 0, LV_F1, LV_A, LV_AC, LV_AH, LV_PI, LV_W, LV_S, LV_G, LV_B, LV_T1, LV_T2, LV_T3, LV_S2, LV_U, LV_SPARE
+};
+static_assert(LV_SPARE + 1 == LAP_VECTORS, "laplace_plan.hpp counts the vectors");
+
 // ---- what a call asks for: its buffers, listed once (`v`: a Budget or a Reserver) ---------------------------------------------------
 
 // the sparse path, in three lists: what depends on m alone (gmb_fitc_set_inducing allocates it) ...
@@ -220,6 +247,13 @@ bool fitc_predict_buffers(FitcState& s, const FitcPlan& pl, double Mt, int D, V&
   return fitc_block_buffers(s, pl, Mt, false, v) && v.rows(s.tp, Mt, D);
 }
 
+// the Laplace path: everything of an evaluation that is its own (the factor buffer, the inverse's and the gradient's vectors are the
+// exact path's and sized by it; a prediction adds predict_buffers alone)
+template <class V>
+bool laplace_evaluate_buffers(LaplaceState& s, const LaplacePlan& pl, V& v) {
+  return v.buf(s.dS, pl.sigma_doubles()) && v.buf(s.dvec, pl.vector_doubles()) && v.buf(s.dsymv, pl.symv_doubles()) &&
+         v.buf(s.dlikpart, pl.lik_doubles()) && v.buf(s.dsums, (double)LAP_LIK_SUMS);
+}
 // chunks of the posterior reductions' first stage over the N training rows
 inline int red_chunks(int64_t N) { return (int)((N + RED_CHUNK - 1) / RED_CHUNK); }
 

@@ -20,7 +20,7 @@ __all__ = ["Engine", "KernelSpec", "GumbiHipError", "library_path", "load_librar
            "ls_limits", "dist_plan", "GmbComm", "DistStep"]
 
 GMB_MAX_DIMS, GMB_MAX_LIN, GMB_MAX_COREG, GMB_MAX_LEVELS = 16, 8, 4, 32
-GMB_OK, GMB_EINVAL, GMB_ENOMEM, GMB_EHIP, GMB_ENOTPD, GMB_ENODEVICE = 0, -1, -2, -3, -4, -5
+GMB_OK, GMB_EINVAL, GMB_ENOMEM, GMB_EHIP, GMB_ENOTPD, GMB_ENODEVICE, GMB_ENOCONV = 0, -1, -2, -3, -4, -5, -6
 GMB_HOST, GMB_DEVICE = 0, 1
 
 # pm.gp.cov names accepted by PymcGP._construct_kernels (gumbi/regression/pymc/GP.py:664-674)
@@ -44,6 +44,10 @@ def resolve_kernel_name(name: str):
     if name in KERNEL_KINDS:
         return name, PERIODIC_OFF
     raise ValueError(f"Continuous kernel must be one of {list(KERNEL_KINDS)}, optionally with '+Periodic', or 'Periodic'; got {name!r}")
+
+
+class LaplaceConvergenceError(RuntimeError):
+    """``gmb_laplace_evaluate`` hit one of its caps (``GMB_ENOCONV``): 40 Newton iterations, or 20 halvings of one step."""
 
 
 class GumbiHipError(RuntimeError):
@@ -235,6 +239,12 @@ class GmbComm(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("ctx", C.c_void_p), ("all_gather", ALL_GATHER)]
 
 
+class LaplaceStats(C.Structure):
+    """``gmb_laplace_stats``: the Newton iteration of the last ``gmb_laplace_evaluate``."""
+
+    _fields_ = [("iterations", C.c_int32), ("halvings", C.c_int32), ("psi", C.c_double), ("step", C.c_double)]
+
+
 class DistStep(C.Structure):
     """``gmb_dist_step``: one step of a rank's schedule (include/gumbi_hip.h)."""
 
@@ -367,6 +377,13 @@ _SIGNATURES = {
     "gmb_fitc_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_fitc_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "gmb_debug_fitc_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "gmb_laplace_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
+    "gmb_laplace_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
+    "gmb_laplace_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gmb_laplace_copy_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmb_laplace_set_options": (C.c_int, [C.c_void_p, C.c_double, C.c_int32]),
+    "gmb_debug_laplace_plan": (C.c_int64, [C.c_int64, C.c_void_p, C.c_int64]),
+    "gmb_debug_laplace_symv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -415,7 +432,8 @@ def _preload_hip_runtime():
 #: ``gmb_leave_out``, and the averages of the posterior over groups of points, ``gmb_predict_groups`` / ``gmb_predict_groups_terms``
 #: with the host-only ``gmb_debug_group_tasks``, and the posterior of the slope, ``gmb_predict_slope`` / ``gmb_predict_slope_terms``
 #: with the host-only ``gmb_debug_slope_tile_rows``, and the batch design by integrated variance reduction, ``gmb_design_batch`` with
-#: the host-only ``gmb_debug_design_plan``)
+#: the host-only ``gmb_debug_design_plan``, and the sparse path ``gmb_fitc_*``, and GP classification by the Laplace approximation,
+#: ``gmb_laplace_*`` with the status ``GMB_ENOCONV``, the struct ``gmb_laplace_stats`` and the host-only ``gmb_debug_laplace_plan``)
 ABI_VERSION = 16
 
 #: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
@@ -530,6 +548,8 @@ class Engine:
             raise MemoryError(f"{what}: {msg}")
         if rc == GMB_ENODEVICE:
             raise GumbiHipError(f"{what}: no HIP device (no CPU fallback exists)")
+        if rc == GMB_ENOCONV:
+            raise LaplaceConvergenceError(f"{what}: {msg}")
         raise GumbiHipError(f"{what}: status {rc}: {msg}")
 
     @property
@@ -911,6 +931,65 @@ class Engine:
         """:func:`fitc_plan` (host-only: no device needed)."""
         return fitc_plan(N, m)
 
+    # -- GP classification: the Laplace approximation (csrc/laplace.hpp) --------------------------------------------
+    def laplace_evaluate(self, theta, grad: bool = True):
+        """``-log q(y | theta)`` of the Laplace approximation for the labels ``set_data`` / ``set_y`` hold (exactly 0 or 1),
+        logit link -- ``(nlq, gradient)`` or ``nlq`` (``gmb_laplace_evaluate``); theta and the gradient laid out as ``evaluate``'s.
+        The Newton iteration starts at 0 in every call.  Leaves the state ``laplace_predict`` needs and the exact path "not
+        factored".  ``ValueError`` for other labels or a model outside the scope (additive, several outputs, periodic),
+        ``LinAlgError`` when B is not positive definite, :class:`LaplaceConvergenceError` when the iteration hits a cap."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        val = C.c_double()
+        g = np.empty(self.spec.theta_size(), dtype=np.float64) if grad else None
+        self._check(self._lib.gmb_laplace_evaluate(self._h, _dptr(theta), theta.size, C.byref(val), _dptr(g) if grad else None),
+                    "gmb_laplace_evaluate")
+        return (val.value, g) if grad else val.value
+
+    def laplace_predict(self, Xs):
+        """Mean and variance of the LATENT function at the rows of ``Xs`` against the state the last ``laplace_evaluate`` left
+        (``gmb_laplace_predict``; the variance without noise and jitter); ``ValueError`` when theta, the data, the labels or the
+        kernel changed since, or an exact factorisation took the factor buffer."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        mean, var = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.float64)
+        self._check(self._lib.gmb_laplace_predict(self._h, _ptr(Xs), M, Xs.shape[1], _ptr(mean), _ptr(var), GMB_HOST), "gmb_laplace_predict")
+        return mean, var
+
+    def laplace_info(self) -> dict:
+        """The Newton iteration of the last ``laplace_evaluate``: ``iterations``, ``halvings``, ``psi``, ``step``."""
+        st = LaplaceStats()
+        self._check(self._lib.gmb_laplace_info(self._h, C.byref(st)), "gmb_laplace_info")
+        return {"iterations": int(st.iterations), "halvings": int(st.halvings), "psi": float(st.psi), "step": float(st.step)}
+
+    def laplace_mode(self, padded: bool = False):
+        """The resident mode ``(f_hat, a_hat)`` with ``f_hat = Sigma a_hat`` (``gmb_laplace_copy_mode``); ``padded``: all
+        ``N`` rounded up to 128 entries the engine keeps (0 beyond ``N``)."""
+        Np = (self.N + 127) // 128 * 128
+        f, a = np.empty(Np, dtype=np.float64), np.empty(Np, dtype=np.float64)
+        self._check(self._lib.gmb_laplace_copy_mode(self._h, _ptr(f), _ptr(a)), "gmb_laplace_copy_mode")
+        return (f, a) if padded else (f[:self.N].copy(), a[:self.N].copy())
+
+    def set_laplace_options(self, tol: float = 1e-9, max_iter: int = 40):
+        """Stop rule and iteration cap (at most 40) of ``laplace_evaluate``'s Newton iteration."""
+        self._check(self._lib.gmb_laplace_set_options(self._h, float(tol), int(max_iter)), "gmb_laplace_set_options")
+
+    def debug_laplace_symv(self, v):
+        """Test door: ``Sigma v`` by the symmetric product against the resident Sigma; ``v`` has ``N`` entries, the result all
+        ``N`` rounded up to 128 the kernel writes."""
+        Np = (self.N + 127) // 128 * 128
+        vin = np.zeros(Np, dtype=np.float64)
+        vin[:self.N] = np.asarray(v, dtype=np.float64)
+        out = np.empty(Np, dtype=np.float64)
+        self._check(self._lib.gmb_debug_laplace_symv(self._h, _ptr(vin), _ptr(out)), "gmb_debug_laplace_symv")
+        return out
+
+    @staticmethod
+    def laplace_plan(N: int) -> dict:
+        """:func:`laplace_plan` (host-only: no device needed)."""
+        return laplace_plan(N)
+
     def predict_device(self, xs_ptr: int, M: int, ldxs: int, mean_ptr: int, var_ptr: int, with_noise=True):
         self._check(
             self._lib.gmb_predict(self._h, C.c_void_p(xs_ptr), M, ldxs, int(bool(with_noise)), C.c_void_p(mean_ptr),
@@ -1203,6 +1282,23 @@ def fitc_plan(N: int, m: int) -> dict:
     plan = {k: int(v) for k, v in zip(keys, buf)}
     h = len(keys)
     plan["tiles"] = [tuple(int(v) for v in buf[h + 3 * t:h + 3 * t + 3]) for t in range(plan["ntile"])]
+    return plan
+
+
+def laplace_plan(N: int) -> dict:
+    """The plan of ``gmb_laplace_evaluate`` for ``N`` observations (host-only): padded sizes, block rows ``nt``, the workspace
+    ``slots`` of the symmetric product, the partial sets of the likelihood pass, ``bytes_state`` of the path's own buffers, and
+    per block row the offsets (in doubles) of the ``nt + 1`` parts its sum adds, in order (``row_terms``)."""
+    lib = load_library()
+    n = int(lib.gmb_debug_laplace_plan(int(N), None, 0))
+    if n < 0:
+        raise ValueError(f"gmb_debug_laplace_plan: N = {N} is refused (code {-n})")
+    buf = np.empty(n, dtype=np.int64)
+    lib.gmb_debug_laplace_plan(int(N), _ptr(buf), n)
+    keys = ("Np", "Nr", "nt", "slots", "lik_blocks", "slot_doubles", "lik_sums", "bytes_state")
+    plan = {k: int(v) for k, v in zip(keys, buf)}
+    h, nt = len(keys), plan["nt"]
+    plan["row_terms"] = [[int(v) for v in buf[h + R * (nt + 1):h + (R + 1) * (nt + 1)]] for R in range(nt)]
     return plan
 
 

@@ -47,7 +47,8 @@ typedef enum gmb_status {
   GMB_ENOMEM = -2,   /* hipMalloc failed                                                       */
   GMB_EHIP = -3,     /* a HIP runtime call or kernel launch failed; see gmb_last_error         */
   GMB_ENOTPD = -4,   /* covariance not positive definite; see gmb_notpd_index (LinAlgError)    */
-  GMB_ENODEVICE = -5 /* no usable gfx950 device -- there is NO CPU fallback                    */
+  GMB_ENODEVICE = -5,/* no usable gfx950 device -- there is NO CPU fallback                    */
+  GMB_ENOCONV = -6   /* gmb_laplace_evaluate: the Newton iteration hit one of its caps          */
 } gmb_status;
 
 typedef enum gmb_kernel_kind { /* pm.gp.cov.<name>, selected at pymc/GP.py:664-674,684 */
@@ -572,6 +573,67 @@ int gmb_fitc_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, i
  * the m x tile blocks, the per-column vectors; then per tile (first column, count, padded count).  A refusal returns -(code):
  * 1 N < 1, 2 m < 1, 3 m > 16384, 4 N > 2^40. */
 int64_t gmb_debug_fitc_plan(int64_t N, int64_t m, int64_t* out, int64_t cap);
+
+/* ---- GP classification: a latent GP with a logit link and a Bernoulli likelihood by the Laplace approximation (ABI stays 16: new
+ * functions, one new status and one new struct, no change of layout) ---
+ * The reference's GPC (gumbi/regression/pymc/GP.py:759-797, pymc/extras.py:8-66) without sampling: Rasmussen & Williams, Algorithms
+ * 3.1, 3.2 and 5.1, csrc/laplace.hpp.  Labels y in {0, 1} (what gmb_set_data / gmb_set_y hold), Sigma exactly the matrix gmb_factorize
+ * builds (K + the noise entries of theta + jitter I; a classifier passes sigma = 0), zero mean:
+ *   pi = 1 / (1 + e^-f)   log p(y | f) = sum y f - log(1 + e^f)   g = y - pi   W = pi (1 - pi)   s = sqrt(W)
+ *   mode: from a = f = 0 in EVERY call (no warm start), b = W f + g, B = I + (s s^T) o Sigma = L L^T,
+ *         a^ = b - s o B^-1 (s o (Sigma b)), a <- a + t (a^ - a), f = Sigma a, t = 1 halved while Psi(a, f) = -1/2 a^T f + log p(y | f)
+ *         falls below the previous Psi (slack 1e-14 |Psi|); stop at max |f_new - f| <= tol max(1, max |f_new|)
+ *   -log q(y | theta) = -Psi(a^, f^) + sum log L_ii with B at the mode
+ *   gradient: 1/2 tr((Z' - a' a'^T) dSigma/dtheta) by the trace pass of gmb_evaluate, Z' = R + u u^T, a' = a^ + u,
+ *         R = (s s^T) o B^-1, s2 = -1/2 (1 - diag B^-1)(1 - 2 pi), u = s2 - R (Sigma s2)   (no division: valid where W is 0)
+ * Caps: 40 Newton iterations, 20 halvings per iteration; hitting one is GMB_ENOCONV, never a silent result.  Resident N x N matrices:
+ * Sigma, the factor buffer (B, then its factor) and, with the gradient, the inverse's -- the exact path's two plus one.  Fixed-order
+ * sums, no floating-point atomics: the same bits call after call.
+ *
+ * Models: whatever a non-additive, single-output gmb_evaluate accepts.  Additive specs, an output column (n_out > 1, heteroskedastic
+ * noise), periodic mode, distributed and capacity-mode engines: GMB_EINVAL.
+ *
+ * State: a Laplace call leaves B's factor in the factor buffer, so the exact path is "not factored" behind it (gmb_factor_valid == 0:
+ * gmb_predict and its relatives refuse until gmb_factorize / gmb_evaluate), and every exact factorisation drops the Laplace state. */
+
+typedef struct gmb_laplace_stats {
+  int32_t iterations; /* accepted Newton steps of the last gmb_laplace_evaluate */
+  int32_t halvings;   /* halvings of t over all of them */
+  double psi;         /* Psi at the last accepted iterate */
+  double step;        /* max |f_new - f| of the last accepted step */
+} gmb_laplace_stats;
+
+/* -log q(y | theta) and, unless grad is NULL, its gradient; theta and the gradient are laid out as gmb_evaluate's.  Sets theta as
+ * gmb_set_theta does.  GMB_EINVAL: labels that are not exactly 0 or 1 (checked on the device), a model outside the scope above;
+ * GMB_ENOTPD + gmb_notpd_index: B not positive definite, or non-finite values; GMB_ENOCONV: a cap was hit; GMB_ENOMEM with the bytes
+ * before anything is computed.  After an error no Laplace state is resident and the engine is usable. */
+int gmb_laplace_evaluate(gmb_engine* e, const double* theta, int32_t n, double* nlq, double* grad);
+
+/* Latent mean k*^T (y - pi^) and variance k** - |L^-1 (s o k*)|^2 at M points (k** without noise and jitter, as
+ * gmb_predict(with_noise = 0)); arguments as gmb_predict.  Valid only behind a successful gmb_laplace_evaluate with nothing in between
+ * that changes the data, the labels, the kernel or theta (gmb_set_*, gmb_append, gmb_truncate, gmb_factorize, gmb_evaluate,
+ * gmb_fitc_evaluate): otherwise GMB_EINVAL with a text that names the cause.  M == 0 is GMB_OK. */
+int gmb_laplace_predict(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* mean, double* var, int32_t memspace);
+
+/* The Newton iteration of the last gmb_laplace_evaluate (also one that ended in GMB_ENOCONV). */
+int gmb_laplace_info(const gmb_engine* e, gmb_laplace_stats* out);
+
+/* The resident mode: f^ and a^ (f^ = Sigma a^), each Np = N rounded up to 128 doubles on the host, 0 beyond N; either may be NULL.
+ * Readiness as gmb_laplace_predict. */
+int gmb_laplace_copy_mode(const gmb_engine* e, double* f, double* a);
+
+/* tol > 0 (default 1e-9) and 1 <= max_iter <= 40 (default 40) of the Newton iteration. */
+int gmb_laplace_set_options(gmb_engine* e, double tol, int32_t max_iter);
+
+/* Host only: the plan of gmb_laplace_evaluate for N observations (csrc/laplace_plan.hpp).  Writes at most `cap` values to `out` (may be
+ * NULL) and returns how many there are: Np, Nr, block rows nt, workspace slots of the symmetric product (tiles of the lower triangle),
+ * partial sets of the likelihood pass, doubles per slot, sums per set, bytes of the state's own buffers; then per block row the nt + 1
+ * offsets (in doubles) of the parts its sum adds, in order.  A refusal returns -(code): 1 N < 1, 2 N > 2^22. */
+int64_t gmb_debug_laplace_plan(int64_t N, int64_t* out, int64_t cap);
+
+/* Test door: out = Sigma v by the symmetric product against the resident Sigma of the last gmb_laplace_evaluate; v and out are Np
+ * doubles on the host (entries of v beyond N are not read as data: they count as 0).  Readiness as gmb_laplace_predict. */
+int gmb_debug_laplace_symv(gmb_engine* e, const double* v, double* out);
 
 /* Pairwise-distance extrema used for the lengthscale prior (gumbi/utils/gp_utils.py:15-48):
  * for each group (one per column if ard, else all n_cols jointly) the minimum NON-ZERO and the
