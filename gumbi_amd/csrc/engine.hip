@@ -35,6 +35,7 @@
 #include "term_walk.hpp"
 #include "factor_state.hpp"
 #include "eval_plan.hpp"
+#include "kernel_dispatch.hpp"
 #include "covariance.hpp"
 #include "gemm_f64.hpp"
 #include "gemm_splitk.hpp"
@@ -366,8 +367,6 @@ int fail(gmb_engine* e, int code, const char* fmt, ...) {
 int alloc_refused(void* owner, size_t bytes, const char* why) {
   return fail(static_cast<gmb_engine*>(owner), GMB_ENOMEM, "hipMalloc of %lld bytes failed: %s", (long long)bytes, why);
 }
-
-int pick_nc(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : 16; }
 
 // ---- timing helpers -----------------------------------------------------------------------
 struct PhaseTimer {
@@ -733,22 +732,6 @@ long long cov_grid_blocks(int ti, int tj, int strip, int tri_grid, int row_first
   return (long long)ti * nst;
 }
 
-template <int KIND>
-int launch_cov_nc(gmb_engine* e, const CovTileArgs& a, int nc) {
-  const long long nb = cov_grid_blocks(a.ti, a.tj, a.strip, a.tri_grid, a.row_first, a.row_stride) * (a.gsplit > 1 ? a.gsplit : 1);
-  if (nb <= 0) return GMB_OK;
-  const dim3 grid((unsigned)nb), block(256);
-  switch (nc) {
-    case 1: hipLaunchKernelGGL((cov_tile_kernel<KIND, 1>), grid, block, 0, e->stream, a); break;
-    case 2: hipLaunchKernelGGL((cov_tile_kernel<KIND, 2>), grid, block, 0, e->stream, a); break;
-    case 4: hipLaunchKernelGGL((cov_tile_kernel<KIND, 4>), grid, block, 0, e->stream, a); break;
-    case 8: hipLaunchKernelGGL((cov_tile_kernel<KIND, 8>), grid, block, 0, e->stream, a); break;
-    default: hipLaunchKernelGGL((cov_tile_kernel<KIND, 16>), grid, block, 0, e->stream, a); break;
-  }
-  HIP_TRY(e, hipGetLastError());
-  return GMB_OK;
-}
-
 int launch_cov(gmb_engine* e, const CovTileArgs& a_in) {
   if (a_in.ti <= 0 || a_in.tj <= 0) return GMB_OK;
   CovTileArgs a = a_in;
@@ -759,14 +742,16 @@ int launch_cov(gmb_engine* e, const CovTileArgs& a_in) {
   // small grids (up to 1024 tiles, N <= 5.7k): four workgroups per tile (N = 392: the build's one launch 29.6 -> 11.8 us, N = 2560:
   // 43 -> 30, N = 4000: 55 -> 39, N = 5200: 61 -> 50; from ~2000 tiles on the split costs more than the direct-loop tiles' tail)
   a.gsplit = (a.strip == 1 && cov_grid_blocks(a.ti, a.tj, 1, a.tri_grid, a.row_first, a.row_stride) <= 1024) ? 4 : 1;
-  switch (a.p.kind) {
-    case GMB_EXPQUAD: return launch_cov_nc<0>(e, a, e->nc_pad);
-    case GMB_MATERN52: return launch_cov_nc<1>(e, a, e->nc_pad);
-    case GMB_MATERN32: return launch_cov_nc<2>(e, a, e->nc_pad);
-    case GMB_MATERN12: return launch_cov_nc<3>(e, a, e->nc_pad);
-    case GMB_EXPONENTIAL: return launch_cov_nc<4>(e, a, e->nc_pad);
-  }
-  return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
+  const long long nb = cov_grid_blocks(a.ti, a.tj, a.strip, a.tri_grid, a.row_first, a.row_stride) * (a.gsplit > 1 ? a.gsplit : 1);
+  if (nb <= 0) return GMB_OK;
+  const dim3 grid((unsigned)nb), block(256);
+  const bool known = with_kind_nc(a.p.kind, e->nc_pad, [&](auto kind, auto nc) {
+    constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+    hipLaunchKernelGGL((cov_tile_kernel<K, NC>), grid, block, 0, e->stream, a);
+  });
+  if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
 }
 
 int spec_ntab(const gmb_kernel_spec& s) { return s.n_coreg + (s.out_col >= 0 ? 1 : 0); }
@@ -1763,33 +1748,26 @@ int winv_level_batched(gmb_engine* e, hipStream_t s, const gmb_engine::InvLevelP
   return GMB_OK;
 }
 
-template <int KIND>
-int launch_grad_nc(gmb_engine* e, const GradArgs& a_in, int nblocks) {
+// one term's trace reductions: the direct-loop tiles, and behind them the interior tiles of a split pass (kinds 0 - 2 only)
+int launch_grad(gmb_engine* e, const GradArgs& a_in, int nblocks) {
   const dim3 grid(nblocks), block(256);
   const size_t lds = grad_lds_bytes(e->nc_pad, a_in.p.n_lin, a_in.p.n_tab);
   GradArgs a = a_in;
   a.part_block0 = 0;
   const int gs = a.gsplit > 1 ? a.gsplit : 1;
   const dim3 grid0((a.split ? a.general_tiles : nblocks) * gs);  // (split: one tile of the general-tile list per gs workgroups)
-  switch (e->nc_pad) {
-    case 1: hipLaunchKernelGGL((grad_tile_kernel<KIND, 1>), grid0, block, lds, e->stream, a); break;
-    case 2: hipLaunchKernelGGL((grad_tile_kernel<KIND, 2>), grid0, block, lds, e->stream, a); break;
-    case 4: hipLaunchKernelGGL((grad_tile_kernel<KIND, 4>), grid0, block, lds, e->stream, a); break;
-    case 8: hipLaunchKernelGGL((grad_tile_kernel<KIND, 8>), grid0, block, lds, e->stream, a); break;
-    default: hipLaunchKernelGGL((grad_tile_kernel<KIND, 16>), grid0, block, lds, e->stream, a); break;
-  }
-  if constexpr (KIND <= 2) {
-    if (a.split) {  // the interior tiles on the matrix pipe: runs of the full enumeration, the partial vectors behind the first set
-      a.part_block0 = a.general_tiles * gs;
-      switch (e->nc_pad) {
-        case 1: hipLaunchKernelGGL((grad_interior_kernel<KIND, 1>), grid, block, 0, e->stream, a); break;
-        case 2: hipLaunchKernelGGL((grad_interior_kernel<KIND, 2>), grid, block, 0, e->stream, a); break;
-        case 4: hipLaunchKernelGGL((grad_interior_kernel<KIND, 4>), grid, block, 0, e->stream, a); break;
-        case 8: hipLaunchKernelGGL((grad_interior_kernel<KIND, 8>), grid, block, 0, e->stream, a); break;
-        default: hipLaunchKernelGGL((grad_interior_kernel<KIND, 16>), grid, block, 0, e->stream, a); break;
+  // (two launches, so the kind and the width are taken apart: the kind once, the width for each launch)
+  const bool known = with_kind(a.p.kind, [&](auto kind) {
+    constexpr int K = decltype(kind)::value;
+    with_nc(e->nc_pad, [&](auto nc) { hipLaunchKernelGGL((grad_tile_kernel<K, decltype(nc)::value>), grid0, block, lds, e->stream, a); });
+    if constexpr (K <= 2) {
+      if (a.split) {  // the interior tiles on the matrix pipe: runs of the full enumeration, the partial vectors behind the first set
+        a.part_block0 = a.general_tiles * gs;
+        with_nc(e->nc_pad, [&](auto nc) { hipLaunchKernelGGL((grad_interior_kernel<K, decltype(nc)::value>), grid, block, 0, e->stream, a); });
       }
     }
-  }
+  });
+  if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
@@ -1913,14 +1891,7 @@ int grad_reduce(gmb_engine* e, int shard, int nshards, const double* Z, int64_t 
         HIP_TRY(e, hipMemsetAsync(e->dgbig, 0, (size_t)ndirect * a.gsplit * 4 * big * sizeof(double), e->stream));
         a.big = e->dgbig;
       }
-      switch (tr.cp.kind) {
-        case GMB_EXPQUAD: rc = launch_grad_nc<0>(e, a, grid); break;
-        case GMB_MATERN52: rc = launch_grad_nc<1>(e, a, grid); break;
-        case GMB_MATERN32: rc = launch_grad_nc<2>(e, a, grid); break;
-        case GMB_MATERN12: rc = launch_grad_nc<3>(e, a, grid); break;
-        default: rc = launch_grad_nc<4>(e, a, grid); break;
-      }
-      if (rc) return rc;
+      if ((rc = launch_grad(e, a, grid))) return rc;
       // second stage: dense slots of the partial vectors -> the term's accumulator region
       GradRanges r{};
       auto add = [&](int dense, int count, int dst) {
@@ -3380,37 +3351,17 @@ int launch_draw(gmb_engine* e, const DrawArgs& a) {
 
 // ---- gradients of the posterior mean and variance (predict_grad.hpp) -----------------------------------------------------------------
 
-template <int KIND, int NC>
-void launch_predict_grad_nc(gmb_engine* e, const PredGradArgs& a, dim3 grid, bool gen, int nset) {
-  auto go = [&](void (*kernel)(PredGradArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
-  if (nset == 2) go(gen ? predict_grad_partial_kernel<KIND, NC, true, 2> : predict_grad_partial_kernel<KIND, NC, false, 2>);
-  else go(gen ? predict_grad_partial_kernel<KIND, NC, true, 1> : predict_grad_partial_kernel<KIND, NC, false, 1>);
-}
-
-template <int KIND>
-void launch_predict_grad_kind(gmb_engine* e, const PredGradArgs& a, dim3 grid, bool gen, int nset) {
-  switch (e->nc_pad) {
-    case 1: launch_predict_grad_nc<KIND, 1>(e, a, grid, gen, nset); break;
-    case 2: launch_predict_grad_nc<KIND, 2>(e, a, grid, gen, nset); break;
-    case 4: launch_predict_grad_nc<KIND, 4>(e, a, grid, gen, nset); break;
-    case 8: launch_predict_grad_nc<KIND, 8>(e, a, grid, gen, nset); break;
-    default: launch_predict_grad_nc<KIND, 16>(e, a, grid, gen, nset); break;
-  }
-}
-
-// one term's partials, `nset` accumulator sets, for the prepared test points in pg_xs / pg_xl / pg_cat (dispatched as launch_cov
-// dispatches the tiles)
+// one term's partials, `nset` accumulator sets, for the prepared test points in pg_xs / pg_xl / pg_cat
 int launch_predict_grad(gmb_engine* e, const PredGradArgs& a, int nchunk, int nset) {
   const dim3 grid((unsigned)(a.test.npad / PG_PTS), (unsigned)nchunk);
   const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
-  switch (a.p.kind) {
-    case GMB_EXPQUAD: launch_predict_grad_kind<0>(e, a, grid, gen, nset); break;
-    case GMB_MATERN52: launch_predict_grad_kind<1>(e, a, grid, gen, nset); break;
-    case GMB_MATERN32: launch_predict_grad_kind<2>(e, a, grid, gen, nset); break;
-    case GMB_MATERN12: launch_predict_grad_kind<3>(e, a, grid, gen, nset); break;
-    case GMB_EXPONENTIAL: launch_predict_grad_kind<4>(e, a, grid, gen, nset); break;
-    default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
-  }
+  const bool known = with_kind_nc(a.p.kind, e->nc_pad, [&](auto kind, auto nc) {
+    constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+    auto go = [&](void (*kernel)(PredGradArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
+    if (nset == 2) go(gen ? predict_grad_partial_kernel<K, NC, true, 2> : predict_grad_partial_kernel<K, NC, false, 2>);
+    else go(gen ? predict_grad_partial_kernel<K, NC, true, 1> : predict_grad_partial_kernel<K, NC, false, 1>);
+  });
+  if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
@@ -3654,34 +3605,21 @@ int decompose_tile(gmb_engine* e, const double* Xs, int64_t mc, int64_t mpad, in
 
 // ---- the posterior of the slope (predict_slope.hpp) ---------------------------------------------------------------------------------
 
-template <int KIND, int NC>
-void launch_slope_cov_nc(gmb_engine* e, const SlopeCovArgs& a, dim3 grid, bool gen) {
-  if (gen) hipLaunchKernelGGL((slope_cross_cov_kernel<KIND, NC, true>), grid, dim3(256), 0, e->stream, a);
-  else hipLaunchKernelGGL((slope_cross_cov_kernel<KIND, NC, false>), grid, dim3(256), 0, e->stream, a);
-}
-
-template <int KIND>
-void launch_slope_cov_kind(gmb_engine* e, const SlopeCovArgs& a, dim3 grid, bool gen) {
-  switch (e->nc_pad) {
-    case 1: launch_slope_cov_nc<KIND, 1>(e, a, grid, gen); break;
-    case 2: launch_slope_cov_nc<KIND, 2>(e, a, grid, gen); break;
-    case 4: launch_slope_cov_nc<KIND, 4>(e, a, grid, gen); break;
-    case 8: launch_slope_cov_nc<KIND, 8>(e, a, grid, gen); break;
-    default: launch_slope_cov_nc<KIND, 16>(e, a, grid, gen); break;
-  }
-}
-
-// one term's derivative cross-covariance of an M-tile into the stacked dV (dispatched as launch_predict_grad, kinds 0 - 2 only:
-// gmb_predict_slope has refused the others)
+// one term's derivative cross-covariance of an M-tile into the stacked dV (kinds 0 - 2 only: the others have no kernel, and
+// gmb_predict_slope has refused them)
 int launch_slope_cov(gmb_engine* e, const SlopeCovArgs& a) {
   const dim3 grid((unsigned)(a.test.npad / SC_PTS), (unsigned)(e->Np / SC_PIECE));
   const bool gen = a.p.n_lin > 0 || a.p.n_tab > 0;
-  switch (a.p.kind) {
-    case GMB_EXPQUAD: launch_slope_cov_kind<0>(e, a, grid, gen); break;
-    case GMB_MATERN52: launch_slope_cov_kind<1>(e, a, grid, gen); break;
-    case GMB_MATERN32: launch_slope_cov_kind<2>(e, a, grid, gen); break;
-    default: return fail(e, GMB_EINVAL, "kernel kind %d has no derivative process", a.p.kind);
-  }
+  if (a.p.kind == GMB_MATERN12 || a.p.kind == GMB_EXPONENTIAL)
+    return fail(e, GMB_EINVAL, "kernel kind %d has no derivative process", a.p.kind);
+  const bool known = with_kind_nc(a.p.kind, e->nc_pad, [&](auto kind, auto nc) {
+    constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+    if constexpr (K <= 2) {
+      if (gen) hipLaunchKernelGGL((slope_cross_cov_kernel<K, NC, true>), grid, dim3(256), 0, e->stream, a);
+      else hipLaunchKernelGGL((slope_cross_cov_kernel<K, NC, false>), grid, dim3(256), 0, e->stream, a);
+    }
+  });
+  if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
   HIP_TRY(e, hipGetLastError());
   return GMB_OK;
 }
@@ -4226,28 +4164,10 @@ int leave_out_impl(gmb_engine* e, const int64_t* idx, int64_t m, int32_t with_no
 
 // ---- averages of the posterior over groups of points (group_average.hpp) ------------------------------------------------------------
 
-template <int KIND, int NC>
-void launch_group_cov_nc(gmb_engine* e, const GroupCovArgs& a, dim3 grid, bool gen) {
-  auto go = [&](void (*kernel)(GroupCovArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
-  if (gen) go(group_cov_partial_kernel<KIND, NC, true>);
-  else go(group_cov_partial_kernel<KIND, NC, false>);
-}
-
-template <int KIND>
-void launch_group_cov_kind(gmb_engine* e, const GroupCovArgs& a, dim3 grid, bool gen) {
-  switch (e->nc_pad) {
-    case 1: launch_group_cov_nc<KIND, 1>(e, a, grid, gen); break;
-    case 2: launch_group_cov_nc<KIND, 2>(e, a, grid, gen); break;
-    case 4: launch_group_cov_nc<KIND, 4>(e, a, grid, gen); break;
-    case 8: launch_group_cov_nc<KIND, 8>(e, a, grid, gen); break;
-    default: launch_group_cov_nc<KIND, 16>(e, a, grid, gen); break;
-  }
-}
-
 constexpr int64_t GA_TASK_SLAB = 32768;  // tasks per launch (the grid's y extent)
 
-// The partials of `ntask` tasks (a.tasks: the first one's triple, a.part: its row) against a.cols, dispatched as launch_cov /
-// launch_predict_grad dispatch theirs; lists longer than the grid's y extent go in slabs.
+// The partials of `ntask` tasks (a.tasks: the first one's triple, a.part: its row) against a.cols; lists longer than the grid's
+// y extent go in slabs.
 int launch_group_cov(gmb_engine* e, const GroupCovArgs& a_in, int64_t ntask) {
   const bool gen = a_in.p.n_lin > 0 || a_in.p.n_tab > 0;
   for (int64_t t0 = 0; t0 < ntask; t0 += GA_TASK_SLAB) {
@@ -4255,14 +4175,13 @@ int launch_group_cov(gmb_engine* e, const GroupCovArgs& a_in, int64_t ntask) {
     a.tasks += 3 * t0;
     a.part += t0 * a.ldp;
     const dim3 grid((unsigned)(a.ldp / GA_COLS), (unsigned)std::min<int64_t>(GA_TASK_SLAB, ntask - t0));
-    switch (a.p.kind) {
-      case GMB_EXPQUAD: launch_group_cov_kind<0>(e, a, grid, gen); break;
-      case GMB_MATERN52: launch_group_cov_kind<1>(e, a, grid, gen); break;
-      case GMB_MATERN32: launch_group_cov_kind<2>(e, a, grid, gen); break;
-      case GMB_MATERN12: launch_group_cov_kind<3>(e, a, grid, gen); break;
-      case GMB_EXPONENTIAL: launch_group_cov_kind<4>(e, a, grid, gen); break;
-      default: return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
-    }
+    const bool known = with_kind_nc(a.p.kind, e->nc_pad, [&](auto kind, auto nc) {
+      constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+      auto go = [&](void (*kernel)(GroupCovArgs)) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, a); };
+      if (gen) go(group_cov_partial_kernel<K, NC, true>);
+      else go(group_cov_partial_kernel<K, NC, false>);
+    });
+    if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
     HIP_TRY(e, hipGetLastError());
   }
   return GMB_OK;
@@ -4884,17 +4803,6 @@ PointSet fitc_x_tile(const gmb_engine* e, const FitcTile& tl) {
   return PointSet{e->pts.xs + tl.first, e->pts.xl + tl.first, e->pts.cat + tl.first, tl.count, e->Nr};
 }
 
-template <int KIND>
-void launch_fitc_deriv_nc(gmb_engine* e, const FitcDerivArgs& a, dim3 grid) {
-  switch (e->nc_pad) {
-    case 1: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 1>), grid, dim3(256), 0, e->stream, a); break;
-    case 2: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 2>), grid, dim3(256), 0, e->stream, a); break;
-    case 4: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 4>), grid, dim3(256), 0, e->stream, a); break;
-    case 8: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 8>), grid, dim3(256), 0, e->stream, a); break;
-    default: hipLaunchKernelGGL((fitc_deriv_kernel<KIND, 16>), grid, dim3(256), 0, e->stream, a); break;
-  }
-}
-
 // sum G o dk(rows, cols) / dtheta over `pad_rows` x `pad_cols` padded pairs, added to acc[0 .. FITC_DERIV_SUMS)
 int fitc_deriv(gmb_engine* e, const PointSet& rows, int64_t pad_rows, const PointSet& cols, int64_t pad_cols, const double* G, int64_t ldg,
                double* acc) {
@@ -4911,12 +4819,13 @@ int fitc_deriv(gmb_engine* e, const PointSet& rows, int64_t pad_rows, const Poin
   const int64_t nblk = (int64_t)a.ti * a.tj;
   const dim3 grid((unsigned)nblk);
   ev_begin(e, e->stream, EV_FITC, 0.0, a.ti, a.tj, 0, 3);
-  switch (a.p.kind) {
-    case GMB_EXPQUAD: launch_fitc_deriv_nc<0>(e, a, grid); break;
-    case GMB_MATERN52: launch_fitc_deriv_nc<1>(e, a, grid); break;
-    case GMB_MATERN32: launch_fitc_deriv_nc<2>(e, a, grid); break;
-    case GMB_MATERN12: launch_fitc_deriv_nc<3>(e, a, grid); break;
-    default: launch_fitc_deriv_nc<4>(e, a, grid); break;
+  const bool known = with_kind_nc(a.p.kind, e->nc_pad, [&](auto kind, auto nc) {
+    constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+    hipLaunchKernelGGL((fitc_deriv_kernel<K, NC>), grid, dim3(256), 0, e->stream, a);
+  });
+  if (!known) {
+    ev_end(e);
+    return fail(e, GMB_EINVAL, "unknown kernel kind %d", a.p.kind);
   }
   hipLaunchKernelGGL(fitc_fold_kernel, dim3(1), dim3(256), 0, e->stream, s.dredpart, nblk, FITC_DERIV_SUMS, 0, FITC_DERIV_SUMS, acc, 1);
   ev_end(e);

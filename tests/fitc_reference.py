@@ -226,6 +226,8 @@ PROBLEMS = {
     "exponential-m1": ("Exponential", 300, 2, 1, 0.1, True),    # m = 1
     "expquad-shared": ("ExpQuad", 300, 2, 48, 0.1, False),      # one lengthscale for both columns
 }
+#: every kind at every padded width 1, 2, 4, 8, 16 of the derivative kernel: N = 200, m = 16, eta = 1.1, sigma = 0.25
+DISPATCH = {f"{kind}-d{d}": (kind, 200, d, 16, 0.25, True) for kind in O.KINDS for d in (1, 2, 3, 5, 9)}
 TILE_ROWS_SMALL_M = 32768  # columns of X per tile of the plan for small m (tests/test_fitc_cpu.py checks it against the engine)
 SEAM = ("Matern52", TILE_ROWS_SMALL_M + 77, 2, 16, 0.2, True)  # two column tiles of X: the second one ragged
 TEST_POINTS = (1, 129, 200)
@@ -234,10 +236,10 @@ TEST_POINTS = (1, 129, 200)
 @functools.lru_cache(maxsize=None)
 def problem(name):
     """(spec, theta, X, y, Z, Xs) of a named problem; every array read-only"""
-    kind, N, d, m, sigma, ard = SEAM if name == "seam" else PROBLEMS[name]
+    kind, N, d, m, sigma, ard = SEAM if name == "seam" else DISPATCH[name] if name in DISPATCH else PROBLEMS[name]
     X, y, ls = O.synthetic_table(N, d, seed=7 + N, sigma=sigma)
     spec = O.make_spec(d, range(d), kind=kind, ard=ard)
-    theta = O.pack_theta(spec, ls if ard else [float(np.mean(ls))], 1.0, sigma)
+    theta = O.pack_theta(spec, ls if ard else [float(np.mean(ls))], 1.1 if name in DISPATCH else 1.0, sigma)
     Z = kmeans_points(X, m, seed=11)
     Xs = np.random.default_rng(3).standard_normal((max(TEST_POINTS), d)) * 1.2
     for a in (theta, X, y, Z, Xs):

@@ -1,7 +1,7 @@
 """The sparse (FITC) path of the engine against an extended-precision reference -- runs on the MI355X box only (``-m gpu``).
 
-The problems are tests/fitc_reference.py's (``PROBLEMS`` and ``seam``: two column tiles of X behind m = 16), Z from seeded k-means
-of X, test points M in {1, 129, 200}.  The engine and the float64 host restatement (LAPACK) are each compared with the longdouble
+The problems are tests/fitc_reference.py's (``PROBLEMS``; ``seam``: two column tiles of X behind m = 16; ``DISPATCH``: every kind
+at every padded width of the derivative kernel, N = 200, m = 16), Z from seeded k-means of X, test points M in {1, 129, 200}.  The engine and the float64 host restatement (LAPACK) are each compared with the longdouble
 reference; for every problem and quantity the engine's error may be at most
 
     max(8 x the host's error, floor)
@@ -81,7 +81,7 @@ class Bars:
 
 
 # ---- values ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + list(F.DISPATCH))  # (DISPATCH: fitc_deriv_kernel<KIND, NC> at every kind and width)
 def test_engine_within_8x_of_the_float64_host(gpu, name):
     spec, theta, X, y, Z, Xs = F.problem(name)
     bars = Bars(name)

@@ -29,6 +29,7 @@ import pytest
 
 import abi_forms as AF
 import group_average_reference as GA
+from oracle import gp_oracle as O
 from test_gpu_abi_forms import FORMS, mat_in, mat_out, sync, take, take_vec, vec_in, vec_out
 from test_gpu_parity import make_engine
 
@@ -104,6 +105,31 @@ def test_against_the_definition(gpu, name, state):
                 assert rel_err(var_d, var, what + " var without cov against var with cov") <= 1e-10
             assert same_bits(results["null"], results["mean"]), f"{name} {state} {which}: NULL weights differ from explicit 1 / |g|"
         assert takes_product_form(eng, X) == (state == "product")
+
+
+@pytest.mark.parametrize("kind", list(O.KINDS))
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 9])
+def test_every_kind_and_width_against_the_definition(gpu, kind, d):
+    """group_cov_partial_kernel<KIND, NC, false> for every kind at every padded width 1, 2, 4, 8, 16 (the general form
+    is the three-term model's above).  N = 200 (two block columns, the second ragged), three groups of 1, 5 and 64 points (M = 70)
+    0.3 off training rows, plain means; eta = 1.1, sigma = 0.25: cond(Sigma) <= 1 + N eta^2 / sigma^2 = 3.9e3, below the Matern
+    table's, so the bars are the ones above."""
+    N = 200
+    X, y, ls = O.synthetic_table(N, d, seed=1000 * d + N)
+    spec = O.make_spec(d, range(d), kind=kind)
+    theta = O.pack_theta(spec, ls, 1.1, 0.25)
+    offsets = GA.offsets_of([1, 5, 64])
+    rng = np.random.default_rng(17)
+    Xs = X[rng.integers(0, N, int(offsets[-1]))] + 0.3 * rng.standard_normal((int(offsets[-1]), d))
+    mean_r, cov_r = GA.by_joint(spec, theta, X, y, Xs, offsets, None)
+    norms = GA.weight_norms(offsets, None)
+    with make_engine(spec, theta, X, y) as eng:
+        eng.factorize()
+        mean, var, cov = eng.predict_groups(Xs, offsets, None, cov=True)
+    what = f"{kind} d = {d}"
+    assert rel_err(mean, mean_r, what + " mean") <= 1e-8
+    assert cov_err(var, np.diag(cov_r), norms, what + " var") <= 1e-9
+    assert cov_err(cov, cov_r, norms, what + " cov") <= 1e-9
 
 
 # ---- 2. engine against engine on the same factor -----------------------------------------------------------------------------------------

@@ -549,6 +549,25 @@ def test_nlml_gradient_matches_oracle(gpu, kind, ard):
     assert not eng.factor_is_current()
 
 
+@pytest.mark.parametrize("kind", list(O.KINDS))
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 9])
+def test_direct_loop_trace_reductions_at_every_kind_and_width(gpu, kind, d):
+    """grad_tile_kernel<KIND, NC> for every kind at every padded width 1, 2, 4, 8, 16.  N = 200: two block columns,
+    the second ragged, three tiles -- up to 128 tiles every tile goes through the direct loops of the one launch, so the smooth
+    kinds take it too (their interior launch: the test below).  With eta = 1.1, sigma = 0.25: cond(Sigma) <= 1 + N eta^2 /
+    sigma^2 = 3.9e3."""
+    N = 200
+    X, y, ls = O.synthetic_table(N, d, seed=200 + d)
+    spec = O.make_spec(d, range(d), kind=kind)
+    theta = O.pack_theta(spec, ls, 1.1, 0.25)
+    with make_engine(spec, theta, X, y) as eng:
+        val, g = eng.evaluate(theta, grad=True)
+    val_r, g_r = O.nlml_and_grad(spec, theta, X, y, dist_mode="direct")
+    print(f"{kind} d={d}: max |g - g_ref| = {np.max(np.abs(g - g_r)):.3e}, max |g_ref| = {np.max(np.abs(g_r)):.3e}")
+    assert np.isclose(val, val_r, rtol=1e-11)
+    assert np.max(np.abs(g - g_r)) < 1e-8 * max(1.0, np.max(np.abs(g_r)))
+
+
 @pytest.mark.parametrize("kind", ["ExpQuad", "Matern52", "Matern32"])
 @pytest.mark.parametrize("d,ard", [(1, True), (2, True), (3, False), (5, True), (8, True), (11, True), (16, False)])
 def test_interior_tiles_of_the_trace_reductions_match_the_oracle(gpu, kind, d, ard):

@@ -48,11 +48,15 @@ def check(got, ref, what):
 
 
 # ---- 1. against the reference ------------------------------------------------------------------------------------------------
+DISPATCH_DIMS = (1, 2, 3, 5, 9)  # continuous columns that pad to the widths 1, 2, 4, 8, 16 the kernels are compiled for
+
 STATIONARY = ([("ExpQuad", 300, 1, 100, True, 0), ("Matern52", 600, 2, 400, True, 0)]
               + [(k, 300, 3, 77, True, 26) for k in O.KINDS]          # a third of the points exactly on training points
               + [("Matern32", 1000, 3, 333, True, 0),                 # ragged: 8 blocks of N, 6 of M, both with a tail
                  ("ExpQuad", 260, 16, 50, True, 0),                   # every prepared column in use
-                 ("Matern52", 300, 3, 77, False, 0)])                 # one shared lengthscale
+                 ("Matern52", 300, 3, 77, False, 0)]                  # one shared lengthscale
+              # every kind at every padded width 1, 2, 4, 8, 16: two block columns of N, the second ragged
+              + [(k, 200, d, 70, True, 0) for k in O.KINDS for d in DISPATCH_DIMS])
 
 
 @pytest.mark.parametrize("kind,N,d,M,ard,on_train", STATIONARY)

@@ -30,6 +30,7 @@ import pytest
 
 import abi_forms as AF
 import slope_reference as SR
+from oracle import gp_oracle as O
 from test_gpu_abi_forms import FORMS, mat_in, mat_out, sync, take
 from test_gpu_parity import make_engine
 
@@ -114,6 +115,30 @@ def test_against_the_reference(gpu, name, state):
             assert mean_err(dmean, G, what + " dmean against gmb_predict_grad") <= 1e-8
         eng.predict(SR.points(name, 129)[:3])
         assert eng.timings()["predict_gemm_form"] == (1 if state == "product" else 0)
+
+
+@pytest.mark.parametrize("kind", ["ExpQuad", "Matern52", "Matern32"])
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 9])
+def test_every_kind_and_width_against_the_reference(gpu, kind, d):
+    """slope_cross_cov_kernel<KIND, NC, false> for every kind with a derivative process at every padded width 1, 2, 4, 8, 16 (DESIGN
+    2.4; the general form is the three-term model's above).  N = 200 (two block columns, the second ragged), M = 70 points 0.3 off
+    training rows; eta = 1.1, sigma = 0.25: cond(Sigma) <= 1 + N eta^2 / sigma^2 = 3.9e3, below the N = 700 table's bound, so the
+    bars are the ones above."""
+    N, M = 200, 70
+    X, y, ls = O.synthetic_table(N, d, seed=1000 * d + N)
+    spec = O.make_spec(d, range(d), kind=kind)
+    theta = O.pack_theta(spec, ls, 1.1, 0.25)
+    rng = np.random.default_rng(M)
+    Xs = X[rng.integers(0, N, M)] + 0.3 * rng.standard_normal((M, d))
+    dmean_r, dvar_r, dcov_r = SR.posterior(spec, theta, X, y, Xs)
+    scale = max(1.0, float(np.max(np.abs(SR.prior_curvature(spec, theta, X, Xs)))))
+    with engine_for(spec, theta, X, y, state="solve") as eng:
+        out = dmean, dvar, dcov = eng.predict_slope(Xs, cov=True)
+    what = f"{kind} d = {d}"
+    assert mean_err(dmean, dmean_r, what + " dmean") <= 1e-8
+    assert cov_err(dvar, dvar_r, scale, what + " dvar") <= 1e-9
+    assert cov_err(dcov, dcov_r, scale, what + " dcov") <= 1e-9
+    check_structure(out, spec, what)
 
 
 # ---- 2. selections of an additive model's terms ---------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ import pytest
 import var_grad_reference as VR
 from oracle import gp_oracle as O
 from test_gpu_parity import GOLD, golden_spec, make_engine, rel
-from test_gpu_predict_grad import frontend_dataset, points, table
+from test_gpu_predict_grad import DISPATCH_DIMS, frontend_dataset, points, table
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +72,8 @@ CASES = {"ExpQuad-N300-d1-M100": _stationary("ExpQuad", 300, 1, 100),           
          "Matern32-N1000-d3-M333": _stationary("Matern32", 1000, 3, 333),                   # eight block columns, M with a tail
          "ExpQuad-N260-d16-M50": _stationary("ExpQuad", 260, 16, 50),                       # every prepared column
          "Matern52-shared-ls": _stationary("Matern52", 300, 3, 77, ard=False),
+         # every kind at every padded width 1, 2, 4, 8, 16: two block columns of N, the second ragged
+         **{f"{k}-N200-d{d}-M70": _stationary(k, 200, d, 70) for k in O.KINDS for d in DISPATCH_DIMS},
          "composite_N140": _composite,
          "additive-N300": _additive,
          "Matern52+Periodic": _periodic("Matern52", 1),
