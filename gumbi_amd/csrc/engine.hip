@@ -52,6 +52,7 @@
 #include "group_average.hpp"
 #include "predict_slope.hpp"
 #include "design_batch.hpp"
+#include "predict_batches.hpp"
 #include "fitc.hpp"
 #include "laplace.hpp"
 
@@ -97,11 +98,13 @@ enum EvKind : int {
   EV_FITC = 21,               // the sparse path's own launches (mt x nt tiles of the block): flags = 0 a cross-covariance against Z, 1 a
                               // pass V L^-1, 2 a column / row / adjoint / transpose pass over a block, 3 a derivative reduction or the
                               // prediction's reduction
+  EV_BATCH = 23,              // gmb_predict_batches: the contraction launches of one M-tile (mt = batches, nt = chunks, k = q; flags = 0
+                              // the partial + finishing launches of Q = V V^T, 1 those of one term's derivative sums)
   EV_LAPLACE = 22             // gmb_laplace_evaluate: a PHASE, around the launches listed above (mt = block rows, k = Newton iteration;
                               // flags = 0 the build of Sigma, 1 a build of B or Z', 2 a Cholesky with its two vector solves, 3 a symmetric
                               // matrix-vector product, 4 elementwise and likelihood work, 5 the inverse, 6 the trace pass)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_LAPLACE); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_BATCH); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -207,6 +210,7 @@ struct gmb_engine {
   DevBuf<double> ga_part;   // [task][column] of one reduction
   SlopeWorkspace slope;     // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
+  BatchWorkspace bw;        // gmb_predict_batches (predict_batches.hpp), beside a prediction's and gmb_predict_grad's workspaces
   DesignWorkspace dz;       // gmb_design_batch (design_batch.hpp), beside a prediction's workspace of one point tile
   FitcState fitc;           // the sparse (FITC) path: everything it keeps (workspaces.hpp), nothing of it shared with the exact path
   LaplaceState lap;         // GP classification (laplace.hpp): Sigma and the vectors; B's factor sits in the factor buffer, FactorState "not factored"
@@ -530,7 +534,8 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_SLOPE_COV:
       case EV_DESIGN:
       case EV_FITC:
-      case EV_LAPLACE: break;
+      case EV_LAPLACE:
+      case EV_BATCH: break;
     }
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -5584,6 +5589,167 @@ int gmb_predict_with_grad(gmb_engine* e, const double* Xs, int64_t M, int64_t ld
   };
   return predict_end(e, &tp, tiles());
 }
+
+// ---- joint posteriors of many small batches (predict_batches.hpp) ------------------------------------------------------------------
+
+// Q = V V^T per batch of one tile into the covariance blocks: bw.cov = diag(k**) - Q + jitter I (V in dV, k** in dkss)
+int batch_gram(gmb_engine* e, const BatchPlan& pl, const BatchTile& tl, double jitter) {
+  BatchGramArgs a{};
+  a.V = e->pw.dV;
+  a.mpad = tl.mpad;
+  a.N = e->N;
+  a.nb = tl.nb;
+  a.chunk = tl.chunk;
+  a.q = pl.q;
+  a.part = e->bw.part;
+  ev_begin(e, e->stream, EV_BATCH, 2.0 * 256.0 * (double)e->N * (double)tl.nb, (int)tl.nb, (int)tl.nchunk, pl.q, 0);
+  hipLaunchKernelGGL(batch_gram_partial_kernel, dim3((unsigned)tl.nb, (unsigned)tl.nchunk), dim3(64), 0, e->stream, a);
+  BatchCovFinishArgs f{};
+  f.part = e->bw.part;
+  f.nchunk = (int32_t)tl.nchunk;
+  f.q = pl.q;
+  f.nb = tl.nb;
+  f.kss = e->pw.dkss;
+  f.jitter = jitter;
+  f.cov = e->bw.cov;
+  hipLaunchKernelGGL(batch_cov_finish_kernel, dim3((unsigned)((tl.mc * pl.q + 255) / 256)), dim3(256), 0, e->stream, f);
+  ev_end(e);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// The walk over the terms of one tile: the prior covariance of the within-batch pairs into bw.cov and, with W = V L^-1 in dV
+// (`grad`), every term's derivative sums into bw.dcov.  The tile's points are prepared per term into the prediction workspace,
+// whose prepared points have served the cross-covariance.
+int batch_terms(gmb_engine* e, const BatchPlan& pl, const BatchTile& tl, bool grad) {
+  int rc;
+  const unsigned nthreads = (unsigned)((tl.mc * pl.q + 255) / 256);  // one thread per (batch, j, l)
+  if (grad) HIP_TRY(e, hipMemsetAsync(e->bw.dcov, 0, (size_t)(tl.mc * pl.q * e->D) * sizeof(double), e->stream));
+  return walk_terms(e, ALL_TERMS, [&](int t) -> int {
+    const gmb_engine::Term& tr = e->terms[t];
+    if ((rc = prep_points(e, e->pw.dXs, tl.mc, e->D, tl.mpad, e->pw.txs, e->pw.txl, e->pw.tcat, &tr.pa))) return rc;
+    BatchTermArgs ta{};
+    ta.p = tr.cp;
+    ta.txs = e->pw.txs;
+    ta.txl = e->pw.txl;
+    ta.tcat = e->pw.tcat;
+    ta.mpad = tl.mpad;
+    ta.nb = tl.nb;
+    ta.q = pl.q;
+    ta.nc_pad = e->nc_pad;
+    BatchGradArgs ga{};
+    BatchGradFinishArgs f{};
+    if (grad) {
+      ga.p = tr.cp;
+      ga.test = PointSet{e->pw.txs, e->pw.txl, e->pw.tcat, tl.mc, tl.mpad};
+      ga.train = train_set(e);
+      ga.W = e->pw.dV;
+      ga.nb = tl.nb;
+      ga.chunk = tl.chunk;
+      ga.q = pl.q;
+      ga.part = e->bw.part;
+      f.t = ta;
+      f.part = e->bw.part;
+      f.nchunk = (int32_t)tl.nchunk;
+      f.nc = tr.pa.nc;
+      f.periodic = tr.pa.periodic;
+      f.D = e->D;
+      for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k];
+      if (tr.pa.periodic) {
+        for (int d = 0; 2 * d < tr.pa.nc; ++d) f.scale[d] = 2.0 * M_PI * tr.pa.two_over_T[d];  // 2 * (2 pi / T_d)
+      } else {
+        for (int k = 0; k < tr.pa.nc; ++k) f.scale[k] = 2.0 * tr.pa.inv_ls[k];
+      }
+      for (int l = 0; l < tr.cp.n_lin; ++l) f.idx_lin[l] = tr.pa.idx_lin[l];
+      f.dcov = e->bw.dcov;
+    }
+    const bool gen = tr.cp.n_lin > 0 || tr.cp.n_tab > 0;
+    const dim3 grid((unsigned)tl.nb, (unsigned)tl.nchunk);
+    const bool known = with_kind_nc(tr.cp.kind, e->nc_pad, [&](auto kind, auto nc) {
+      constexpr int K = decltype(kind)::value, NC = decltype(nc)::value;
+      hipLaunchKernelGGL(batch_prior_kernel<K>, dim3(nthreads), dim3(256), 0, e->stream, ta, (double*)e->bw.cov);
+      if (!grad) return;
+      ev_begin(e, e->stream, EV_BATCH, 2.0 * 256.0 * (double)e->N * (double)tl.nb * (NC + tr.cp.n_lin), (int)tl.nb, (int)tl.nchunk, pl.q, 1);
+      if (gen) hipLaunchKernelGGL((batch_grad_partial_kernel<K, NC, true>), grid, dim3(64), 0, e->stream, ga);
+      else hipLaunchKernelGGL((batch_grad_partial_kernel<K, NC, false>), grid, dim3(64), 0, e->stream, ga);
+      hipLaunchKernelGGL(batch_grad_finish_kernel<K>, dim3(nthreads), dim3(256), 0, e->stream, f);
+      ev_end(e);
+    });
+    if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", tr.cp.kind);
+    HIP_TRY(e, hipGetLastError());
+    return GMB_OK;
+  });
+}
+
+int gmb_predict_batches(gmb_engine* e, const double* Xs, int64_t B, int32_t q, int64_t ldxs, double jitter, double* mean, double* cov,
+                        double* dmean, int64_t ldg, double* dcov, int32_t memspace) {
+  const char* what = "gmb_predict_batches";
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  const bool grad = dmean || dcov;
+  if (q < 1 || q > BATCH_MAX_Q || B < 0)
+    return fail(e, GMB_EINVAL, "%s: B = %lld batches of q = %d points (B >= 0 and 1 <= q <= %d are required)", what, (long long)B, (int)q,
+                BATCH_MAX_Q);
+  if ((B > 0 && (!Xs || !mean || !cov)) || (dmean == nullptr) != (dcov == nullptr) || ldxs < e->D || (grad && ldg < e->D) || !(jitter >= 0.0))
+    return fail(e, GMB_EINVAL, "%s: bad Xs/ldxs/jitter/mean/cov/ldg, or one of dmean and dcov without the other", what);
+  if (B == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  // the plan first (host arithmetic), then the bytes against the device, then the allocation: a refusal has touched nothing
+  BatchPlan pl;
+  if (pl.make(e->N, e->Np, B, q))
+    return fail(e, GMB_EINVAL, "%s: B = %lld batches of q = %d points are more than a call takes (B q <= 2^40)", what, (long long)B, (int)q);
+  int nacc = 1;  // accumulators per (chunk, batch): Q alone, or a term's prepared columns and linear sums
+  if (grad)
+    for (const gmb_engine::Term& tr : e->terms) nacc = std::max<int>(nacc, e->nc_pad + tr.cp.n_lin);
+  const double pg_part = ((double)PG_TARGET_WGS * PG_PTS + (double)pl.mt) * (e->nc_pad + MAX_LIN);  // (predict_grad_workspace, one set)
+  {
+    Budget need;
+    batch_buffers(*e, pl, nacc, grad, pg_part, need);
+    double free_b;
+    if ((rc = device_free_bytes(e, &free_b))) return rc;
+    if (need.fresh > free_b)
+      return fail(e, GMB_ENOMEM, "%s: B = %lld batches of q = %d points behind N = %lld need %.0f bytes on the device (V of one M-tile: %.0f), "
+                                 "%.0f more than it holds for the engine now; %.0f bytes are free -- nothing was computed",
+                  what, (long long)B, (int)q, (long long)e->N, need.total, 8.0 * (double)pl.mt * (double)e->Np, need.fresh, free_b);
+    Reserver take{e->pool};
+    batch_buffers(*e, pl, nacc, grad, pg_part, take);
+    if (take.rc) return take.rc;
+  }
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;  // V is always solved for, as in gmb_predict_with_grad: neither dW nor U is touched
+  const double* alpha = nullptr;
+  if (grad && (rc = resident_alpha(e, &alpha))) return predict_end(e, nullptr, rc);
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  const int64_t qq = (int64_t)q * q;
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t t = 0; t < pl.ntile; ++t) {
+      const BatchTile tl = pl.tile(t);
+      const int64_t m0 = tl.first * q;
+      if ((rc = predict_cross_cov(e, ALL_TERMS, Xs + m0 * ldxs, tl.mc, tl.mpad, ldxs, 0, ck.in))) return rc;
+      if ((rc = predict_solve_v(e, tl.mpad, false))) return rc;
+      if ((rc = predict_reduce(e, tl.mc, tl.mpad, false))) return rc;
+      if ((rc = batch_gram(e, pl, tl, jitter))) return rc;
+      if (grad) {
+        if ((rc = predict_solve_w(e, tl.mpad))) return rc;
+        // (the tile's raw points are in dXs: predict_cross_cov; W = K(X*, X) Sigma^-1 in dV)
+        if ((rc = predict_grad_tile(e, ALL_TERMS, e->pw.dXs, tl.mc, tl.mpad, alpha, nullptr))) return rc;
+      }
+      if ((rc = batch_terms(e, pl, tl, grad))) return rc;
+      if (hipMemcpyAsync(mean + m0, e->pw.dmean, tl.mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          hipMemcpyAsync(cov + tl.first * qq, e->bw.cov, tl.nb * qq * sizeof(double), ck.out, e->stream) != hipSuccess)
+        return fail(e, GMB_EHIP, "%s: copying the values out failed", what);
+      if (grad && (hipMemcpy2DAsync(dmean + m0 * ldg, ldg * sizeof(double), e->pg.grad, row, row, tl.mc, ck.out, e->stream) != hipSuccess ||
+                   hipMemcpyAsync(dcov + tl.first * qq * e->D, e->bw.dcov, tl.nb * qq * row, ck.out, e->stream) != hipSuccess))
+        return fail(e, GMB_EHIP, "%s: copying the gradients out failed", what);
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
+int64_t gmb_debug_batch_plan(int64_t N, int64_t Np, int64_t B, int32_t q, int64_t* out, int64_t cap) { return batch_plan_dump(N, Np, B, q, out, cap); }
 
 int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
                       double* mean, double* cov, int64_t ldc, int32_t memspace) {

@@ -4,11 +4,12 @@
 // for a row count and its other size arguments.  reserve() renews by walking that list, bytes() sums sizeof(T) * count over it and
 // a Budget measures with the two, so what a call is refused for and what it allocates cannot drift apart.  The counts are
 // doubles: a request that has to be refused may not fit in int64_t, and every count that IS allocated is an integer below 2^53.
-// One level up, predict_buffers / joint_buffers / group_buffers / design_buffers list every buffer of a call once, over a visitor
+// One level up, predict_buffers / joint_buffers / group_buffers / design_buffers / batch_buffers list every buffer of a call once, over a visitor
 // (a Budget, then a Reserver); they are templates over the engine, of which they use N, Np, D and the members named in them.
 //
 // No HIP and no engine types: tools/workspace_budget_check.cpp runs this very header over a host allocator.
 #pragma once
+#include "batch_plan.hpp"
 #include "design_plan.hpp"
 #include "device_buffers.hpp"
 #include "fitc_plan.hpp"
@@ -134,6 +135,23 @@ struct DesignWorkspace : Workspace<DesignWorkspace> {
   void sized_for(int64_t Np, int64_t ld, int64_t nchunk, int64_t nres, int D) {
     for_np = Np, for_ld = ld, for_chunks = nchunk, for_res = nres, for_d = D;
   }
+};
+
+// gmb_predict_batches (predict_batches.hpp), by the batches of its largest M-tile: the chunked partial tiles (`part` doubles: the
+// plan's slots x accumulators x q x q), the covariance blocks (q x q per batch) and, with gradients, their derivatives (x D)
+struct BatchWorkspace : Workspace<BatchWorkspace> {
+  DevBuf<double> part, cov, dcov;
+  double for_part = 0.0;
+  int for_q = 0, for_d = 0;
+  bool has_grad = false;
+  template <class F>
+  bool each(double nb, double npart, int q, int D, bool grad, F&& f) {
+    return f(part, npart) && f(cov, nb * q * q) && (!grad || f(dcov, nb * q * q * D));
+  }
+  int64_t held(double npart, int q, int D, bool grad) const {
+    return for_part < npart || for_q < q || for_d < D || (grad && !has_grad) ? 0 : rows;
+  }
+  void sized_for(double npart, int q, int D, bool grad) { for_part = npart, for_q = q, for_d = D, has_grad = grad; }
 };
 
 // The sparse (FITC) path (fitc.hpp).  Two m x tile blocks with the tile's columns fastest (what the cross-covariance
@@ -296,6 +314,14 @@ template <class E, class V>
 bool design_buffers(E& e, const DesignPlan& pl, double nres, bool gemm_form, V& v) {
   return predict_buffers(e, (double)pl.mt, v) && (!gemm_form || v.rows(e.pw2, (double)pl.mt, e.Np)) &&
          v.rows(e.dz, (double)pl.Mc, e.Np, pl.ld, pl.nchunk, (int64_t)nres, (int)e.D);
+}
+
+// gmb_predict_batches: a prediction's buffers for the plan's largest tile, the feature's own workspace for `nacc` accumulators per
+// (chunk, batch) and, with gradients, gmb_predict_grad's workspace for the same tile (`pg_part`: doubles of its partials)
+template <class E, class V>
+bool batch_buffers(E& e, const BatchPlan& pl, int nacc, bool grad, double pg_part, V& v) {
+  return predict_buffers(e, (double)pl.mt, v) && v.rows(e.bw, pl.cov_doubles() / (pl.q * pl.q), pl.part_doubles(nacc), (int)pl.q, (int)e.D, grad) &&
+         (!grad || (v.rows(e.pg, (double)pl.mt, (int)e.D) && v.buf(e.pg_part, pg_part)));
 }
 
 }  // namespace gmb

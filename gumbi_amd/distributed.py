@@ -402,6 +402,10 @@ class DistributedEngine:
         raise NotImplementedError("predict_with_grad: the posterior's gradients are not built for distributed GPs "
                                   "(gmb_predict_with_grad needs the complete factor of a single-engine factorisation)")
 
+    def predict_batches(self, Xs, q, jitter=1e-6, grad=True):
+        raise NotImplementedError("predict_batches: the joint posteriors of batches and their derivatives are not built for "
+                                  "distributed GPs (gmb_predict_batches needs the complete factor of a single-engine factorisation)")
+
     # -- introspection: the resident state is replicated, the single-engine accessors apply ------------
     def notpd_index(self):
         return self.eng.notpd_index()

@@ -373,6 +373,9 @@ _SIGNATURES = {
     "gmb_design_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "gmb_debug_design_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "gmb_predict_batches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    "gmb_debug_batch_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]),
     "gmb_fitc_set_inducing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     "gmb_fitc_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_fitc_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -433,7 +436,9 @@ def _preload_hip_runtime():
 #: with the host-only ``gmb_debug_group_tasks``, and the posterior of the slope, ``gmb_predict_slope`` / ``gmb_predict_slope_terms``
 #: with the host-only ``gmb_debug_slope_tile_rows``, and the batch design by integrated variance reduction, ``gmb_design_batch`` with
 #: the host-only ``gmb_debug_design_plan``, and the sparse path ``gmb_fitc_*``, and GP classification by the Laplace approximation,
-#: ``gmb_laplace_*`` with the status ``GMB_ENOCONV``, the struct ``gmb_laplace_stats`` and the host-only ``gmb_debug_laplace_plan``)
+#: ``gmb_laplace_*`` with the status ``GMB_ENOCONV``, the struct ``gmb_laplace_stats`` and the host-only ``gmb_debug_laplace_plan``,
+#: and the joint posteriors of many small batches with their derivatives, ``gmb_predict_batches`` with the host-only
+#: ``gmb_debug_batch_plan``)
 ABI_VERSION = 16
 
 #: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
@@ -892,6 +897,31 @@ class Engine:
                                                     _ptr(dmean), _ptr(dvar), self.D, GMB_HOST), "gmb_predict_with_grad")
         return mean, var, dmean, dvar
 
+    def predict_batches(self, Xs, q, jitter=1e-6, grad=True):
+        """The joint LATENT posterior of every batch of ``q`` consecutive rows of ``Xs`` (``(B q, D)`` or ``(B, q, D)``,
+        ``1 <= q <= 16``) and its derivative with respect to the batch's own coordinates (``gmb_predict_batches``):
+        ``(mean (B, q), cov (B, q, q), dmean (B, q, D), dcov (B, q, q, D))``, or the first two with ``grad=False`` (the same
+        bits; the second triangular pass is skipped).  ``cov[b] = K(P_b, P_b) - V_b V_b^T + jitter I``, exactly symmetric;
+        ``dcov[b, j, l] = d cov[b, j, l] / d x_j``, for ``l = j`` the full derivative of the variance, i.e.
+        :meth:`predict_with_grad`'s ``dvar``; ``dmean`` is :meth:`predict_grad`'s.  One engine call per evaluation of a
+        Monte-Carlo batch acquisition for ``B`` restarts.  Leaves the factor and everything a fit left beside it untouched."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        q = int(q)
+        if Xs.ndim == 3 and Xs.shape[1] == q:
+            Xs = Xs.reshape(-1, Xs.shape[2])
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"predict_batches: Xs must be (B q, {self.D}) or (B, q, {self.D}), got {Xs.shape}")
+        if q < 1 or Xs.shape[0] % q:
+            raise ValueError(f"predict_batches: {Xs.shape[0]} points are no whole number of batches of q = {q}")
+        B, D = Xs.shape[0] // q, self.D
+        mean, cov = np.empty((B, q), dtype=np.float64), np.empty((B, q, q), dtype=np.float64)
+        dmean = np.empty((B, q, D), dtype=np.float64) if grad else None
+        dcov = np.empty((B, q, q, D), dtype=np.float64) if grad else None
+        self._check(self._lib.gmb_predict_batches(self._h, _ptr(Xs), B, q, D, float(jitter), _ptr(mean), _ptr(cov),
+                                                  _ptr(dmean) if grad else None, D, _ptr(dcov) if grad else None, GMB_HOST),
+                    "gmb_predict_batches")
+        return (mean, cov, dmean, dcov) if grad else (mean, cov)
+
     # -- sparse GPs: FITC on inducing points (csrc/fitc.hpp) ---------------------------------------------------------
     def set_inducing(self, Z):
         """The inducing points of the sparse approximation (``gmb_fitc_set_inducing``): ``Z`` is ``(m, D)``, columns as ``X``.
@@ -1264,6 +1294,24 @@ def design_plan(Np: int, M: int, R: int) -> dict:
     h, nt = len(keys), int(buf[4])
     plan["tiles"] = [tuple(int(v) for v in buf[h + 4 * t:h + 4 * t + 4]) for t in range(nt)]
     plan["chunks"] = [tuple(int(v) for v in buf[h + 4 * nt + 2 * c:h + 4 * nt + 2 * c + 2]) for c in range(plan["nchunk"])]
+    return plan
+
+
+def batch_plan(N: int, Np: int, B: int, q: int) -> dict:
+    """The plan of ``gmb_predict_batches`` for ``B`` batches of ``q`` points behind ``N`` training points padded to ``Np``
+    (host-only): ``bt`` batches per full M-tile, ``ntile``, ``mt`` rows of the prediction workspace, the ``slots`` the partials are
+    sized for, the ``unit`` of a chunk's length, and the tiles ``(first batch, batches, points, padded points, chunk length,
+    chunks)``.  ``ValueError`` for a request the call refuses."""
+    lib = load_library()
+    n = int(lib.gmb_debug_batch_plan(int(N), int(Np), int(B), int(q), None, 0))
+    if n < 0:
+        raise ValueError(f"gmb_debug_batch_plan: N = {N}, Np = {Np}, B = {B}, q = {q} is refused (code {-n})")
+    buf = np.empty(n, dtype=np.int64)
+    lib.gmb_debug_batch_plan(int(N), int(Np), int(B), int(q), _ptr(buf), n)
+    keys = ("bt", "ntile", "mt", "slots", "unit")
+    plan = {k: int(v) for k, v in zip(keys, buf)}
+    h = len(keys)
+    plan["tiles"] = [tuple(int(v) for v in buf[h + 6 * t:h + 6 * t + 6]) for t in range(plan["ntile"])]
     return plan
 
 

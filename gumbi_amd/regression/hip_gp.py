@@ -702,7 +702,7 @@ class HipGP(Regressor):
             return P
 
         kwargs = {}
-        if acquisition == "EI":  # the incumbent: the best observed standardized value of this output
+        if acquisition in ("EI", "qEI"):  # the incumbent: the best observed standardized value of this output
             y = np.asarray(self.model.y, float)
             if self.out_col in self.categorical_dims:
                 oc = self.dims.index(self.out_col)
@@ -862,6 +862,110 @@ class HipGP(Regressor):
         self.proposal_result = res
         self.proposal_raw_acquisition = raw_value
         return cand[best], float(value[best])
+
+    # -- joint batch proposals: Monte-Carlo q-EI on per-batch joint posteriors -----------------------------------------------------
+    def batch_acquisition_with_grad(self, batches_z, output=None, acquisition="qEI", maximize=True, categorical_levels=None,
+                                    mc_samples=256, seed=None, jitter=1e-6, _problem=None, _base=None):
+        """Batch acquisition value (B,) and its gradient (B, q, n_cont) with respect to the STANDARDIZED continuous coordinates
+        ``batches_z`` (B, q, n_cont, in ``continuous_dims`` order) of B batches of q points, on the noise-free joint posterior of
+        each batch: ONE ``engine.predict_batches`` call, chained with the acquisition's adjoints in (mean, cov)
+
+            grad_j = mean_bar_j dmean_j + cov_bar_jj dcov[j, j] + 2 sum_{l != j} cov_bar_jl dcov[j, l]
+
+        ``"qEI"`` is the log of the Monte-Carlo expected improvement of the batch as a whole on ``mc_samples`` fixed base samples
+        (:func:`gumbi_amd.acquisition.batch_expected_improvement`; scrambled Sobol points under ``seed``); larger is better for
+        both settings of ``maximize``.  This is the objective :meth:`propose_batch` optimises -- the analogue of
+        :meth:`acquisition_with_grad`."""
+        from .. import acquisition as acq
+
+        f, cont, cols, full = _problem or self._acquisition_problem(output, acquisition, maximize, categorical_levels, None)
+        Z = np.asarray(batches_z, float)
+        if Z.ndim != 3 or Z.shape[2] != len(cont):
+            raise ValueError(f"batches_z must be (B, q, {len(cont)}), got {Z.shape}")
+        B, q, nc = Z.shape
+        base = acq.sobol_normals(mc_samples, q, seed=self.seed if seed is None else seed) if _base is None else _base
+        mean, cov, dmean, dcov = self.engine.predict_batches(full(Z.reshape(B * q, nc)), q, jitter=jitter, grad=True)
+        value, mean_bar, cov_bar = f(mean, cov, base, maximize)
+        weight = 2.0 * cov_bar
+        idx = np.arange(q)
+        weight[:, idx, idx] = cov_bar[:, idx, idx]
+        grad = mean_bar[:, :, None] * dmean[:, :, cols] + np.einsum("bjl,bjld->bjd", weight, dcov[:, :, :, cols])
+        return value, grad
+
+    def propose_batch(self, q, output=None, acquisition="qEI", maximize=True, bounds=None, categorical_levels=None, num_restarts=10,
+                      raw_samples=512, mc_samples=256, seed=None, **optim_kwargs):
+        """A batch of ``q`` points to measure next, optimised AS A WHOLE against the correlation between its own points (the
+        reference's ``BotorchGP.propose(q=.., mc_samples=256, sequential=False)``, botorch/GP.py:652): multi-start L-BFGS-B on the
+        Monte-Carlo log q-EI of the batch's joint noise-free posterior, in standardized units.  The greedy batch of
+        :meth:`propose_continuous` (``sequential=True``) conditions on one pick at a time; this one moves all q points together.
+
+        ``raw_samples`` seeded uniform batches inside ``bounds`` are scored in ONE values-only ``engine.predict_batches`` call and
+        the best ``num_restarts`` become the starts; the restarts are optimised in lock step -- one ``scipy.optimize.minimize``
+        over their ``num_restarts x q x n_cont`` coordinates with the summed negative acquisition -- and every objective
+        evaluation is ONE ``engine.predict_batches`` call at ``B = num_restarts`` (:meth:`batch_acquisition_with_grad`) against
+        the factor :meth:`find_MAP` left resident.  The ``mc_samples`` base samples are drawn once (scrambled Sobol under the
+        seed) and stay fixed, so the objective is deterministic.
+
+        Bounds, the incumbent and the choice of ``output`` follow :meth:`propose_continuous`.  Returns the best batch -- of the
+        optimised restarts and their starts -- as a parray of ``q`` points in natural units and sets :attr:`proposal`,
+        :attr:`proposal_acquisition` (its acquisition value), :attr:`optimization_bounds`, :attr:`proposal_result` and
+        :attr:`proposal_raw_acquisition` (the raw batches' scores).  Remaining ``optim_kwargs`` go to L-BFGS-B's ``options``.
+        ``1 <= q <= 16``.  Not for the Kronecker path (pass ``kronecker=False``) or distributed GPs."""
+        from scipy.optimize import minimize
+
+        from .. import acquisition as acq
+
+        q = int(q)
+        if q < 1 or q > 16:
+            raise ValueError(f"propose_batch: q must be 1 .. 16, got {q}")
+        if acquisition != "qEI":
+            raise ValueError(f'propose_batch: acquisition must be "qEI", got {acquisition!r}')
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError("propose_batch: the joint posteriors of batches are not built for the Kronecker engine "
+                                      "(pass kronecker=False)")
+        problem = self._acquisition_problem(output, acquisition, maximize, categorical_levels, None)
+        f, cont, cols, full = problem
+        nc = len(cont)
+        num_restarts, raw_samples = int(num_restarts), max(int(raw_samples), int(num_restarts))
+
+        # standardized bounds, one entry per continuous dim (as propose_continuous)
+        if bounds is None:
+            Xc = np.asarray(self.model.X, float)[:, cols]
+            lo, hi = Xc.min(axis=0), Xc.max(axis=0)
+        else:
+            bz = bounds.z
+            both = np.array([np.asarray(bz[d + "_z"].values(), float).ravel() for d in cont])
+            if both.shape != (nc, 2):
+                raise ValueError("bounds must hold two entries (lower, upper) per continuous dimension")
+            lo, hi = both.min(axis=1), both.max(axis=1)
+        self.optimization_bounds = (lo.copy(), hi.copy())
+
+        rng = np.random.default_rng(self.seed if seed is None else seed)
+        options = {"maxiter": 200, **optim_kwargs.pop("options", {}), **optim_kwargs}
+        base = acq.sobol_normals(mc_samples, q, seed=int(rng.integers(2**31 - 1)))
+
+        def score(batches):  # values only: (B, q, nc) -> (B,)
+            mean, cov = self.engine.predict_batches(full(batches.reshape(-1, nc)), q, grad=False)
+            return f(mean, cov, base, maximize)[0]
+
+        raw = lo + (hi - lo) * rng.random((raw_samples, q, nc))
+        raw_value = score(raw)
+        starts = raw[np.argsort(-raw_value, kind="stable")[:num_restarts]]
+
+        def objective(z):
+            value, grad = self.batch_acquisition_with_grad(z.reshape(num_restarts, q, nc), maximize=maximize, _problem=problem, _base=base)
+            return -float(np.sum(value)), -grad.ravel()
+
+        res = minimize(objective, starts.ravel(), jac=True, method="L-BFGS-B",
+                       bounds=list(zip(np.tile(lo, num_restarts * q), np.tile(hi, num_restarts * q))), options=options)
+        cand = np.clip(np.concatenate([res.x.reshape(num_restarts, q, nc), starts]), lo, hi)
+        value = score(cand)
+        best = int(np.argmax(value))
+        self.proposal_result = res
+        self.proposal_raw_acquisition = raw_value
+        self.proposal_acquisition = float(value[best])
+        self.proposal = self.parray(**{d: cand[best][:, k] for k, d in enumerate(cont)}, stdzd=True)
+        return self.proposal
 
     def _shaped_rows(self):
         """:meth:`get_shaped_data` for a table of ANY number of rows: ``(K, D)`` and ``(K,)`` -- the base method squeezes a

@@ -277,6 +277,10 @@ class IcmEngine:
         raise NotImplementedError("design_batch: the rectangular posterior covariance of the candidates and the reference points is "
                                   "built on the single-device engine only, not for the Kronecker engine (pass kronecker=False)")
 
+    def predict_batches(self, Xs, q, jitter=1e-6, grad=True):
+        raise NotImplementedError("predict_batches: the joint posteriors of batches and their derivatives are not built for the "
+                                  "Kronecker engine (pass kronecker=False)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

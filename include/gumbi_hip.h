@@ -532,6 +532,33 @@ int gmb_design_batch(gmb_engine* e, const double* Xc, int64_t M, int64_t ldc, co
  * one M-tile, 5 R > 2^30. */
 int64_t gmb_debug_design_plan(int64_t Np, int64_t M, int64_t R, int64_t* out, int64_t cap);
 
+/* ---- joint posteriors of many small batches, with derivatives (ABI stays 16: new functions only, no change of layout) ----------------
+ * What a reparameterised Monte-Carlo batch acquisition (q-EI; the reference's `propose(q=..)`, gumbi/regression/botorch/GP.py:652)
+ * needs for R restarts at once (csrc/predict_batches.hpp).  Xs: (B q) x D row-major, leading dimension ldxs >= D, in `memspace`;
+ * batch b is rows [b q, (b + 1) q), 1 <= q <= 16.  Everything is the LATENT posterior (no noise) against the resident factor:
+ *   mean   B q values
+ *   cov    B x q x q contiguous: C_b = K(P_b, P_b) - V_b V_b^T + jitter I, both triangles written, exactly symmetric
+ *   dmean  (B q) x D with leading dimension ldg >= D: gmb_predict_grad's quantity
+ *   dcov   B x q x q x D contiguous: dcov[b, j, l, :] = d C_b[j, l] / d x_j; for l = j the FULL derivative of C_b[j, j], which is
+ *          gmb_predict_with_grad's dvar at that point.  With w_l = Sigma^-1 k(X, x_l), per term and summed over the terms,
+ *            d C[j, l] / d x_j = d_1 k(x_j, x_l) - sum_n W_ln d k(x_j, x_n) / d x_j                 (l != j)
+ *            d C[j, j] / d x_j = d k(x_j, x_j) / d x_j - 2 sum_n W_jn d k(x_j, x_n) / d x_j
+ *          (the same f' and sqrt(r^2 + 1e-12) as gmb_predict_grad: two coincident points of a batch give a Matern-1/2 derivative 0)
+ * Categorical and output columns of dmean and dcov are 0.  dmean and dcov may BOTH be NULL: only the values are computed, and
+ * W = V L^-1 is not formed (the same mean and cov bits).  Per M-tile the flow is gmb_predict_with_grad's; tiles are cut at whole
+ * batches.  The contractions over the training points run on v_mfma_f64_16x16x4_f64, one wave per (batch, chunk of N), partials
+ * summed in chunk order: no atomics, the same bits call after call.  Readiness, refusals and the state contract are
+ * gmb_predict_with_grad's; GMB_EINVAL also for q outside 1 .. 16, B < 0, a NULL mean or cov, dmean without dcov or the reverse;
+ * B == 0 is GMB_OK; a request the device cannot hold returns GMB_ENOMEM.  A refusal launches nothing and writes nothing. */
+int gmb_predict_batches(gmb_engine* e, const double* Xs, int64_t B, int32_t q, int64_t ldxs, double jitter, double* mean, double* cov,
+                        double* dmean, int64_t ldg, double* dcov, int32_t memspace);
+/* Host only: the plan of gmb_predict_batches behind N training points padded to Np.  Writes at most `cap` values to `out` (may be
+ * NULL) and returns how many there are: bt (batches of a full M-tile), ntile, mt (rows of the prediction workspace), slots
+ * ((chunk, batch) pairs the partials are sized for), the unit of a chunk's length; then per tile (first batch, batches, points,
+ * padded points, chunk length, chunks).  A refusal returns -(code): 1 q outside 1 .. 16, 2 B < 1, 3 N < 1 or Np no multiple of
+ * 128 that holds N, 4 B q > 2^40. */
+int64_t gmb_debug_batch_plan(int64_t N, int64_t Np, int64_t B, int32_t q, int64_t* out, int64_t cap);
+
 /* ---- sparse GPs: the FITC approximation on m inducing points (ABI stays 16: new functions only, no change of layout) -----------------
  * PyMC's MarginalSparse(approx="FITC") (gumbi/regression/pymc/GP.py:571-591, fit(sparse=True, n_u=...)), csrc/fitc.hpp.  With Z the
  * m inducing points and k the model's covariance without noise:
