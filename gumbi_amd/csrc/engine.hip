@@ -52,6 +52,7 @@
 #include "group_average.hpp"
 #include "predict_slope.hpp"
 #include "design_batch.hpp"
+#include "pathwise.hpp"
 #include "predict_batches.hpp"
 #include "fitc.hpp"
 #include "laplace.hpp"
@@ -100,11 +101,15 @@ enum EvKind : int {
                               // prediction's reduction
   EV_BATCH = 23,              // gmb_predict_batches: the contraction launches of one M-tile (mt = batches, nt = chunks, k = q; flags = 0
                               // the partial + finishing launches of Q = V V^T, 1 those of one term's derivative sums)
+  EV_PATHS = 24,              // the pathwise draws' own launches (mt = point tiles or point blocks, nt = chunks, k = draws; flags = 0 the
+                              // all-draws kernel + its finish over the features at the training points (prepare), 1 the all-draws
+                              // kernel + its finish of one M-tile (eval), 2 the own-draw kernel + its finish; the residual and A's
+                              // transposed store of a preparation are in no event)
   EV_LAPLACE = 22             // gmb_laplace_evaluate: a PHASE, around the launches listed above (mt = block rows, k = Newton iteration;
                               // flags = 0 the build of Sigma, 1 a build of B or Z', 2 a Cholesky with its two vector solves, 3 a symmetric
                               // matrix-vector product, 4 elementwise and likelihood work, 5 the inverse, 6 the trace pass)
 };
-inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_BATCH); }
+inline bool ev_trace_only(EvKind k) { return k == EV_PREDICT_COV || (k >= EV_PREDICT_GRAD && k <= EV_PATHS); }
 
 struct EventPair {
   hipEvent_t a, b;
@@ -211,6 +216,7 @@ struct gmb_engine {
   SlopeWorkspace slope;     // gmb_predict_slope (predict_slope.hpp), beside a prediction's workspace of Dc stacked blocks
   DevBuf<int64_t> ga_idx;   // the task triples, then first_task (G + 1), then offsets (G + 1)
   BatchWorkspace bw;        // gmb_predict_batches (predict_batches.hpp), beside a prediction's and gmb_predict_grad's workspaces
+  PathState paths;          // gmb_paths_* (pathwise.hpp): A = Sigma^-1 R of the prepared draws, tied to the factor's epoch
   DesignWorkspace dz;       // gmb_design_batch (design_batch.hpp), beside a prediction's workspace of one point tile
   FitcState fitc;           // the sparse (FITC) path: everything it keeps (workspaces.hpp), nothing of it shared with the exact path
   LaplaceState lap;         // GP classification (laplace.hpp): Sigma and the vectors; B's factor sits in the factor buffer, FactorState "not factored"
@@ -535,6 +541,7 @@ void ev_collect(gmb_engine* e) {  // stream already synchronised
       case EV_DESIGN:
       case EV_FITC:
       case EV_LAPLACE:
+      case EV_PATHS:
       case EV_BATCH: break;
     }
     (void)hipEventDestroy(p.a);
@@ -5750,6 +5757,274 @@ int gmb_predict_batches(gmb_engine* e, const double* Xs, int64_t B, int32_t q, i
 }
 
 int64_t gmb_debug_batch_plan(int64_t N, int64_t Np, int64_t B, int32_t q, int64_t* out, int64_t cap) { return batch_plan_dump(N, Np, B, q, out, cap); }
+
+// ---- pathwise posterior draws (pathwise.hpp, paths_plan.hpp) ------------------------------------------------------------------------
+
+namespace {
+
+// the all-draws kernel over one tile of prepared points (txs: stride tpad) into paths.out ([draw of Sp][point of tl.mpad]); with
+// `train` the contraction runs over the training points and the features (pl.N = e->N), without over the features alone (pl.N = 0)
+int paths_eval_tile(gmb_engine* e, const PathsPlan& pl, const PathsTile& tl, const double* txs, int64_t tpad, bool train) {
+  PathState& st = e->paths;
+  const gmb_engine::Term& tr = e->terms[0];
+  PathsEvalArgs a{};
+  a.txs = txs;
+  a.tpad = tpad;
+  a.mc = tl.mc;
+  a.xs = e->pts.xs;
+  a.npad = e->Nr;
+  a.N = train ? e->N : 0;
+  a.A = st.A;
+  a.wt = st.wt;
+  a.omega = st.omega;
+  a.phase = st.phase;
+  a.F = pl.F;
+  a.F4 = pl.F4;
+  a.N4 = pl.N4;
+  a.Sp = pl.Sp;
+  a.eta2 = tr.cp.eta2;
+  a.chunk = tl.chunk;
+  a.part = tl.nchunk > 1 ? (double*)st.part : (double*)st.out;  // one chunk: its partials ARE the results
+  a.mpad = tl.mpad;
+  const dim3 grid((unsigned)tl.pt, (unsigned)pl.ndb, (unsigned)tl.nchunk);
+  ev_begin(e, e->stream, EV_PATHS, 2.0 * (double)tl.mc * (double)(a.N + pl.F) * pl.Sp, (int)tl.pt, (int)tl.nchunk, pl.S, train ? 1 : 0);
+  const bool known = with_kind_nc(tr.cp.kind, e->nc_pad, [&](auto kind, auto nc) {
+    hipLaunchKernelGGL((paths_eval_kernel<decltype(kind)::value, decltype(nc)::value>), grid, dim3(64), 0, e->stream, a);
+  });
+  if (known && tl.nchunk > 1)
+    hipLaunchKernelGGL(paths_eval_finish_kernel, dim3((unsigned)(((int64_t)pl.S * tl.mpad + 255) / 256)), dim3(256), 0, e->stream,
+                       (const double*)st.part, (int32_t)tl.nchunk, pl.Sp, pl.S, tl.mpad, (double*)st.out);
+  ev_end(e);
+  if (!known) return fail(e, GMB_EINVAL, "unknown kernel kind %d", tr.cp.kind);
+  HIP_TRY(e, hipGetLastError());
+  return GMB_OK;
+}
+
+// what the two evaluation calls ask: a prepared state of the factor's current epoch
+int paths_ready(gmb_engine* e, const char* what) {
+  if (!e) return GMB_EINVAL;
+  if (!e->paths.ready) return fail(e, GMB_EINVAL, "%s: no paths are prepared: call gmb_paths_prepare first", what);
+  if (e->paths.epoch != e->fs.epoch() || !e->have_theta || e->terms.empty())
+    return fail(e, GMB_EINVAL, "%s: the prepared paths are stale (the data, theta or the factor changed since gmb_paths_prepare): prepare them again", what);
+  return GMB_OK;
+}
+
+// the plan's bytes against the device, then the allocation (`buffers`: the call's list over a visitor)
+extern "C++" template <typename Buffers>
+int paths_reserve(gmb_engine* e, const char* what, Buffers&& buffers) {
+  int rc;
+  Budget need;
+  buffers(need);
+  double free_b;
+  if ((rc = device_free_bytes(e, &free_b))) return rc;
+  if (need.fresh > free_b)
+    return fail(e, GMB_ENOMEM, "%s needs %.0f bytes on the device, %.0f more than it holds for the engine now; %.0f bytes are free -- nothing was computed",
+                what, need.total, need.fresh, free_b);
+  Reserver take{e->pool};
+  buffers(take);
+  return take.rc;
+}
+
+}  // namespace
+
+int gmb_paths_prepare(gmb_engine* e, int32_t S, int32_t F, const double* omega, const double* phase, const double* w, const double* eps) {
+  const char* what = "gmb_paths_prepare";
+  if (!e) return GMB_EINVAL;
+  if (e->solve_hook || e->dist_mode != 0)  // (said before readiness: switching the mode has already dropped the factor)
+    return fail(e, GMB_EINVAL, "%s is not available on distributed engines (gmb_dist_*, capacity mode): factorise with gmb_factorize on one device", what);
+  int rc = joint_ready(e, what);
+  if (rc) return rc;
+  const gmb_kernel_spec& sp = e->spec;
+  if (sp.additive || e->terms.size() != 1)
+    return fail(e, GMB_EINVAL, "%s: additive models are not supported (one stationary term over the continuous dimensions only)", what);
+  if (e->periodic) return fail(e, GMB_EINVAL, "%s: periodic models are not supported (their prior features are warped inputs)", what);
+  if (sp.n_lin > 0) return fail(e, GMB_EINVAL, "%s: linear dimensions are not supported (their prior features are finite linear features)", what);
+  if (spec_ntab(sp) > 0)
+    return fail(e, GMB_EINVAL, "%s: coregion tables (categorical dimensions or an output column) are not supported", what);
+  if (S < 1 || S > PATHS_MAX_S) return fail(e, GMB_EINVAL, "%s: S = %d draws (1 <= S <= %d is required)", what, (int)S, PATHS_MAX_S);
+  if (F < 1 || F > PATHS_MAX_F) return fail(e, GMB_EINVAL, "%s: F = %d features (1 <= F <= %d is required)", what, (int)F, PATHS_MAX_F);
+  if (!omega || !phase || !w || !eps) return fail(e, GMB_EINVAL, "%s: omega, phase, w and eps must not be NULL", what);
+  HIP_TRY(e, hipSetDevice(e->device));
+  PathState& st = e->paths;
+  const gmb_engine::Term& tr = e->terms[0];
+  PathsPlan pl;  // the features alone, at the training points
+  if (pl.make(0, F, e->N, S)) return fail(e, GMB_EINVAL, "%s: S = %d, F = %d behind N = %lld is more than a call takes", what, (int)S, (int)F, (long long)e->N);
+  const int64_t mrow = round_up(S, TILE);  // the draws as the test index of a prediction's V
+  if ((rc = paths_reserve(e, what, [&](auto& v) { paths_prepare_buffers(*e, st, pl, (double)mrow, v); }))) return rc;
+  st.clear();  // from here on the previous draws are gone
+  // the host's part: frequencies by prepared column, phases, weights scaled by eta sqrt(2 / F) and laid draw-fastest
+  const int nc = tr.pa.nc, ncp = e->nc_pad;
+  std::vector<double> hom((size_t)ncp * pl.F4, 0.0), hph((size_t)pl.F4, 0.0), hwt((size_t)pl.F4 * pl.Sp, 0.0);
+  const double scale = tr.eta * std::sqrt(2.0 / (double)F);
+  for (int64_t f = 0; f < F; ++f) {
+    for (int k = 0; k < nc; ++k) hom[(size_t)k * pl.F4 + f] = omega[f * nc + k];
+    hph[f] = phase[f];
+    for (int s = 0; s < S; ++s) hwt[(size_t)f * pl.Sp + s] = scale * w[(int64_t)s * F + f];
+  }
+  HIP_TRY(e, hipMemcpyAsync(st.omega, hom.data(), hom.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(st.phase, hph.data(), hph.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(st.wt, hwt.data(), hwt.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(st.eps, eps, (size_t)S * e->N * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  reset_predict_timings(e);
+  e->tm.predict_gemm_form = 0;  // the right-hand sides are solved for, as in gmb_predict_with_grad: neither dW nor U is touched
+  const double d = std::sqrt(tr.cp.sigma2 + tr.cp.jitter);  // exactly the diagonal the covariance build adds to K
+  PhaseTimer tp(e);
+  auto work = [&]() -> int {
+    for (int64_t t = 0; t < pl.ntile; ++t) {  // R = y - Phi(X) w~ - d eps, draw index fastest, into the prediction's V
+      const PathsTile tl = pl.tile(t);
+      if ((rc = paths_eval_tile(e, pl, tl, e->pts.xs + tl.first, e->Nr, false))) return rc;
+      hipLaunchKernelGGL(paths_resid_kernel, dim3((unsigned)((mrow * tl.mc + 255) / 256)), dim3(256), 0, e->stream, (const double*)st.out, tl.mpad,
+                         (const double*)e->dy, (const double*)st.eps, e->N, S, d, tl.first, tl.mc, (double*)e->pw.dV, mrow);
+    }
+    if (e->Np > e->N) HIP_TRY(e, hipMemsetAsync(e->pw.dV + e->N * mrow, 0, (size_t)((e->Np - e->N) * mrow) * sizeof(double), e->stream));
+    HIP_TRY(e, hipGetLastError());
+    if ((rc = predict_solve_v(e, mrow, false))) return rc;  // R L^-T ...
+    if ((rc = predict_solve_w(e, mrow))) return rc;         // ... L^-1 = (Sigma^-1 R)^T
+    hipLaunchKernelGGL(paths_store_a_kernel, dim3((unsigned)((e->Np * pl.Sp + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->pw.dV, mrow,
+                       e->N, e->Np, S, pl.Sp, (double*)st.A);
+    HIP_TRY(e, hipGetLastError());
+    return GMB_OK;
+  };
+  rc = predict_end(e, &tp, work());  // (drains the stream: the host vectors above and the caller's eps have been read)
+  if (rc) return rc;
+  st.ready = true;
+  st.epoch = e->fs.epoch();
+  st.S = S, st.Sp = pl.Sp, st.F = F, st.F4 = pl.F4;
+  return GMB_OK;
+}
+
+int gmb_paths_eval(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* Y, int64_t ldy, int32_t memspace) {
+  const char* what = "gmb_paths_eval";
+  int rc = paths_ready(e, what);
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !Y)) || ldxs < e->D || ldy < M)
+    return fail(e, GMB_EINVAL, "%s: bad M/Xs/ldxs/Y/ldy (M >= 0, ldxs >= D, ldy >= M, no NULL array)", what);
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  PathState& st = e->paths;
+  PathsPlan pl;
+  if (pl.make(e->N, st.F, M, st.S)) return fail(e, GMB_EINVAL, "%s: M = %lld points are more than a call takes (M <= 2^40)", what, (long long)M);
+  if ((rc = paths_reserve(e, what, [&](auto& v) { paths_eval_buffers(*e, st, pl, v); }))) return rc;
+  reset_predict_timings(e);
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t t = 0; t < pl.ntile; ++t) {
+      const PathsTile tl = pl.tile(t);
+      HIP_TRY(e, hipMemcpy2DAsync(e->pg.Xs, row, Xs + tl.first * ldxs, ldxs * sizeof(double), row, tl.mc, ck.in, e->stream));
+      if ((rc = prep_points(e, e->pg.Xs, tl.mc, e->D, tl.mpad, e->pg.xs, e->pg.xl, e->pg.cat, &e->terms[0].pa))) return rc;
+      if ((rc = paths_eval_tile(e, pl, tl, e->pg.xs, tl.mpad, true))) return rc;
+      if (hipMemcpy2DAsync(Y + tl.first, ldy * sizeof(double), st.out, tl.mpad * sizeof(double), tl.mc * sizeof(double), st.S, ck.out, e->stream) != hipSuccess)
+        return fail(e, GMB_EHIP, "%s: copying the draws out failed", what);
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
+int gmb_paths_eval_own(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, const int32_t* draw, double* val, double* grad, int64_t ldg,
+                       int32_t memspace) {
+  const char* what = "gmb_paths_eval_own";
+  int rc = paths_ready(e, what);
+  if (rc) return rc;
+  if (M < 0 || (M > 0 && (!Xs || !draw || !val)) || ldxs < e->D || (grad && ldg < e->D))
+    return fail(e, GMB_EINVAL, "%s: bad M/Xs/ldxs/draw/val/ldg (M >= 0, ldxs >= D, ldg >= D, no NULL array but grad)", what);
+  if (M == 0) return GMB_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  PathState& st = e->paths;
+  {  // every point's draw exists: looked at on the host before anything is launched
+    std::vector<int32_t> staged;
+    const int32_t* hd = draw;
+    if (memspace == GMB_DEVICE) {
+      staged.resize((size_t)M);
+      HIP_TRY(e, hipMemcpy(staged.data(), draw, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost));
+      hd = staged.data();
+    }
+    for (int64_t m = 0; m < M; ++m)
+      if (hd[m] < 0 || hd[m] >= st.S)
+        return fail(e, GMB_EINVAL, "%s: draw[%lld] = %d is outside [0, %d)", what, (long long)m, (int)hd[m], (int)st.S);
+  }
+  PathsPlan pl;
+  if (pl.make(e->N, st.F, M, st.S)) return fail(e, GMB_EINVAL, "%s: M = %lld points are more than a call takes (M <= 2^40)", what, (long long)M);
+  if ((rc = paths_reserve(e, what, [&](auto& v) { paths_own_buffers(*e, st, pl, v); }))) return rc;
+  reset_predict_timings(e);
+  const CopyKinds ck = copy_kinds(memspace);
+  const size_t row = e->D * sizeof(double);
+  const gmb_engine::Term& tr = e->terms[0];
+  PhaseTimer tp(e);
+  auto tiles = [&]() -> int {
+    for (int64_t t = 0; t < pl.ntile; ++t) {
+      const PathsTile tl = pl.tile(t);
+      HIP_TRY(e, hipMemcpy2DAsync(e->pg.Xs, row, Xs + tl.first * ldxs, ldxs * sizeof(double), row, tl.mc, ck.in, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(st.draw, draw + tl.first, (size_t)tl.mc * sizeof(int32_t), ck.in, e->stream));
+      if ((rc = prep_points(e, e->pg.Xs, tl.mc, e->D, tl.mpad, e->pg.xs, e->pg.xl, e->pg.cat, &tr.pa))) return rc;
+      if (grad) HIP_TRY(e, hipMemsetAsync(e->pg.grad, 0, (size_t)(tl.mc * e->D) * sizeof(double), e->stream));
+      PathsOwnArgs a{};
+      a.txs = e->pg.xs;
+      a.mpad = tl.mpad;
+      a.mc = tl.mc;
+      a.draw = st.draw;
+      a.xs = e->pts.xs;
+      a.npad = e->Nr;
+      a.N = e->N;
+      a.A = st.A;
+      a.wt = st.wt;
+      a.omega = st.omega;
+      a.phase = st.phase;
+      a.F = pl.F;
+      a.F4 = pl.F4;
+      a.N4 = pl.N4;
+      a.Sp = pl.Sp;
+      a.eta2 = tr.cp.eta2;
+      a.chunk = tl.own_chunk;
+      a.part = st.part;
+      const dim3 grid((unsigned)(tl.mpad / PATHS_OWN_PTS), (unsigned)tl.own_nchunk);
+      ev_begin(e, e->stream, EV_PATHS, 0.0, (int)(tl.mpad / PATHS_OWN_PTS), (int)tl.own_nchunk, st.S, 2);
+      const bool known = with_kind_nc(tr.cp.kind, e->nc_pad, [&](auto kind, auto nc) {
+        hipLaunchKernelGGL((paths_own_kernel<decltype(kind)::value, decltype(nc)::value>), grid, dim3(256), 0, e->stream, a);
+      });
+      if (!known) {
+        ev_end(e);
+        return fail(e, GMB_EINVAL, "unknown kernel kind %d", tr.cp.kind);
+      }
+      PathsOwnFinishArgs f{};
+      f.part = st.part;
+      f.nchunk = (int32_t)tl.own_nchunk;
+      f.nc = tr.pa.nc;
+      f.nc_pad = e->nc_pad;
+      f.D = e->D;
+      f.mpad = tl.mpad;
+      f.mc = tl.mc;
+      for (int k = 0; k < tr.pa.nc; ++k) f.idx_cont[k] = tr.pa.idx_cont[k], f.scale[k] = 2.0 * tr.pa.inv_ls[k];
+      f.val = st.val;
+      f.grad = grad ? (double*)e->pg.grad : nullptr;
+      hipLaunchKernelGGL(paths_own_finish_kernel, dim3((unsigned)((tl.mc + 255) / 256)), dim3(256), 0, e->stream, f);
+      ev_end(e);
+      HIP_TRY(e, hipGetLastError());
+      if (hipMemcpyAsync(val + tl.first, st.val, (size_t)tl.mc * sizeof(double), ck.out, e->stream) != hipSuccess ||
+          (grad && hipMemcpy2DAsync(grad + tl.first * ldg, ldg * sizeof(double), e->pg.grad, row, row, tl.mc, ck.out, e->stream) != hipSuccess))
+        return fail(e, GMB_EHIP, "%s: copying the results out failed", what);
+    }
+    return GMB_OK;
+  };
+  return predict_end(e, &tp, tiles());
+}
+
+int gmb_paths_clear(gmb_engine* e) {
+  if (!e) return GMB_EINVAL;
+  PathState& st = e->paths;
+  st.clear();
+  st.A.drop(e->pool), st.wt.drop(e->pool), st.omega.drop(e->pool), st.phase.drop(e->pool);
+  st.out.drop(e->pool), st.part.drop(e->pool), st.val.drop(e->pool), st.eps.drop(e->pool), st.draw.drop(e->pool);
+  return GMB_OK;
+}
+
+int32_t gmb_paths_count(gmb_engine* e) { return e && e->paths.ready ? e->paths.S : 0; }
+
+int64_t gmb_debug_paths_plan(int64_t N, int64_t F, int64_t M, int64_t S, int32_t nacc, int64_t* out, int64_t cap) {
+  return paths_plan_dump(N, F, M, S, nacc, out, cap);
+}
 
 int gmb_predict_joint(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, int32_t with_noise, double jitter,
                       double* mean, double* cov, int64_t ldc, int32_t memspace) {

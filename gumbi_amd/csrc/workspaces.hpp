@@ -4,7 +4,7 @@
 // for a row count and its other size arguments.  reserve() renews by walking that list, bytes() sums sizeof(T) * count over it and
 // a Budget measures with the two, so what a call is refused for and what it allocates cannot drift apart.  The counts are
 // doubles: a request that has to be refused may not fit in int64_t, and every count that IS allocated is an integer below 2^53.
-// One level up, predict_buffers / joint_buffers / group_buffers / design_buffers / batch_buffers list every buffer of a call once, over a visitor
+// One level up, predict_buffers / joint_buffers / group_buffers / design_buffers / batch_buffers / paths_*_buffers list every buffer of a call once, over a visitor
 // (a Budget, then a Reserver); they are templates over the engine, of which they use N, Np, D and the members named in them.
 //
 // No HIP and no engine types: tools/workspace_budget_check.cpp runs this very header over a host allocator.
@@ -14,6 +14,7 @@
 #include "device_buffers.hpp"
 #include "fitc_plan.hpp"
 #include "laplace_plan.hpp"
+#include "paths_plan.hpp"
 #include "slope_plan.hpp"  // SLOPE_MAX_COLS
 #include "workspace_sizes.hpp"
 
@@ -152,6 +153,21 @@ struct BatchWorkspace : Workspace<BatchWorkspace> {
     return for_part < npart || for_q < q || for_d < D || (grad && !has_grad) ? 0 : rows;
   }
   void sized_for(double npart, int q, int D, bool grad) { for_part = npart, for_q = q, for_d = D, has_grad = grad; }
+};
+
+// The pathwise posterior draws (pathwise.hpp): what gmb_paths_prepare leaves resident -- A = Sigma^-1 R and the scaled
+// feature weights, both draw-fastest ([index][Sp]), the frequencies by prepared column and the phases -- and the calls' own
+// buffers: the results of one M-tile ([draw][point]), the chunked partials, the own-draw values and draw indices, the staged
+// normals of a preparation.  `epoch` is FactorState's when the state was prepared: a state of another epoch is stale.
+struct PathState {
+  bool ready = false;
+  unsigned epoch = 0;
+  int32_t S = 0, Sp = 0;
+  int64_t F = 0, F4 = 0;
+  DevBuf<double> A, wt, omega, phase;
+  DevBuf<double> out, part, val, eps;
+  DevBuf<int32_t> draw;
+  void clear() { ready = false, S = Sp = 0, F = F4 = 0; }
 };
 
 // The sparse (FITC) path (fitc.hpp).  Two m x tile blocks with the tile's columns fastest (what the cross-covariance
@@ -322,6 +338,26 @@ template <class E, class V>
 bool batch_buffers(E& e, const BatchPlan& pl, int nacc, bool grad, double pg_part, V& v) {
   return predict_buffers(e, (double)pl.mt, v) && v.rows(e.bw, pl.cov_doubles() / (pl.q * pl.q), pl.part_doubles(nacc), (int)pl.q, (int)e.D, grad) &&
          (!grad || (v.rows(e.pg, (double)pl.mt, (int)e.D) && v.buf(e.pg_part, pg_part)));
+}
+
+// gmb_paths_prepare: a prediction's buffers for `mrow` rows (the draws as test index), the resident state, the staged normals
+// (S x N) and the feature pass over the training points (`pl`: the features-only plan at M = N)
+template <class E, class V>
+bool paths_prepare_buffers(E& e, PathState& st, const PathsPlan& pl, double mrow, V& v) {
+  return predict_buffers(e, mrow, v) && v.buf(st.A, (double)e.Np * pl.Sp) && v.buf(st.wt, (double)pl.F4 * pl.Sp) &&
+         v.buf(st.omega, (double)e.nc_pad * (double)pl.F4) && v.buf(st.phase, (double)pl.F4) && v.buf(st.eps, (double)pl.S * (double)e.N) &&
+         v.buf(st.out, pl.out_doubles()) && v.buf(st.part, pl.part_doubles());
+}
+// gmb_paths_eval: the points of the largest M-tile raw and prepared (gmb_predict_grad's workspace), its results and partials
+template <class E, class V>
+bool paths_eval_buffers(E& e, PathState& st, const PathsPlan& pl, V& v) {
+  return v.rows(e.pg, (double)pl.mt, (int)e.D) && v.buf(st.out, pl.out_doubles()) && v.buf(st.part, pl.part_doubles());
+}
+// gmb_paths_eval_own: the same points, the values, the draw indices and the partials of nc_pad + 1 accumulators
+template <class E, class V>
+bool paths_own_buffers(E& e, PathState& st, const PathsPlan& pl, V& v) {
+  return v.rows(e.pg, (double)pl.mt, (int)e.D) && v.buf(st.val, (double)pl.mt) && v.buf(st.draw, (double)pl.mt) &&
+         v.buf(st.part, pl.own_part_doubles(e.nc_pad + 1));
 }
 
 }  // namespace gmb

@@ -406,6 +406,18 @@ class DistributedEngine:
         raise NotImplementedError("predict_batches: the joint posteriors of batches and their derivatives are not built for "
                                   "distributed GPs (gmb_predict_batches needs the complete factor of a single-engine factorisation)")
 
+    def paths_prepare(self, omega, phase, w, eps):
+        raise NotImplementedError("paths_prepare: pathwise posterior draws are not built for distributed GPs (gmb_paths_prepare needs the complete factor of a single-engine factorisation)")
+
+    def paths_eval(self, Xs):
+        raise NotImplementedError("paths_eval: pathwise posterior draws are not built for distributed GPs (gmb_paths_prepare needs the complete factor of a single-engine factorisation)")
+
+    def paths_eval_own(self, Xs, draw, grad=True):
+        raise NotImplementedError("paths_eval_own: pathwise posterior draws are not built for distributed GPs (gmb_paths_prepare needs the complete factor of a single-engine factorisation)")
+
+    def paths_clear(self):
+        raise NotImplementedError("paths_clear: pathwise posterior draws are not built for distributed GPs (gmb_paths_prepare needs the complete factor of a single-engine factorisation)")
+
     # -- introspection: the resident state is replicated, the single-engine accessors apply ------------
     def notpd_index(self):
         return self.eng.notpd_index()

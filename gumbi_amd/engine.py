@@ -376,6 +376,12 @@ _SIGNATURES = {
     "gmb_predict_batches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "gmb_debug_batch_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]),
+    "gmb_paths_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gmb_paths_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_paths_eval_own": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gmb_paths_clear": (C.c_int, [C.c_void_p]),
+    "gmb_paths_count": (C.c_int32, [C.c_void_p]),
+    "gmb_debug_paths_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]),
     "gmb_fitc_set_inducing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     "gmb_fitc_evaluate": (C.c_int, [C.c_void_p, _DBL_P, C.c_int32, _DBL_P, _DBL_P]),
     "gmb_fitc_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -438,7 +444,8 @@ def _preload_hip_runtime():
 #: the host-only ``gmb_debug_design_plan``, and the sparse path ``gmb_fitc_*``, and GP classification by the Laplace approximation,
 #: ``gmb_laplace_*`` with the status ``GMB_ENOCONV``, the struct ``gmb_laplace_stats`` and the host-only ``gmb_debug_laplace_plan``,
 #: and the joint posteriors of many small batches with their derivatives, ``gmb_predict_batches`` with the host-only
-#: ``gmb_debug_batch_plan``)
+#: ``gmb_debug_batch_plan``, and the pathwise posterior draws, ``gmb_paths_prepare`` / ``gmb_paths_eval`` / ``gmb_paths_eval_own`` /
+#: ``gmb_paths_clear`` / ``gmb_paths_count`` with the host-only ``gmb_debug_paths_plan``)
 ABI_VERSION = 16
 
 #: points per task of ``gmb_predict_groups`` (csrc/group_tasks.hpp)
@@ -521,6 +528,8 @@ class Engine:
         self.spec = None
         self.N = 0
         self.D = 0
+        #: advanced by every :meth:`paths_prepare` and :meth:`paths_clear`: the identity of the ONE set of pathwise draws the engine holds
+        self.paths_generation = 0
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -922,6 +931,73 @@ class Engine:
                     "gmb_predict_batches")
         return (mean, cov, dmean, dcov) if grad else (mean, cov)
 
+    # -- pathwise posterior draws (csrc/pathwise.hpp) ---------------------------------------------------------------------
+    def paths_prepare(self, omega, phase, w, eps):
+        """Prepare ``S`` posterior function draws (``gmb_paths_prepare``; the arrays are :func:`gumbi_amd.pathwise.path_inputs`'s):
+        ``omega (F, Dc)`` frequencies in the prepared coordinates, ``phase (F,)``, ``w (S, F)`` and ``eps (S, N)`` standard
+        normals.  One solve with ``S`` right-hand sides against the resident factor; the state stays on the device until the
+        data, theta or the factor change.  ``ValueError`` for a model outside the scope (linear or categorical dimensions,
+        several outputs, additive, periodic), ``1 <= S <= 512``, ``1 <= F <= 16384``.  Leaves the factor and everything a fit
+        left beside it untouched.
+
+        Returns the set's generation: :attr:`paths_generation`, which every preparation and :meth:`paths_clear` advance -- an
+        engine holds ONE set, and whoever keeps a handle on a set (``PosteriorPaths``) compares it to know whether the set is
+        still the engine's."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        if omega.ndim == 1:
+            omega = omega[:, None]
+        phase = np.ascontiguousarray(phase, dtype=np.float64).ravel()
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if w.ndim != 2 or eps.ndim != 2 or omega.ndim != 2:
+            raise ValueError("paths_prepare: omega must be (F, Dc), w (S, F) and eps (S, N)")
+        S, F = w.shape
+        if omega.shape[0] != F or phase.shape != (F,) or eps.shape != (S, self.N) or omega.shape[1] != len(self.spec.idx_cont):
+            raise ValueError(f"paths_prepare: omega {omega.shape}, phase {phase.shape}, w {w.shape}, eps {eps.shape} do not fit "
+                             f"(F, {len(self.spec.idx_cont)}), (F,), (S, F), (S, {self.N})")
+        self.paths_generation += 1  # (before the call: a preparation that fails half-way has dropped the previous set as well)
+        self._check(self._lib.gmb_paths_prepare(self._h, S, F, _ptr(omega), _ptr(phase), _ptr(w), _ptr(eps)), "gmb_paths_prepare")
+        return self.paths_generation
+
+    @property
+    def n_paths(self) -> int:
+        """Draws of the prepared set (``gmb_paths_count``): the rows :meth:`paths_eval` returns; 0 when none are prepared."""
+        return int(self._lib.gmb_paths_count(self._h))
+
+    def paths_eval(self, Xs):
+        """All prepared draws at the rows of ``Xs``: ``(S, M)`` (``gmb_paths_eval``) -- draws of the LATENT function.  No
+        triangular pass and nothing of size M x N: ``M`` may be a whole grid.  ``ValueError`` when no paths are prepared or the
+        data, theta or the factor changed since."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        Y = np.empty((self.n_paths, M), dtype=np.float64)  # (the engine's own count: whoever prepared the set)
+        self._check(self._lib.gmb_paths_eval(self._h, _ptr(Xs), M, self.D, _ptr(Y), M, GMB_HOST), "gmb_paths_eval")
+        return Y
+
+    def paths_eval_own(self, Xs, draw, grad=True):
+        """Row ``m`` of ``Xs`` on draw ``draw[m]`` only (``gmb_paths_eval_own``): ``(val (M,), grad (M, D))`` -- the gradient with
+        respect to the point, columns as :meth:`predict_grad` -- or ``(val, None)`` with ``grad=False``.  One call per objective
+        evaluation of a Thompson search over many draws and restarts."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError(f"points_array must be (M, {self.D}), got {Xs.shape}")
+        M = Xs.shape[0]
+        draw = np.ascontiguousarray(draw, dtype=np.int32).ravel()
+        if draw.shape != (M,):
+            raise ValueError(f"paths_eval_own: draw must hold one index per point ({M}), got {draw.shape}")
+        val = np.empty(M, dtype=np.float64)
+        g = np.empty((M, self.D), dtype=np.float64) if grad else None
+        self._check(self._lib.gmb_paths_eval_own(self._h, _ptr(Xs), M, self.D, _ptr(draw), _ptr(val), _ptr(g) if grad else None, self.D,
+                                                 GMB_HOST), "gmb_paths_eval_own")
+        return val, g
+
+    def paths_clear(self):
+        """Drop the prepared draws and free their device buffers (``gmb_paths_clear``)."""
+        self.paths_generation += 1
+        self._check(self._lib.gmb_paths_clear(self._h), "gmb_paths_clear")
+
     # -- sparse GPs: FITC on inducing points (csrc/fitc.hpp) ---------------------------------------------------------
     def set_inducing(self, Z):
         """The inducing points of the sparse approximation (``gmb_fitc_set_inducing``): ``Z`` is ``(m, D)``, columns as ``X``.
@@ -1312,6 +1388,25 @@ def batch_plan(N: int, Np: int, B: int, q: int) -> dict:
     plan = {k: int(v) for k, v in zip(keys, buf)}
     h = len(keys)
     plan["tiles"] = [tuple(int(v) for v in buf[h + 6 * t:h + 6 * t + 6]) for t in range(plan["ntile"])]
+    return plan
+
+
+def paths_plan(N: int, F: int, M: int, S: int, nacc: int = 2) -> dict:
+    """The plan of the pathwise calls for ``S`` draws of ``F`` features at ``M`` points behind ``N`` training points (host-only):
+    ``Sp`` (S padded to 16), ``draw_blocks`` of 64, ``N4`` / ``F4`` (the two parts of the contraction index, padded to 4), ``mt``
+    rows of the largest M-tile, ``ntile``, the doubles of the all-draws partials and of the own-draw partials for ``nacc``
+    accumulators, and the tiles ``(first point, points, padded points, point tiles of 16, chunk length, chunks, own-draw chunk
+    length, own-draw chunks)``.  ``ValueError`` for a request the calls refuse."""
+    lib = load_library()
+    n = int(lib.gmb_debug_paths_plan(int(N), int(F), int(M), int(S), int(nacc), None, 0))
+    if n < 0:
+        raise ValueError(f"gmb_debug_paths_plan: N = {N}, F = {F}, M = {M}, S = {S} is refused (code {-n})")
+    buf = np.empty(n, dtype=np.int64)
+    lib.gmb_debug_paths_plan(int(N), int(F), int(M), int(S), int(nacc), _ptr(buf), n)
+    keys = ("Sp", "draw_blocks", "N4", "F4", "mt", "ntile", "part_doubles", "own_part_doubles")
+    plan = {k: int(v) for k, v in zip(keys, buf)}
+    h = len(keys)
+    plan["tiles"] = [tuple(int(v) for v in buf[h + 8 * t:h + 8 * t + 8]) for t in range(plan["ntile"])]
     return plan
 
 

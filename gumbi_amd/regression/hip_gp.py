@@ -133,6 +133,57 @@ def _loaded_shared_objects() -> int:
 _PHDR_COUNTER = None
 
 
+class PosteriorPaths:
+    """A set of posterior function draws (:meth:`HipGP.draw_paths`): functions of the model's inputs that can be evaluated at any
+    points after the fact.  The state lives on the GP's engine, which holds ONE set: another ``draw_paths`` or
+    ``propose_thompson`` replaces it, and a refit or new data invalidate it -- this object's methods then raise ``ValueError``
+    rather than evaluate another set's draws."""
+
+    def __init__(self, gp, outputs, cont, cols, full, n_draws, generation):
+        self.gp, self.outputs, self.continuous_dims, self.n_draws = gp, outputs, cont, n_draws
+        self._cols, self._full = cols, full
+        self._engine, self._generation = gp.engine, generation  # the engine holds ONE set: this one while its generation stands
+
+    def _own_engine(self):
+        """The engine, if the set it holds is still this one: another ``draw_paths`` / ``propose_thompson``, a cleared set or a
+        rebuilt engine is a ``ValueError`` here (changed data, theta or factor are the engine's own to refuse)."""
+        eng = self.gp.engine
+        if eng is not self._engine or eng.paths_generation != self._generation:
+            raise ValueError("these posterior paths are stale: the GP has drawn another set (draw_paths, propose_thompson), cleared "
+                             "them or rebuilt its engine since; draw them again")
+        return eng
+
+    def at_points(self, points):
+        """All draws at a 1-D parray of ``points``: a parray of shape ``(n_draws, M)`` in standardized units, like
+        :meth:`HipGP.draw_point_samples`; also left in the GP's :attr:`predictions` / :attr:`predictions_X`."""
+        gp = self.gp
+        eng = self._own_engine()
+        points_array, _, _ = gp._prepare_points_for_prediction(points, output=self.outputs)
+        samples = eng.paths_eval(np.asarray(points_array, dtype=np.float64))
+        gp.predictions = gp.parray(**{self.outputs[0]: samples}, stdzd=True)
+        gp.predictions_X = points
+        return gp.predictions
+
+    def on_grid(self):
+        """All draws at the points :meth:`prepare_grid` defined, at any grid size: a parray of shape ``(n_draws, *grid shape)``."""
+        gp = self.gp
+        self._own_engine()
+        if gp.grid_points is None:
+            raise ValueError("Grid must first be specified with `prepare_grid`")
+        samples = self.at_points(gp.grid_points)
+        gp.predictions = samples.reshape(-1, *gp.grid_parray.shape)
+        gp.predictions_X = gp.predictions_X.reshape(gp.grid_parray.shape)
+        return gp.predictions
+
+    def value_and_grad(self, points_z, draw, grad=True):
+        """Point ``m`` of ``points_z`` -- ``(M, n_cont)`` STANDARDIZED continuous coordinates in ``continuous_dims`` order -- on
+        draw ``draw[m]`` only: ``(value (M,), gradient (M, n_cont))`` in standardized units (the gradient ``None`` with
+        ``grad=False``).  ONE ``engine.paths_eval_own`` call: the objective of a Thompson search."""
+        Z = np.asarray(points_z, float).reshape(-1, len(self.continuous_dims))
+        val, g = self._own_engine().paths_eval_own(self._full(Z), draw, grad=grad)
+        return val, (g[:, self._cols] if grad else None)
+
+
 class HipGP(Regressor):
     """Gaussian-process regression on an MI355X.  Drop-in for ``gumbi.GP`` on the
     ``fit() / prepare_grid() / predict_grid()`` path; see the module docstring."""
@@ -965,6 +1016,117 @@ class HipGP(Regressor):
         self.proposal_raw_acquisition = raw_value
         self.proposal_acquisition = float(value[best])
         self.proposal = self.parray(**{d: cand[best][:, k] for k, d in enumerate(cont)}, stdzd=True)
+        return self.proposal
+
+    # -- pathwise posterior draws: function samples and Thompson batches -----------------------------------------------------------
+    def _paths_problem(self, output, what):
+        """What :meth:`draw_paths` and :meth:`propose_thompson` share: the one output, the continuous dims with their columns
+        of a model point, and ``full(Z)`` as :meth:`_acquisition_problem` makes it (no categorical level to fix: models with
+        categorical dimensions are outside the pathwise draws' scope)."""
+        if self.distributed:
+            raise NotImplementedError(f"{what}: pathwise posterior draws are not built for distributed GPs (the factor is spread over ranks)")
+        if isinstance(self.engine, icm.IcmEngine):
+            raise NotImplementedError(f"{what}: pathwise posterior draws are not built for the Kronecker path (pass kronecker=False)")
+        if self.MAP is None or self.engine is None:
+            raise ValueError(f"The model must be fit (find_MAP) before {what}")
+        outputs = self._parse_prediction_output(output)
+        if len(outputs) != 1:
+            raise ValueError(f"{what} works on ONE output: pass output= one of {outputs}")
+        cont = list(self.continuous_dims)
+        cols = [self.dims.index(d) for d in cont]
+        template = self.parray(**{d: np.array([0.0]) for d in cont}, stdzd=True)
+        row, _, _ = self._prepare_points_for_prediction(template, output=outputs)
+        row = np.asarray(row, float)[0]
+
+        def full(Z):
+            P = np.tile(row, (len(Z), 1))
+            P[:, cols] = Z
+            return P
+
+        return outputs, cont, cols, full
+
+    def draw_paths(self, n_draws=16, n_features=2048, seed=None, antithetic=False, output=None):
+        """``n_draws`` posterior FUNCTION draws (:class:`PosteriorPaths`) by pathwise conditioning (Matheron's rule; DESIGN
+        §3.20): a prior draw from ``n_features`` random Fourier features plus an exact-kernel update against the data, prepared
+        by one solve with ``n_draws`` right-hand sides against the factor :meth:`find_MAP` left resident.  Afterwards a draw is
+        a function: it can be evaluated at any points, any number of times, at O(N + n_features) per point and draw -- on a
+        whole :meth:`prepare_grid` grid, where :meth:`draw_grid_samples` needs the grid's joint covariance.  The draws are of
+        the latent function (no observation noise).  The random-feature prior is an approximation (error O(1 / sqrt(n_features))
+        in the prior covariance); the data term uses the exact kernel.  Reproducible from ``seed`` (default: the GP's);
+        ``antithetic=True`` draws in pairs that mirror each other around the posterior mean.
+
+        The paths live on the engine until the model is refit, conditioned on new data or another set is drawn: one set at a
+        time.  One stationary kernel over the continuous dimensions only (no linear or categorical dimensions, one output, not
+        additive, not periodic): anything else is refused."""
+        from .. import pathwise
+
+        outputs, cont, cols, full = self._paths_problem(output, "draw_paths")
+        spec = self.model.spec
+        omega, phase, w, eps = pathwise.path_inputs(spec.kind, int(n_draws), int(n_features), len(spec.idx_cont), len(self.model.y),
+                                                    self.seed if seed is None else seed, antithetic=antithetic)
+        generation = self.engine.paths_prepare(omega, phase, w, eps)
+        return PosteriorPaths(self, outputs, cont, cols, full, int(n_draws), generation)
+
+    def propose_thompson(self, q, output=None, maximize=True, bounds=None, num_restarts=10, raw_samples=512, n_features=2048, seed=None,
+                         **optim_kwargs):
+        """A batch of ``q`` points by Thompson sampling: ``q`` posterior function draws (:meth:`draw_paths`), each maximised (or
+        minimised) over the continuous inputs inside ``bounds`` -- a plate-sized batch at the cost of ONE solve, where
+        :meth:`propose_batch` stops at 16 points and the greedy batch of :meth:`propose_continuous` pays a bordered update and a
+        search per pick.
+
+        ONE ``engine.paths_eval`` call scores ``raw_samples`` seeded uniform points under all ``q`` draws; the best
+        ``num_restarts`` of each draw become its starts; all ``q x num_restarts`` starts are optimised in lock step by one
+        L-BFGS-B run over their coordinates, every objective evaluation ONE ``engine.paths_eval_own`` call.  Per draw the best
+        of its optimised points and its starts is returned: a parray of ``q`` points in natural units, also in
+        :attr:`proposal`; :attr:`proposal_acquisition` holds each point's value under its own draw (standardized units),
+        :attr:`proposal_raw_acquisition` the raw samples' ``(q, raw_samples)`` values, :attr:`proposal_result` scipy's result.
+        Bounds and the choice of ``output`` follow :meth:`propose_continuous`; remaining ``optim_kwargs`` go to L-BFGS-B's
+        ``options``."""
+        from scipy.optimize import minimize
+
+        q = int(q)
+        if q < 1 or q > 512:
+            raise ValueError(f"propose_thompson: q must be 1 .. 512, got {q}")
+        rng = np.random.default_rng(self.seed if seed is None else seed)
+        paths = self.draw_paths(q, n_features=n_features, seed=int(rng.integers(2**31 - 1)), output=output)
+        cont, cols, full = paths.continuous_dims, paths._cols, paths._full
+        nc = len(cont)
+        num_restarts, raw_samples = int(num_restarts), max(int(raw_samples), int(num_restarts))
+        if bounds is None:
+            Xc = np.asarray(self.model.X, float)[:, cols]
+            lo, hi = Xc.min(axis=0), Xc.max(axis=0)
+        else:
+            bz = bounds.z
+            both = np.array([np.asarray(bz[d + "_z"].values(), float).ravel() for d in cont])
+            if both.shape != (nc, 2):
+                raise ValueError("bounds must hold two entries (lower, upper) per continuous dimension")
+            lo, hi = both.min(axis=1), both.max(axis=1)
+        self.optimization_bounds = (lo.copy(), hi.copy())
+        options = {"maxiter": 200, **optim_kwargs.pop("options", {}), **optim_kwargs}
+        sign = 1.0 if maximize else -1.0
+
+        raw = lo + (hi - lo) * rng.random((raw_samples, nc))
+        raw_value = paths._own_engine().paths_eval(full(raw))  # (q, raw_samples)
+        order = np.argsort(-sign * raw_value, axis=1, kind="stable")[:, :num_restarts]
+        starts = raw[order]  # (q, num_restarts, nc)
+        draw = np.repeat(np.arange(q, dtype=np.int32), num_restarts)
+
+        def objective(z):
+            value, grad = paths.value_and_grad(z.reshape(q * num_restarts, nc), draw)
+            return -sign * float(np.sum(value)), -sign * grad.ravel()
+
+        res = minimize(objective, starts.ravel(), jac=True, method="L-BFGS-B",
+                       bounds=list(zip(np.tile(lo, q * num_restarts), np.tile(hi, q * num_restarts))), options=options)
+        cand = np.clip(np.concatenate([res.x.reshape(q, num_restarts, nc), starts], axis=1), lo, hi)  # (q, 2 num_restarts, nc)
+        value, _ = paths.value_and_grad(cand.reshape(-1, nc), np.repeat(np.arange(q, dtype=np.int32), 2 * num_restarts), grad=False)
+        value = value.reshape(q, 2 * num_restarts)
+        best = np.argmax(sign * value, axis=1)
+        picks = cand[np.arange(q), best]
+        self.proposal_result = res
+        self.proposal_raw_acquisition = raw_value
+        self.proposal_acquisition = value[np.arange(q), best]
+        self.proposal_paths = paths
+        self.proposal = self.parray(**{d: picks[:, k] for k, d in enumerate(cont)}, stdzd=True)
         return self.proposal
 
     def _shaped_rows(self):

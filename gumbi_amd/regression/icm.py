@@ -281,6 +281,18 @@ class IcmEngine:
         raise NotImplementedError("predict_batches: the joint posteriors of batches and their derivatives are not built for the "
                                   "Kronecker engine (pass kronecker=False)")
 
+    def paths_prepare(self, omega, phase, w, eps):
+        raise NotImplementedError("paths_prepare: pathwise posterior draws are not built for the Kronecker engine (pass kronecker=False)")
+
+    def paths_eval(self, Xs):
+        raise NotImplementedError("paths_eval: pathwise posterior draws are not built for the Kronecker engine (pass kronecker=False)")
+
+    def paths_eval_own(self, Xs, draw, grad=True):
+        raise NotImplementedError("paths_eval_own: pathwise posterior draws are not built for the Kronecker engine (pass kronecker=False)")
+
+    def paths_clear(self):
+        raise NotImplementedError("paths_clear: pathwise posterior draws are not built for the Kronecker engine (pass kronecker=False)")
+
     def predict(self, Xs, with_noise=True, terms=None):
         _no_terms(terms, "predict(terms=...)")
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

@@ -96,7 +96,7 @@ class HipSparseGP(HipGP):
                  "predict_grid_slope", "acquisition_with_grad", "propose_continuous", "condition_on", "predict_joint",
                  "draw_point_samples", "draw_grid_samples", "decompose_points", "decompose_grid", "leave_one_out", "leave_group_out",
                  "predict_groups", "predict_average", "marginal_design", "predict_marginal", "compare_levels", "design_batch",
-                 "variance_reduction", "batch_acquisition_with_grad", "propose_batch")
+                 "variance_reduction", "batch_acquisition_with_grad", "propose_batch", "draw_paths", "propose_thompson")
 
     def __init__(self, dataset, outputs=None, seed=2021, device=0, distributed=None, kronecker=False):
         if distributed:

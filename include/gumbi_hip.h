@@ -559,6 +559,40 @@ int gmb_predict_batches(gmb_engine* e, const double* Xs, int64_t B, int32_t q, i
  * 128 that holds N, 4 B q > 2^40. */
 int64_t gmb_debug_batch_plan(int64_t N, int64_t Np, int64_t B, int32_t q, int64_t* out, int64_t cap);
 
+/* ---- pathwise posterior draws: function samples by Matheron's rule (ABI stays 16: new functions only, no change of layout) ------------
+ * csrc/pathwise.hpp, csrc/paths_plan.hpp.  For draw s, with a prior draw from F random Fourier features in the prepared coordinates
+ * u = x / ls,
+ *   f_s(x) = phi(x)^T w_s + k(x, X) a_s,   a_s = Sigma^-1 (y - Phi(X) w_s - d o eps_s),   phi_f(x) = eta sqrt(2 / F) cos(omega_f^T u + b_f),
+ * d^2 = sigma^2 + jitter, exactly the diagonal the covariance build adds to K.  The draws are of the LATENT function.
+ * gmb_paths_prepare: omega F x Dc row-major (Dc continuous dimensions, in the order of the kernel's idx_cont), phase F, w S x F and
+ * eps S x N standard normals, all HOST arrays.  Forms A = Sigma^-1 R for all S draws with a prediction's two triangular passes
+ * against the resident factor and keeps it on the device, tied to the factorisation: any later call that changes data, theta or
+ * the factor makes the paths stale (GMB_EINVAL from the evaluations).  1 <= S <= 512, 1 <= F <= 16384.  Readiness is
+ * gmb_predict_batches's (a current single-engine factor); GMB_EINVAL -- nothing launched, nothing written -- also for models with
+ * linear dimensions, coregion tables (categorical dimensions, an output column), additive or periodic models.  The factor, both
+ * alphas, U, the inverse factor and the joint state are left as found.
+ * gmb_paths_eval: all S draws at the M rows of Xs (leading dimension ldxs >= D, in `memspace`): Y is S x M row-major with leading
+ * dimension ldy >= M.  No triangular pass, nothing of size M x N: M is walked in tiles of 65536 points.
+ * gmb_paths_eval_own: point m on draw draw[m] (int32, in `memspace`, in [0, S): anything else is GMB_EINVAL before any launch) only:
+ * val M values and, unless grad is NULL, grad M x D with leading dimension ldg >= D (columns that are no continuous dimension: 0).
+ * Fixed-order sums, no atomics: the same bits call after call.  M == 0 is GMB_OK; a request the device cannot hold returns
+ * GMB_ENOMEM before any launch.  gmb_paths_clear drops the state and frees its buffers. */
+int gmb_paths_prepare(gmb_engine* e, int32_t S, int32_t F, const double* omega, const double* phase, const double* w, const double* eps);
+int gmb_paths_eval(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, double* Y, int64_t ldy, int32_t memspace);
+int gmb_paths_eval_own(gmb_engine* e, const double* Xs, int64_t M, int64_t ldxs, const int32_t* draw, double* val, double* grad, int64_t ldg,
+                       int32_t memspace);
+int gmb_paths_clear(gmb_engine* e);
+/* S of the prepared draws (the rows gmb_paths_eval writes), 0 when none are prepared; a stale set still counts until it is replaced
+ * or cleared. */
+int32_t gmb_paths_count(gmb_engine* e);
+/* Host only: the plan of the pathwise calls for S draws of F features at M points behind N training points.  Writes at most `cap`
+ * values to `out` (may be NULL) and returns how many there are: Sp (S padded to 16), draw blocks of 64, N and F padded to 4, rows
+ * of the largest M-tile, M-tiles, doubles of the all-draws partials, doubles of the own-draw partials for `nacc` accumulators;
+ * then per tile (first point, points, padded points, point tiles of 16, chunk length and chunks of the all-draws kernel, chunk
+ * length and chunks of the own-draw kernel).  A refusal returns -(code): 1 S outside 1 .. 512, 2 F outside 1 .. 16384, 3 M < 1 or
+ * beyond 2^40, 4 N < 1 or beyond 2^40. */
+int64_t gmb_debug_paths_plan(int64_t N, int64_t F, int64_t M, int64_t S, int32_t nacc, int64_t* out, int64_t cap);
+
 /* ---- sparse GPs: the FITC approximation on m inducing points (ABI stays 16: new functions only, no change of layout) -----------------
  * PyMC's MarginalSparse(approx="FITC") (gumbi/regression/pymc/GP.py:571-591, fit(sparse=True, n_u=...)), csrc/fitc.hpp.  With Z the
  * m inducing points and k the model's covariance without noise:
